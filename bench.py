@@ -6,6 +6,7 @@
     python bench.py --gpus N --mode train                    (cfg4: fwd + bwd + RCCL gradient all-reduce)
     python bench.py --gpus N --config cfg3                   (BASELINE configs[2]: 64 RoI crops 96^3 sharded over N ranks)
     python bench.py --headline-only                          (the headline leg + roofline + cpu_baseline, nothing else)
+    python bench.py ... --dump-outputs DIR                   (also writes the last timed step's output as DIR/cost.npy)
 
 Workload (N=1): BASELINE.json configs[1], "Global scene model: 1242x375, 192 disparities, full 3D hourglass fwd, batch=1 on 1
 MI355X", synthesised as SURVEY.md section 8(d) cfg2: left/right features [1,32,96,312] (1242x375 padded to 1248x384, stride 4),
@@ -70,7 +71,33 @@ def parse_args(argv=None):
     ap.add_argument("--sustained-steps", type=int, default=2000)
     ap.add_argument("--rehearse", action="store_true",
                     help="launch / timing-protocol / output rehearsal on the CPU (gloo group, a sleep as the step): NOT a measurement")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the headline step's output of its last timed step as DIR/<name>.npy (rank 0; fixed seeded inputs and "
+                         "weights, so two builds can be compared output for output)")
+    args = ap.parse_args(argv)
+    if args.dump_outputs and (args.rehearse or args.mode != "infer" or args.config != "cfg2"):
+        ap.error("--dump-outputs covers the headline step (--mode infer --config cfg2) only")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays):
+    """``arrays``: name -> numpy array, written as ``path/<name>.npy`` in float32 (float64 stays float64); at most 64 MB in all."""
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return {name: {"shape": list(a.shape), "dtype": str(a.dtype)} for name, a in out.items()}
 
 
 def rehearse(args, rank, world):
@@ -297,6 +324,9 @@ def main(argv=None):
     from benchlib.headline import Headline
     hd = Headline(args, rank, world, device, dist, barrier)
     hd.run_core()
+    if args.dump_outputs and rank == 0:
+        # forward_pair's return value in the last of the K timed steps of `value`: the cost volume [1, 1, D, H, W] a caller receives
+        emit.rank_note("dump_outputs", {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {"cost": hd.outs["value"]})})
     records = hd.all_rank_records(joined)
     emit.rank_note("rank_record", hd.rank_record(joined))         # every rank leaves its own line on stderr (prefixed: not JSON)
     line = hd.core_line(joined) if rank == 0 else None

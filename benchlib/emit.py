@@ -89,7 +89,11 @@ def _parses(text):
 
 def rank_note(tag, obj, stream=None):
     """One line of a rank's own record (any rank): ``[tag] {json}`` on stderr -- readable, greppable, never the result line."""
-    print(_prefixed(tag, obj), file=stream or sys.stderr, flush=True)
+    # one write() for the line AND its newline: print() issues two, and stderr passes each straight to the descriptor, so the ranks
+    # of one job sharing a pipe could land a record between another rank's text and its newline
+    s = stream or sys.stderr
+    s.write(_prefixed(tag, obj) + "\n")
+    s.flush()
 
 
 def detail_note(obj, root=None, stream=None):

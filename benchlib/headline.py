@@ -71,7 +71,9 @@ class Headline:
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
             elapsed = float(t.item())
         assert torch.isfinite(out).all()
-        self.outs[tag] = out.cpu().numpy() if self.rank == 0 and self.world == 1 else None    # 23 MB, compared with the CPU oracle
+        # 23 MB, compared with the CPU oracle (N = 1) and written by --dump-outputs (rank 0, any N)
+        keep = self.rank == 0 and (self.world == 1 or getattr(a, "dump_outputs", None))
+        self.outs[tag] = out.cpu().numpy() if keep else None
         return elapsed
 
     def leg(self, tag, factored=True, sheared=True, commuted=True, arithmetic=None, brackets=("volume", "conv1", "conv2")):

@@ -2,7 +2,8 @@
 """Golden vectors of `points_in_boxes_cpu` from the REFERENCE'S OWN compiled C++ (oracle/_ref, built by `make -C oracle ref` from
 /root/reference/snvc/extension/roiaware_pool3d/src/roiaware_pool3d.cpp:121-168 where it lies).  Run where /root/reference exists:
     make -C oracle ref && python tests/golden/make_golden_ref_native.py
-Writes tests/golden/points_in_boxes_cpu_ref.npz: inputs + the reference's outputs (data only)."""
+Writes tests/golden/points_in_boxes_cpu_ref.npz (the edge cases) and tests/golden/points_in_boxes_cpu_ref_trials.npz (five seeded
+random scenes): inputs + the reference's outputs (data only)."""
 import os
 import sys
 
@@ -45,9 +46,33 @@ def cases():
     return out
 
 
+def trials():
+    """Five random scenes, seed 7: boxes anywhere in a 20 m cube, points scattered around their centres."""
+    rng = np.random.default_rng(7)
+    out = []
+    for _ in range(5):
+        nb, npts = int(rng.integers(1, 40)), int(rng.integers(1, 3000))
+        boxes = np.concatenate([rng.uniform(-10, 10, (nb, 3)), rng.uniform(0.2, 6, (nb, 3)), rng.uniform(-7, 7, (nb, 1))], 1).astype(np.float32)
+        pts = (boxes[rng.integers(0, nb, npts), :3] + rng.normal(0, 1.5, (npts, 3))).astype(np.float32)
+        out.append((pts, boxes))
+    return out
+
+
+def write_trials():
+    blob = {}
+    for t, (pts, boxes) in enumerate(trials()):
+        blob[f"{t}_pts"], blob[f"{t}_boxes"] = pts, boxes
+        blob[f"{t}_flags"] = R.points_in_boxes_cpu(pts, boxes)
+        print("trial", t, pts.shape, boxes.shape, "flags set:", int(blob[f"{t}_flags"].sum()))
+    path = os.path.join(ROOT, "tests", "golden", "points_in_boxes_cpu_ref_trials.npz")
+    np.savez_compressed(path, **blob)
+    print("wrote", path, os.path.getsize(path), "bytes")
+
+
 def main():
     if not R.available():
         sys.exit("oracle/_ref/snvc_ref_roiaware.so missing: run `make -C oracle ref`")
+    write_trials()
     blob = {}
     for k, (pts, boxes) in cases().items():
         blob[f"{k}_pts"], blob[f"{k}_boxes"] = pts, boxes

@@ -135,3 +135,22 @@ def test_committed_gpu_capture_parses():
         assert c["value"] > 0 and c["cores"] >= 1 and c["kind"] in ("port", "reference") and c["sample"]
         assert last["value"] > 0 and abs(last["value"] * last["ms_per_step"] / 1e3 / last["n_gpus"] - 1.0) < 1e-6
         assert last["dtype"].startswith("f32") and last["value_fp32_mfma"] > 0
+
+
+def test_dump_outputs_writes_float_npy_within_the_limit(tmp_path):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 kept), and nothing at all beyond 64 MB in all."""
+    import numpy as np
+    import bench
+    got = bench.dump_outputs(str(tmp_path / "d"), {"cost": np.arange(6, dtype=np.float16).reshape(2, 3), "x": np.zeros(4)})
+    assert got == {"cost": {"shape": [2, 3], "dtype": "float32"}, "x": {"shape": [4], "dtype": "float64"}}
+    a = np.load(tmp_path / "d" / "cost.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, np.arange(6).reshape(2, 3))
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT_BYTES // 4 + 1, np.float32)})
+    assert not (tmp_path / "big").exists()
+
+
+def test_dump_outputs_is_refused_where_there_is_no_headline_step():
+    for extra in (["--rehearse"], ["--mode", "train"], ["--config", "cfg3"]):
+        rc, out, err = _run(["--steps", "2", "--warmup", "1", "--dump-outputs", "unused"] + extra)
+        assert rc == 2 and "--dump-outputs" in err, (extra, err[-500:])
