@@ -3,11 +3,12 @@
 
     snvc_amd.extension.build_cost_volume   <->  snvc.extension.build_cost_volume
     snvc_amd.extension.roiaware_pool3d     <->  snvc.extension.roiaware_pool3d
+    snvc_amd.extension.iou3d_nms           <->  snvc.extension.iou3d_nms
     snvc_amd.models.submodule              <->  snvc.models.submodule (3D blocks)
     snvc_amd.models.vernier                <->  snvc.models.vernier   (VernierScale 3D trunk)
 
 Everything executes in hand-written HIP kernels from ``libsnvc_hip.so`` (C ABI:
-``include/snvc_hip.h``).  There is no CPU path: CPU tensors raise, and a missing shared
+``include/snvc_hip.h``, ``include/snvc_iou3d.h``).  There is no CPU path: CPU tensors raise, and a missing shared
 library raises at first use.
 """
 __version__ = "0.1.0"
@@ -16,6 +17,7 @@ __version__ = "0.1.0"
 _ALIASES = {
     "snvc.extension.build_cost_volume": "snvc_amd.extension.build_cost_volume",
     "snvc.extension.roiaware_pool3d.roiaware_pool3d_utils": "snvc_amd.extension.roiaware_pool3d.roiaware_pool3d_utils",
+    "snvc.extension.iou3d_nms.iou3d_nms_utils": "snvc_amd.extension.iou3d_nms.iou3d_nms_utils",
     "snvc.models.submodule": "snvc_amd.models.submodule",
     "snvc.models.vernier": "snvc_amd.models.vernier",
 }
