@@ -12,6 +12,7 @@ from torch.autograd import Function
 from torch.autograd.function import once_differentiable
 
 from ... import ops
+from ..._derived import stamp
 
 # Stands where the reference's pybind module sits (BuildCostVolume.cpp:44-48): same two names.
 build_cost_volume_cuda = types.SimpleNamespace(
@@ -71,12 +72,11 @@ def build_cost_volume(left, right, shift, downsample):
         except Exception:        # Unsupported shape, misaligned view, workspace OOM, ...: not this function's errors
             gen = None
         if gen is not None:
-            w = model.conv1[0][0].weight
             seen = model.conv1[0][0].__dict__["_snvc_factored"].get("spacing_seen")      # (q, m0, D, W) of THIS shift array, or ("general", D, W)
             stream = torch.cuda.current_stream(left.device).cuda_stream
             return LazyCostVolume(left, right, shift, downsample, build_cost_volume_cuda.build_cost_volume_forward,
                                   tuple(seen[:2]) if (seen is not None and seen[0] != "general") else None,
-                                  prefetch=(ref, gen, (w.data_ptr(), w._version, stream)))
+                                  prefetch=(ref, gen, stamp((model.conv1[0][0].weight,), (stream,))))
     if shift.dtype == torch.float32 and shift.numel() > 0:
         # reference __init__.py:12, at the same point of the call sequence and with the same single sync; the launch also
         # classifies the array's spacing, which GlobalStack.forward_pair would otherwise sync for a second time

@@ -15,6 +15,8 @@ from torch.utils._pytree import tree_map
 
 import threading
 
+from ._derived import fresh
+
 
 class _Consumer(threading.local):
     """Weakref to the GlobalStack that consumed the last lazy volume on the fused path IN THIS THREAD (set by GlobalStack.forward): the
@@ -47,7 +49,7 @@ class LazyCostVolume(torch.Tensor):
         r._spacing = spacing
         r._source_versions = (left._version, right._version, shift._version)
         r._own_version = r._version      # in-place aten operators on the wrapper bump ITS counter (above __torch_dispatch__)
-        r._prefetch = prefetch           # (weakref to the model, its paused step, the weight version it was started with) or None
+        r._prefetch = prefetch           # (weakref to the model, its paused step, the stamp of the weight and stream it started with) or None
         return r
 
     def take_prefetch(self, model):
@@ -58,10 +60,9 @@ class LazyCostVolume(torch.Tensor):
         pre, self._prefetch = self._prefetch, None
         if pre is None:
             return None
-        ref, gen, wver = pre
-        w = model.conv1[0][0].weight
+        ref, gen, st = pre
         stream = torch.cuda.current_stream(self.device).cuda_stream
-        if ref() is not model or wver != (w.data_ptr(), w._version, stream):
+        if ref() is not model or not fresh(st, (model.conv1[0][0].weight,), (stream,)):
             gen.close()
             return None
         return gen

@@ -23,11 +23,23 @@ import torch.nn as nn
 
 from ..extension.build_cost_volume import _BuildCostVolume, build_cost_volume  # noqa: F401  (re-exported)
 from .. import ops
-from .submodule import (_GENERATION, _ROUTES, ConvBNReLU3d, HipConv3d, SplitOverflow, _FactoredFirstConvFn, _ShearedFirstConvBNFn,
+from .._derived import derived, fresh, stamp
+from .submodule import (_ROUTES, ConvBNReLU3d, HipConv3d, SplitOverflow, _FactoredFirstConvFn, _ShearedFirstConvBNFn,
                         _ShearedFirstConvFn, _folded_bn, _is_channel_head as _is_head_conv, _Plan, convbn_3d, folded_head_weights,
                         hourglass, overflow_guard, sheared_geometry, sheared_kernels, EPI_RELU)
 
 _PREP_EPOCH = itertools.count(1)      # stamps of the per-model first-layer prep buffers (see _forward_pair_steps)
+
+
+def _factored_plans(conv: nn.Module, c: int) -> dict:
+    """The factored first layer's packed right half ("right"), its folded-BatchNorm plan ("plan") and what the routes add to the
+    dict lazily: all of it rebuilt when the weight changes."""
+    plans = conv.__dict__.get("_snvc_factored")
+    if plans is None or not fresh(plans["stamp"], (conv.weight,)):
+        w = conv.weight
+        plans = conv.__dict__["_snvc_factored"] = {"stamp": stamp((w,)), "plan": _Plan(),
+                                                   "right": ops.Conv3dLayer(w.detach()[:, c:].contiguous(), 3, 1, 1, 1, False)}
+    return plans
 
 
 class GlobalStack(nn.Module):
@@ -144,9 +156,8 @@ class GlobalStack(nn.Module):
         tensors = [t for sq in list(seqs.values()) + [hg.conv6] for t in (sq[0].weight, sq[1].weight, sq[1].bias, sq[1].running_mean, sq[1].running_var)]
         tensors.append(self.classifier.weight)
         tensors += [self.conv1[0][1].weight, self.conv1[0][1].bias, self.conv1[0][1].running_mean, self.conv1[0][1].running_var]
-        key = tuple((t.data_ptr(), t._version) for t in tensors if t is not None) + (device, _GENERATION[0])
         st = self.__dict__.get("_snvc_x3")
-        if st is not None and st["key"] == key:
+        if st is not None and fresh(st["stamp"], tensors, (device,)):
             return st
 
         def bound(nm):
@@ -154,7 +165,7 @@ class GlobalStack(nn.Module):
             b = nm.bias.detach().abs() if nm.bias is not None else torch.zeros(1, device=device)
             return float((b + self.X3_SIGMAS * g).max().item())
         b = {k: bound(sq[1]) for k, sq in seqs.items()}
-        st = {"key": key, "exp": {"v1": self._x3_exponent(bound(self.conv1[0][1]))}, "layers": {}, "affine": {}}
+        st = {"stamp": stamp(tensors, (device,)), "exp": {"v1": self._x3_exponent(bound(self.conv1[0][1]))}, "layers": {}, "affine": {}}
         st["exp"].update({k: self._x3_exponent(v) for k, v in b.items()})
         geo = {"conv2": (1, False), "h1": (2, False), "h2": (1, False), "h3": (2, False), "h4": (1, False), "h5": (2, True)}
         for k, sq in seqs.items():
@@ -195,11 +206,7 @@ class GlobalStack(nn.Module):
     def _x3_v1_affine(st, scale, bias):
         """The first layer's folded BatchNorm with the exponent of the split first-layer tensor folded in (exact: a power of two)."""
         e1 = st["exp"]["v1"]
-        src = st.get("v1_affine_src")      # the folded tensors themselves are kept: an address cannot come back as another tensor
-        if src is None or src[0] is not scale or src[1] is not bias or src[2] != (scale._version, bias._version, e1):
-            st["v1_affine"] = ((scale * 2.0 ** e1).contiguous(), (bias * 2.0 ** e1).contiguous())
-            st["v1_affine_src"] = (scale, bias, (scale._version, bias._version, e1))
-        return st["v1_affine"]
+        return derived(st, "v1_affine", (scale, bias), lambda: ((scale * 2.0 ** e1).contiguous(), (bias * 2.0 ** e1).contiguous()))
 
     def _x3_select(self, device, arithmetic=None):
         """The split-mode state if this call runs in split mode, else None."""
@@ -407,11 +414,7 @@ class GlobalStack(nn.Module):
         left_s = left[:, :, ::ds, ::ds].contiguous()
         right_r = right[:, :, ::ds, :].contiguous()          # rows ds*h; every input column
         wt = conv.weight
-        plans = conv.__dict__.setdefault("_snvc_factored", {})
-        key = (wt.data_ptr(), wt._version, wt.device, _GENERATION[0])
-        if plans.get("key") != key:
-            plans.clear()
-            plans.update(key=key, right=ops.Conv3dLayer(wt.detach()[:, c:].contiguous(), 3, 1, 1, 1, False), plan=_Plan())
+        plans = _factored_plans(conv, c)
         scale, bias = _folded_bn(bn, plans["plan"])
         planes = self._left_planes_layer(plans, wt.detach()[:, :c])(left_s.unsqueeze(2)).view(n, c, 3, h, w)
         if phases == 2:
@@ -457,11 +460,7 @@ class GlobalStack(nn.Module):
             return None
         q, m0 = structure
         wt = conv.weight
-        plans = conv.__dict__.setdefault("_snvc_factored", {})
-        key = (wt.data_ptr(), wt._version, wt.device, _GENERATION[0])
-        if plans.get("key") != key:
-            plans.clear()
-            plans.update(key=key, right=ops.Conv3dLayer(wt.detach()[:, c:].contiguous(), 3, 1, 1, 1, False), plan=_Plan())
+        plans = _factored_plans(conv, c)
         planes = self._left_planes_layer(plans, wt.detach()[:, :c])(left.unsqueeze(2)).view(n, c, 3, h, w)
         lay_g, lay_col = self._sheared_layers(plans, wt.detach()[:, c:], q)
         off, wu, off_col, wu_col = sheared_geometry(q, m0, d, w)
@@ -842,12 +841,7 @@ class GlobalStack(nn.Module):
             assert torch.all(shift >= 0.)
         c = left.size(1)
         w = conv.weight
-        plans = conv.__dict__.setdefault("_snvc_factored", {})
-        key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-        if plans.get("key") != key:
-            wr = w.detach()[:, c:].contiguous()
-            plans.clear()
-            plans.update(key=key, right=ops.Conv3dLayer(wr, 3, 1, 1, 1, False), plan=_Plan())
+        plans = _factored_plans(conv, c)
         scale, bias = _folded_bn(bn, plans["plan"])
         # the first layer's small 2D convolutions run in split mode whenever the stack behind them does (same arithmetic contract:
         # fp32 accuracy on the half pipe); `arithmetic="fp32"` keeps every layer on the fp32-MFMA kernels
@@ -942,11 +936,8 @@ class GlobalStack(nn.Module):
             # resumed by GlobalStack.forward(volume).  Anything may have run on this model in between -- another build_cost_volume (two
             # pending volumes), a forward_pair, a parameter update: if the prep buffers are no longer this step's own, or the folded
             # first-layer parameters moved, the step starts over from its inputs (the shift array's answer stays: it was checked)
-            w_now = conv.weight
-            fresh = (self.__dict__.get("_snvc_prep_epoch") == epoch and plans.get("key") == key
-                     and (w_now.data_ptr(), w_now._version, w_now.device, _GENERATION[0]) == key
-                     and all(a is b for a, b in zip(_folded_bn(bn, plans["plan"]), (scale, bias))))
-            if not fresh:
+            if not (self.__dict__.get("_snvc_prep_epoch") == epoch and conv.__dict__.get("_snvc_factored") is plans
+                    and fresh(plans["stamp"], (conv.weight,)) and all(a is b for a, b in zip(_folded_bn(bn, plans["plan"]), (scale, bias)))):
                 _ROUTES["lazy_prefetch_stale"] += 1
                 return (yield from self._forward_pair_steps(left, right, shift, downsample, factored, timing, True, sheared, fused_bn,
                                                             structure, commuted, arithmetic, pause=False))

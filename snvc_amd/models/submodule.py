@@ -30,6 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from .. import ops
+from .._derived import derived, fresh, invalidate_all, stamp
 from ..ops import EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID
 
 
@@ -45,8 +46,6 @@ def _cubic(v, what):
     return int(v)
 
 
-_GENERATION = [0]   # bumped by invalidate_plans(): part of every cache key
-
 # How often each fused route was taken (tests assert on it: a silent regression to a slower or to a torch route shows)
 import collections
 import math
@@ -57,14 +56,14 @@ TRAIN_EXACT_K57 = [False]     # True: k5 / k7 layers under autograd on the direc
 def invalidate_plans(module: Optional[nn.Module] = None) -> None:
     """Drop the packed-weight / folded-BatchNorm / dgrad / factored-conv caches.
 
-    The caches are keyed on ``(data_ptr, tensor._version, device)``.  Every in-place update that goes
-    through autograd-visible tensors (``optimizer.step()``, ``load_state_dict``, ``p.copy_()`` under
-    ``no_grad``, ``p.detach().mul_()``) bumps ``_version`` and invalidates them by itself.  Writes through
-    ``.data`` (``p.data.mul_(2)``, an EMA swap that assigns ``.data`` storage in place) do NOT bump it: after
-    such a write call this function -- for one module tree, or with no argument for every model of the
-    process (a generation counter in the keys)."""
+    A cached value is valid while its source tensors are the same objects at the same address with the same ``_version``
+    (snvc_amd/_derived.py).  Every in-place update that goes through autograd-visible tensors (``optimizer.step()``,
+    ``load_state_dict``, ``p.copy_()`` under ``no_grad``, ``p.detach().mul_()``) bumps ``_version`` and invalidates them by
+    itself.  Writes through ``.data`` (``p.data.mul_(2)``, an EMA swap that assigns ``.data`` storage in place) do NOT bump it:
+    after such a write call this function -- for one module tree, or with no argument for every model of the process (a
+    generation counter in every stamp)."""
     if module is None:
-        _GENERATION[0] += 1
+        invalidate_all()
         return
     for m in module.modules():
         for name in CACHE_ATTRS:
@@ -79,14 +78,9 @@ CACHE_ATTRS = ("_snvc_plans", "_snvc_plans_f16", "_snvc_plans_x3", "_snvc_plans2
                "_snvc_coor_maps", "_snvc_x3", "_snvc_x3_off", "_snvc_x3_guard", "_snvc_last_v1", "_snvc_streams", "_snvc_lazy_warned", "_snvc_prep_ws", "_snvc_prep_epoch")
 
 
-class _Plan:
-    """Packed weights + folded affine for one conv(+norm) pair, rebuilt when parameters change."""
-
-    def __init__(self):
-        self.key = None
-        self.layer: Optional[ops.Conv3dLayer] = None
-        self.scale = None
-        self.bias = None
+class _Plan(dict):
+    """The values derived from one conv(+norm) pair's parameters (packed weights, folded affine, ...): a store for
+    ``_derived.derived``, each entry rebuilt when its sources change."""
 
 
 def _conv_geometry(conv: nn.Module):
@@ -104,31 +98,25 @@ def _conv_geometry(conv: nn.Module):
     return k, s, p, d, transposed
 
 
-def _get_layer(conv: nn.Module, plan: _Plan) -> ops.Conv3dLayer:
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if plan.layer is None or plan.key != key:
-        k, s, p, d, transposed = _conv_geometry(conv)
-        plan.layer = ops.Conv3dLayer(w.detach(), k, s, p, d, transposed)
-        plan.key = key
-    return plan.layer
+def _get_layer(conv: nn.Module, plan: _Plan, cls=ops.Conv3dLayer):
+    """conv's weights packed for ``cls`` (Conv3dLayer, Conv3dLayerF16 or Conv3dLayerX3)."""
+    return derived(plan, "layer", (conv.weight,), lambda: cls(conv.weight.detach(), *_conv_geometry(conv)))
+
+
+def _bn_sources(bn):
+    return bn.weight, bn.bias, bn.running_mean, bn.running_var
 
 
 def _folded_bn(bn: nn.BatchNorm3d, plan: _Plan):
     """Eval-mode BatchNorm3d as y = x*scale + bias (fp64 fold, cast once)."""
-    key = (bn.weight._version if bn.weight is not None else -1, bn.bias._version if bn.bias is not None else -1,
-           bn.running_mean._version, bn.running_var._version, bn.running_mean.data_ptr(), bn.running_mean.device,
-           _GENERATION[0])
-    if plan.scale is None or getattr(plan, "bn_key", None) != key:
+    def build():
         var = bn.running_var.detach().double()
         mean = bn.running_mean.detach().double()
         g = bn.weight.detach().double() if bn.weight is not None else torch.ones_like(var)
         b = bn.bias.detach().double() if bn.bias is not None else torch.zeros_like(var)
         sc = g / torch.sqrt(var + bn.eps)
-        plan.scale = sc.float().contiguous()
-        plan.bias = (b - mean * sc).float().contiguous()
-        plan.bn_key = key
-    return plan.scale, plan.bias
+        return sc.float().contiguous(), (b - mean * sc).float().contiguous()
+    return derived(plan, "bn", _bn_sources(bn), build)
 
 
 _BatchNormNd = (nn.BatchNorm3d, nn.BatchNorm2d)      # the 2D neck's layers run as depth-1 3D layers (raw is 5-D either way)
@@ -231,21 +219,17 @@ def _dgrad_layer(conv: nn.Module, plan: _Plan) -> ops.Conv3dLayer:
     Conv3d stride 1  -> Conv3d with taps flipped and channels transposed;
     Conv3d(k3,s2,p1) -> ConvTranspose3d(k3,s2,p1,op1) over the SAME weight memory;
     ConvTranspose3d  -> Conv3d(k3,s2,p1) over the SAME weight memory."""
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if getattr(plan, "dgrad", None) is None or plan.dgrad_key != key:
+    def build():
         k, s, p, d, transposed = _conv_geometry(conv)
-        wd = w.detach()
+        wd = conv.weight.detach()
         if transposed:
-            plan.dgrad = ops.Conv3dLayer(wd, 3, 2, 1, 1, False)
-        elif s == 1:
-            plan.dgrad = ops.Conv3dLayer(wd.transpose(0, 1).flip(2, 3, 4).contiguous(), k, 1, p, d, False)
-        elif s == 2 and k == 3 and p == 1 and d == 1:
-            plan.dgrad = ops.Conv3dLayer(wd, 3, 2, 1, 1, True)
-        else:
-            raise NotImplementedError("dgrad of this strided convolution is not on the path")
-        plan.dgrad_key = key
-    return plan.dgrad
+            return ops.Conv3dLayer(wd, 3, 2, 1, 1, False)
+        if s == 1:
+            return ops.Conv3dLayer(_flip3d(wd), k, 1, p, d, False)
+        if s == 2 and k == 3 and p == 1 and d == 1:
+            return ops.Conv3dLayer(wd, 3, 2, 1, 1, True)
+        raise NotImplementedError("dgrad of this strided convolution is not on the path")
+    return derived(plan, "dgrad", (conv.weight,), build)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -279,33 +263,15 @@ def _x3_train_route(conv: nn.Module, x: torch.Tensor) -> bool:
 
 def _l1_out(conv: nn.Module, plan: _Plan) -> torch.Tensor:
     """sum |w| per OUTPUT channel (cached per weight version): |conv(x)[c]| <= l1[c] * max|x|."""
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if getattr(plan, "l1", None) is None or plan.l1_key != key:
-        dims = (0, 2, 3, 4) if isinstance(conv, nn.ConvTranspose3d) else (1, 2, 3, 4)
-        plan.l1 = w.detach().abs().sum(dims).float().contiguous()
-        plan.l1_key = key
-    return plan.l1
-
-
-def _l1_in(conv: nn.Module, plan: _Plan) -> torch.Tensor:
-    """sum |w| per INPUT channel: the data gradient's filters (|dgrad(g)[c]| <= l1_in[c] * max|g|)."""
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if getattr(plan, "l1_in", None) is None or plan.l1_in_key != key:
-        dims = (1, 2, 3, 4) if isinstance(conv, nn.ConvTranspose3d) else (0, 2, 3, 4)
-        plan.l1_in = w.detach().abs().sum(dims).float().contiguous()
-        plan.l1_in_key = key
-    return plan.l1_in
+    dims = (0, 2, 3, 4) if isinstance(conv, nn.ConvTranspose3d) else (1, 2, 3, 4)
+    return derived(plan, "l1", (conv.weight,), lambda: conv.weight.detach().abs().sum(dims).float().contiguous())
 
 
 def _x3_train_layers(conv: nn.Module, plan: _Plan):
     """(forward layer, data-gradient layer) on the split kernels, weights scaled on the device; rebuilt when the weights change."""
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if getattr(plan, "x3t", None) is None or plan.x3t_key != key:
+    def build():
         k, s, p, d, transposed = _conv_geometry(conv)
-        wd = w.detach()
+        wd = conv.weight.detach()
         wm = ops.split_scale_of(wd.contiguous())
         fwd = ops.Conv3dLayerX3(wd, 3, s, 1, 1, transposed, w_mul_dev=wm)
         if transposed:
@@ -314,8 +280,8 @@ def _x3_train_layers(conv: nn.Module, plan: _Plan):
             dg = ops.Conv3dLayerX3(_flip3d(wd), 3, 1, 1, 1, False, w_mul_dev=wm)
         else:
             dg = ops.Conv3dLayerX3(wd, 3, 2, 1, 1, True, w_mul_dev=wm)
-        plan.x3t, plan.x3t_key = (fwd, dg), key
-    return plan.x3t
+        return fwd, dg
+    return derived(plan, "x3t", (conv.weight,), build)
 
 
 def _split_operand(t: torch.Tensor, amax: Optional[torch.Tensor]):
@@ -441,7 +407,6 @@ class _ConvNormActFn(torch.autograd.Function):
             g_amax = None
         # data and weight gradients
         k, st, p, d, transposed = _conv_geometry(conv)
-        dl = _dgrad_layer(conv, plan)
         extra = None
         if ctx.grad_box is not None:        # the gradient of x's other use (a skip connection): added by the dgrad kernel's epilogue
             extra, ctx.grad_box.grad, ctx.grad_box.consumed = ctx.grad_box.grad, None, True
@@ -461,6 +426,7 @@ class _ConvNormActFn(torch.autograd.Function):
             gx = _x3_train_layers(conv, plan)[1].forward_f32(pair, mul, residual_f32=extra)
             _ROUTES["x3_train_dgrad"] += 1
         elif needs[0]:
+            dl = _dgrad_layer(conv, plan)
             if odd:
                 gx = dl(draw, None, None, None, 0, None)[:, :, :x.size(2), :x.size(3), :x.size(4)].contiguous()
                 if extra is not None:
@@ -576,12 +542,11 @@ def _flip3d(w):
 def _first_conv_train_cache(conv, weight, c):
     """Packed layers of the factored first convolution's training functions, rebuilt when the weight changes: ``fl`` / ``bl``
     = the left half's forward / dgrad layers (the general and the sheared function add their right-half layers lazily)."""
-    fac = conv.__dict__.setdefault("_snvc_factored_train", {})
-    key = (weight.data_ptr(), weight._version, weight.device, _GENERATION[0])
-    if fac.get("key") != key:
+    fac = conv.__dict__.get("_snvc_factored_train")
+    if fac is None or not fresh(fac["stamp"], (weight,)):
         wl = weight.detach()[:, :c].contiguous()
-        fac.clear()
-        fac.update(key=key, fl=ops.Conv3dLayer(wl, 3, 1, 1, 1, False), bl=ops.Conv3dLayer(_flip3d(wl), 3, 1, 1, 1, False))
+        fac = conv.__dict__["_snvc_factored_train"] = {
+            "stamp": stamp((weight,)), "fl": ops.Conv3dLayer(wl, 3, 1, 1, 1, False), "bl": ops.Conv3dLayer(_flip3d(wl), 3, 1, 1, 1, False)}
     return fac
 
 
@@ -937,20 +902,11 @@ def _folded_head_layer(conv: nn.Module, norm: Optional[nn.Module], head: nn.Modu
     """``head(norm(conv(x)))`` with NO activation in between is one layer to ONE channel:
     W'[ci][tap] = sum_co h[co] * scale[co] * W[co, ci][tap],  b' = sum_co h[co] * shift[co]   (folded in fp64).
     Returns (layer, one, bias) with ``one`` / ``bias`` the [1] scale / shift tensors of that layer's epilogue."""
-    w, hw = conv.weight, head.weight
-    bn_key = None
-    if norm is not None:
-        bn_key = (norm.weight._version if norm.weight is not None else -1, norm.bias._version if norm.bias is not None else -1,
-                  norm.running_mean._version, norm.running_var._version, norm.running_mean.data_ptr())
-    key = (w.data_ptr(), w._version, hw.data_ptr(), hw._version, bn_key, w.device, _GENERATION[0])
-    cached = getattr(plan, "folded_head", None)
-    if cached is None or cached[0] != key:
-        k, s, p, d, transposed = _conv_geometry(conv)
+    def build():
         wf, fb = folded_head_weights(conv, norm, head)
-        layer = ops.Conv3dLayer(wf.float().contiguous(), k, s, p, d, transposed)
-        one = torch.ones(1, dtype=torch.float32, device=w.device)
-        cached = plan.folded_head = (key, layer, one, fb.float().reshape(1))
-    return cached[1], cached[2], cached[3]
+        layer = ops.Conv3dLayer(wf.float().contiguous(), *_conv_geometry(conv))
+        return layer, torch.ones(1, dtype=torch.float32, device=conv.weight.device), fb.float().reshape(1)
+    return derived(plan, "folded_head", (conv.weight, head.weight) + (_bn_sources(norm) if norm is not None else ()), build)
 
 
 def folded_head_weights(conv: nn.Module, norm: Optional[nn.Module], head: nn.Module):
@@ -1078,17 +1034,12 @@ def fused_conv3d_f16(conv: nn.Module, norm: Optional[nn.Module], x: torch.Tensor
     if conv.weight.device != x.device:
         raise RuntimeError(f"conv3d weight is on {conv.weight.device} but the input is on {x.device}")
     plan = conv.__dict__.setdefault("_snvc_plans_f16", {}).setdefault(x.device, _Plan())
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if plan.layer is None or plan.key != key:
-        k, s, p, d, transposed = _conv_geometry(conv)
-        plan.layer = ops.Conv3dLayerF16(w.detach(), k, s, p, d, transposed)
-        plan.key = key
+    layer = _get_layer(conv, plan, ops.Conv3dLayerF16)
     scale, bias = _folded_bn(norm, plan) if norm is not None else (None, None)
     flags = (EPI_RELU if relu else 0) | (EPI_SIGMOID if sigmoid else 0)
     if residual is not None:
         flags |= EPI_ADD_POST if residual_after_act else EPI_ADD_PRE
-    return plan.layer(x, scale, bias, residual, flags, out)
+    return layer(x, scale, bias, residual, flags, out)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1169,23 +1120,13 @@ def x3_exponent(bound: float) -> int:
 def x3_norm_bound(norm, plan) -> float:
     """|beta| + X3_SIGMAS * |gamma| of a frozen BatchNorm3d, maximised over channels (cached with the folded affine); of a
     GroupNorm likewise (its result is gamma * xhat + beta with xhat normalised per sample and group)."""
-    if isinstance(norm, nn.GroupNorm):
-        w, b = norm.weight, norm.bias
-        gkey = (None if w is None else (w.data_ptr(), w._version), None if b is None else (b.data_ptr(), b._version), _GENERATION[0])
-        hit = getattr(plan, "x3_gn_bound", None)
-        if hit is None or hit[0] != gkey:
-            g = w.detach().abs() if w is not None else torch.ones(1)
-            bb = b.detach().abs().to(g.device) if b is not None else torch.zeros(1, device=g.device)
-            hit = plan.x3_gn_bound = (gkey, float((bb + X3_SIGMAS * g).max().item()), w, b)      # w, b held: no address reuse
-        return hit[1]
-    key = getattr(plan, "bn_key", None)
-    hit = getattr(plan, "x3_bound", None)
-    if hit is None or hit[0] != key or key is None:
-        _folded_bn(norm, plan)
-        g = norm.weight.detach().abs() if norm.weight is not None else torch.ones(1, device=norm.running_mean.device)
-        b = norm.bias.detach().abs() if norm.bias is not None else torch.zeros(1, device=norm.running_mean.device)
-        hit = plan.x3_bound = (plan.bn_key, float((b + X3_SIGMAS * g).max().item()))
-    return hit[1]
+    w, b = norm.weight, norm.bias
+
+    def build():
+        g = w.detach().abs() if w is not None else torch.ones(1)
+        bb = b.detach().abs().to(g.device) if b is not None else torch.zeros(1, device=g.device)
+        return float((bb + X3_SIGMAS * g).max().item())
+    return derived(plan, "x3_bound", (w, b), build)
 
 
 def x3_ok(*modules, group_norm: bool = True) -> bool:
@@ -1211,21 +1152,16 @@ def fused_conv3d_x3(conv: nn.Module, norm: Optional[nn.Module], x: SplitT, *, re
     exponent is ``out_exp`` if given (a slice of a larger pair must share the pair's), else chosen from the bound
     |beta| + X3_SIGMAS |gamma| (+ the residual's bound)."""
     plan = conv.__dict__.setdefault("_snvc_plans_x3", {}).setdefault(x.t.device, _Plan())
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if plan.layer is None or plan.key != key:
-        k, s_, p_, d_, transposed = _conv_geometry(conv)
-        plan.layer = ops.Conv3dLayerX3(w.detach(), k, s_, p_, d_, transposed)
-        plan.key = key
+    layer = _get_layer(conv, plan, ops.Conv3dLayerX3)
     scale = bias = None
     bound = None
     if isinstance(norm, nn.GroupNorm):
-        return _fused_conv3d_x3_gn(plan, norm, x, relu, sigmoid, residual, residual_after_act, out, out_exp, to_f32, flag)
+        return _fused_conv3d_x3_gn(plan, layer, norm, x, relu, sigmoid, residual, residual_after_act, out, out_exp, to_f32, flag)
     if norm is not None:
         scale, bias = _folded_bn(norm, plan)
         bound = x3_norm_bound(norm, plan)
     flags = (EPI_RELU if relu else 0) | (EPI_SIGMOID if sigmoid else 0)
-    f32 = to_f32 or plan.layer.cout == 1
+    f32 = to_f32 or layer.cout == 1
     res_t = None
     if residual is not None:
         flags |= EPI_ADD_POST if residual_after_act else EPI_ADD_PRE
@@ -1239,12 +1175,12 @@ def fused_conv3d_x3(conv: nn.Module, norm: Optional[nn.Module], x: SplitT, *, re
         e = x3_exponent(bound) if out_exp is None else out_exp
     else:
         e = residual.exp if residual is not None else 0
-    y = plan.layer(x.t, 0 if x.mul_dev is not None else x.exp, scale, bias, residual=res_t, flags=flags, out=out, out_exp=e,
+    y = layer(x.t, 0 if x.mul_dev is not None else x.exp, scale, bias, residual=res_t, flags=flags, out=out, out_exp=e,
                    to_f32=f32, overflow=flag, x_mul_dev=x.mul_dev, res_exp=residual.exp if residual is not None else None)
     return y if f32 else SplitT(y, e, bound)
 
 
-def _fused_conv3d_x3_gn(plan, norm, x: SplitT, relu, sigmoid, residual, residual_after_act, out, out_exp, to_f32, flag):
+def _fused_conv3d_x3_gn(plan, layer, norm, x: SplitT, relu, sigmoid, residual, residual_after_act, out, out_exp, to_f32, flag):
     """A ``convbn_3d(..., gn=True)`` layer (reference submodule.py:41-49) in split mode (r5): GroupNorm needs the statistics of the
     convolution's own result, so the layer is  split-mode convolution -> fp32 NCDHW raw result -> snvc_norm_stats (per sample and
     group) -> one pass that applies scale / shift (+ residual, activation) and writes the split pair
@@ -1252,7 +1188,7 @@ def _fused_conv3d_x3_gn(plan, norm, x: SplitT, relu, sigmoid, residual, residual
     arithmetic as every split layer; the statistics and the affine are the fp32 path's own kernels."""
     if sigmoid:
         raise NotImplementedError("split mode: GroupNorm + Sigmoid is not on the path")
-    raw = plan.layer(x.t, 0 if x.mul_dev is not None else x.exp, None, None, flags=0, out_exp=0, to_f32=True, x_mul_dev=x.mul_dev)
+    raw = layer(x.t, 0 if x.mul_dev is not None else x.exp, None, None, flags=0, out_exp=0, to_f32=True, x_mul_dev=x.mul_dev)
     scale, shift, _, _ = ops.norm_stats(raw, norm.weight, norm.bias, norm.num_groups, True, norm.eps)
     flags = EPI_RELU if relu else 0
     _ROUTES["x3_group_norm"] += 1
@@ -1543,25 +1479,23 @@ class _Conv2dNormActFn(torch.autograd.Function):
                                                 ctx.has_res and needs[5], needs[3], needs[4])
         gb = draw.sum(dim=(0, 2, 3, 4)) if (ctx.has_bias and needs[2]) else None
         w = conv.weight.detach()
-        key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-        if getattr(plan, "dgrad2d_key", None) != key:
+
+        def build():
             mk = lambda t, k, st, tr: ops.Conv3dLayer(t.contiguous(), k, st, (k - 1) // 2, 1, tr, planar=True)   # noqa: E731
             if kind[0] == "deconv":
-                plan.dgrad2d = mk(w, 3, 2, False)                                   # Conv2d(k3,s2,p1) over the same weight memory
-            elif kind[0] == "whole":
-                plan.dgrad2d = ops.Conv3dLayer(w.reshape(w.size(0), -1).t().reshape(-1, w.size(0), 1, 1, 1).contiguous(), 1, 1, 0, 1,
-                                               False, planar=True)
-            elif kind[2] == 1:
-                plan.dgrad2d = mk(w.transpose(0, 1).flip(2, 3), kind[1], 1, False)
-            elif kind[1] == 3:
-                plan.dgrad2d = mk(w, 3, 2, True)                                    # ConvTranspose2d(k3,s2,p1,op1), same weight memory
-            else:
-                plan.dgrad2d = mk(w.transpose(0, 1), 1, 1, False)                   # k1 / stride 2: a 1x1 layer, scattered below
-            plan.dgrad2d_key = key
+                return mk(w, 3, 2, False)                                           # Conv2d(k3,s2,p1) over the same weight memory
+            if kind[0] == "whole":
+                return ops.Conv3dLayer(w.reshape(w.size(0), -1).t().reshape(-1, w.size(0), 1, 1, 1).contiguous(), 1, 1, 0, 1, False,
+                                       planar=True)
+            if kind[2] == 1:
+                return mk(w.transpose(0, 1).flip(2, 3), kind[1], 1, False)
+            if kind[1] == 3:
+                return mk(w, 3, 2, True)                                            # ConvTranspose2d(k3,s2,p1,op1), same weight memory
+            return mk(w.transpose(0, 1), 1, 1, False)                               # k1 / stride 2: a 1x1 layer, scattered below
         gx = gw = None
         h, wd = x5.size(3), x5.size(4)
         if needs[0]:
-            g = plan.dgrad2d(draw, None, None, None, 0, None)
+            g = derived(plan, "dgrad2d", (conv.weight,), build, kind)(draw, None, None, None, 0, None)
             if kind[0] == "conv" and kind[2] == 2:
                 if kind[1] == 3:        # twice draw's extent: crop the gradient of the padding when x's extent is odd
                     gx = g if (g.size(3), g.size(4)) == (h, wd) else g[:, :, :, :h, :wd].contiguous()
@@ -1603,13 +1537,10 @@ def _affine2d(conv, norm, plan: _Plan):
     if isinstance(norm, nn.BatchNorm2d):
         scale, bias = _folded_bn(norm, plan)
     if conv.bias is not None:
-        key = (conv.bias._version, conv.bias.data_ptr(), None if scale is None else scale.data_ptr(), _GENERATION[0])
-        if getattr(plan, "cb_key", None) != key:
+        def build():
             b = conv.bias.detach().float()
-            plan.cb = ((b * scale + bias) if scale is not None else b).contiguous()
-            plan.cs = scale if scale is not None else torch.ones_like(b)
-            plan.cb_key = key
-        scale, bias = plan.cs, plan.cb
+            return (scale if scale is not None else torch.ones_like(b)), ((b * scale + bias) if scale is not None else b).contiguous()
+        scale, bias = derived(plan, "affine2d", (conv.bias, scale, bias), build)
     return scale, bias
 
 
@@ -1630,19 +1561,18 @@ def fused_conv2d(conv: nn.Conv2d, norm, x: torch.Tensor, *, relu=False, sigmoid=
             return fused_conv2d(conv, norm, x.transpose(2, 3).contiguous(), relu=relu, sigmoid=sigmoid, residual=residual,
                                 residual_after_act=residual_after_act)
         plan = conv.__dict__.setdefault("_snvc_plans2d_t", {}).setdefault(x.device, _Plan())
-    key = (w.data_ptr(), w._version, w.device, whole, _GENERATION[0])
-    if plan.layer is None or plan.key != key:
+
+    def build():
         if conv.groups != 1 or tuple(conv.dilation) != (1, 1):
             raise NotImplementedError("grouped / dilated Conv2d is not in the 2D neck")
         if whole:      # one output pixel: a 1x1 layer over the flattened (c, h, w) input
-            plan.layer = ops.Conv3dLayer(w.detach().reshape(w.size(0), -1, 1, 1, 1), 1, 1, 0, 1, False, planar=True)
-        else:
-            k, st = kh, conv.stride[0]
-            if kh != kw or conv.stride[0] != conv.stride[1] or tuple(conv.padding) != ((k - 1) // 2,) * 2 or k not in (1, 3) or st not in (1, 2):
-                raise NotImplementedError(f"Conv2d geometry {conv} is not in the 2D neck")
-            wk = w.detach().transpose(2, 3).contiguous() if transposed_input else w.detach()
-            plan.layer = ops.Conv3dLayer(wk, k, st, (k - 1) // 2, 1, False, planar=True)
-        plan.key = key
+            return ops.Conv3dLayer(w.detach().reshape(w.size(0), -1, 1, 1, 1), 1, 1, 0, 1, False, planar=True)
+        k, st = kh, conv.stride[0]
+        if kh != kw or conv.stride[0] != conv.stride[1] or tuple(conv.padding) != ((k - 1) // 2,) * 2 or k not in (1, 3) or st not in (1, 2):
+            raise NotImplementedError(f"Conv2d geometry {conv} is not in the 2D neck")
+        wk = w.detach().transpose(2, 3).contiguous() if transposed_input else w.detach()
+        return ops.Conv3dLayer(wk, k, st, (k - 1) // 2, 1, False, planar=True)
+    layer = derived(plan, "layer", (w,), build, (whole,))
     flags = (EPI_RELU if relu else 0) | (EPI_SIGMOID if sigmoid else 0)
     if residual is not None:
         flags |= EPI_ADD_POST if residual_after_act else EPI_ADD_PRE
@@ -1650,12 +1580,12 @@ def fused_conv2d(conv: nn.Conv2d, norm, x: torch.Tensor, *, relu=False, sigmoid=
     r5 = residual.unsqueeze(2) if residual is not None else None
     if _train2d(x, conv, norm, residual):
         kind = ("whole",) if whole else ("conv", kh, conv.stride[0])
-        y = _conv2d_train(conv, norm, x5.contiguous(), r5.contiguous() if r5 is not None else None, flags, plan, kind, plan.layer)
+        y = _conv2d_train(conv, norm, x5.contiguous(), r5.contiguous() if r5 is not None else None, flags, plan, kind, layer)
         return y.squeeze(2)
     scale, bias = _affine2d(conv, norm, plan)
     if isinstance(norm, nn.GroupNorm):
-        return _group_norm_2d(plan.layer(x5, scale, bias), norm, r5, flags).squeeze(2)
-    y = plan.layer(x5, scale, bias, r5, flags).squeeze(2)
+        return _group_norm_2d(layer(x5, scale, bias), norm, r5, flags).squeeze(2)
+    y = layer(x5, scale, bias, r5, flags).squeeze(2)
     return y.transpose(2, 3) if transposed_input else y
 
 
@@ -1674,20 +1604,16 @@ def fused_deconv2d(conv: nn.ConvTranspose2d, norm, x: torch.Tensor, *, relu=Fals
             or conv.groups != 1 or conv.bias is not None:
         raise NotImplementedError("the 2D neck's up-sampling layers are ConvTranspose2d(k3,s2,p1,op1,bias=False)")
     plan = _plan2d(conv, x.device)
-    w = conv.weight
-    key = (w.data_ptr(), w._version, w.device, _GENERATION[0])
-    if plan.layer is None or plan.key != key:
-        plan.layer = ops.Conv3dLayer(w.detach().contiguous(), 3, 2, 1, 1, True, planar=True)
-        plan.key = key
+    layer = derived(plan, "layer", (conv.weight,), lambda: ops.Conv3dLayer(conv.weight.detach().contiguous(), 3, 2, 1, 1, True, planar=True))
     flags = (EPI_RELU if relu else 0) | (EPI_ADD_PRE if residual is not None else 0)
     r5 = residual.unsqueeze(2) if residual is not None else None
     if _train2d(x, conv, norm, residual):
         return _conv2d_train(conv, norm, x.unsqueeze(2).contiguous(), r5.contiguous() if r5 is not None else None, flags, plan,
-                             ("deconv",), plan.layer).squeeze(2)
+                             ("deconv",), layer).squeeze(2)
     scale, bias = _affine2d(conv, norm, plan)
     if isinstance(norm, nn.GroupNorm):
-        return _group_norm_2d(plan.layer(x.unsqueeze(2), scale, bias), norm, r5, flags).squeeze(2)
-    return plan.layer(x.unsqueeze(2), scale, bias, r5, flags).squeeze(2)
+        return _group_norm_2d(layer(x.unsqueeze(2), scale, bias), norm, r5, flags).squeeze(2)
+    return layer(x.unsqueeze(2), scale, bias, r5, flags).squeeze(2)
 
 
 def _cbr2d(seq, x, **kw):

@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _derived, _lib
 from ._lib import (EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID, EPI_STREAM_OUT, F32, F64, Conv3dDesc,
                    Unsupported, check)
 
@@ -112,6 +112,8 @@ def cost_volume_forward_right(right, shift, out=None):
         out = torch.empty((n, c, d, h, w), dtype=torch.float32, device=right.device)
     elif tuple(out.shape) != (n, c, d, h, w) or out.dtype != torch.float32 or not out.is_contiguous():
         raise RuntimeError("cost_volume_forward_right `out` must be a contiguous float32 [N,C,D,H,W] tensor")
+    else:
+        _written(out)
     if out.numel() == 0:
         return out
     right, shift = right.contiguous(), shift.contiguous()
@@ -347,6 +349,7 @@ class Conv3dLayer:
         else:
             if tuple(out.shape) != out_shape or out.dtype != torch.float32 or not _dense_inner(out):
                 raise RuntimeError("conv3d `out` must be a float32 channel-dense view of the output shape")
+            _written(out)
         if residual is not None:
             if tuple(residual.shape) != out_shape:
                 raise RuntimeError("residual must have the output's shape")
@@ -430,6 +433,7 @@ def warped_expand(p, q, e, planes, shift, scale, bias, out, flags: int = 0):
     if planes is not None and (tuple(planes.shape) != (n, c, 3, h, w) or not planes.is_contiguous()):
         raise RuntimeError("planes must be a contiguous [N,C,3,H,W] tensor")
     shift = shift.contiguous()
+    _written(out)
     with torch.cuda.device(out.device):
         check(_lib.lib().snvc_warped_expand(_ptr(p), _ptr(q), _ptr(e), _ptr(planes), _ptr(shift), _ptr(scale), _ptr(bias), _ptr(out),
                                             n, c, d, h, w, int(flags) | WARPED_EXPAND_FORM[0], _stream(out)), "snvc_warped_expand")
@@ -474,6 +478,7 @@ def warped_expand_split(p, q, e, planes, shift, scale, bias, out, flags: int = 0
     if planes is not None and (tuple(planes.shape) != (n, c, 3, h, w) or not planes.is_contiguous()):
         raise RuntimeError("planes must be a contiguous [N,C,3,H,W] tensor")
     shift = shift.contiguous()
+    _written(out)
     with torch.cuda.device(out.device):
         check(_lib.lib().snvc_warped_expand_split(_ptr(p), _ptr(q), _ptr(e), _ptr(planes), _ptr(shift), _ptr(scale), _ptr(bias), _ptr(out),
                                                   _lo_ptr(out), _ptr(overflow), n, c, d, h, w, _batch_stride(out), int(flags), _stream(out)),
@@ -593,6 +598,7 @@ def sheared_expand(g, gcol, planes, scale, bias, out, q: int, m0: int, off: int,
         raise RuntimeError("sheared_expand needs a contiguous float32 out [N,C,D,H,W]")
     if planes is not None and (tuple(planes.shape) != (n, c, 3, h, w) or not planes.is_contiguous()):
         raise RuntimeError("planes must be a contiguous [N,C,3,H,W] tensor")
+    _written(out)
     with torch.cuda.device(out.device):
         check(_lib.lib().snvc_sheared_expand_amax(_ptr(g), _ptr(gcol), _ptr(planes), _ptr(scale), _ptr(bias), _ptr(out), n, c, d, h, w,
                                                   int(q), int(m0), g.size(3), int(off), gcol.size(3), int(off_col), int(flags),
@@ -614,6 +620,7 @@ def sheared_expand_split(g, gcol, planes, scale, bias, out, q: int, m0: int, off
             raise RuntimeError("sheared_expand_split needs contiguous float32 g / gcol [N,3C,H,*] (depth classes stacked class-major)")
     if planes is not None and (tuple(planes.shape) != (n, c, 3, h, w) or not planes.is_contiguous()):
         raise RuntimeError("planes must be a contiguous [N,C,3,H,W] tensor")
+    _written(out)
     with torch.cuda.device(out.device):
         check(_lib.lib().snvc_sheared_expand_split(_ptr(g), _ptr(gcol), _ptr(planes), _ptr(scale), _ptr(bias), _ptr(out), _lo_ptr(out),
                                                    _ptr(overflow), n, c, d, h, w, int(q), int(m0), g.size(3), int(off), gcol.size(3),
@@ -838,9 +845,7 @@ def bn_track(norm, mean, var, cnt: float) -> bool:
     with torch.cuda.device(rm.device):
         check(_lib.lib().snvc_bn_track(_ptr(rm), _ptr(rv), _ptr(nbt), _ptr(mean), _ptr(var), rm.numel(), float(norm.momentum),
                                        float(cnt / max(cnt - 1, 1)), _stream(rm)), "snvc_bn_track")
-    # the kernel wrote through raw pointers: tell the version counters (the folded eval-mode BatchNorm is cached on ._version)
-    for t in (rm, rv) + ((nbt,) if nbt is not None else ()):
-        torch.autograd.graph.increment_version(t)
+    _written(rm, rv, nbt)
     return True
 
 
@@ -861,6 +866,12 @@ def act_backward_reduce(raw, gy, residual, scale, shift, flags: int, per_sample:
 
 
 AMAX_SLOTS = 64      # SNVC_AMAX_SLOTS
+
+
+def _written(*tensors) -> None:
+    """Bump the version counters of caller-supplied tensors (``out=``) a kernel wrote through raw pointers: derived values and
+    tags (_derived.py, tag_amax / tag_twin) then see the write like an in-place torch op.  A result allocated here needs no bump."""
+    torch.autograd.graph.increment_version([t for t in tensors if t is not None])
 
 
 _AMAX_POOL = threading.local()
@@ -894,16 +905,13 @@ def tag_amax(t: torch.Tensor, amax: Optional[torch.Tensor]) -> torch.Tensor:
     """Remember the word that holds max|t| on the tensor object itself: the layer that consumes ``t`` hands it to its weight gradient
     (split-operand form) instead of reading the whole tensor again.  Purely an optimisation: a tensor without the tag works."""
     if amax is not None:
-        t.snvc_amax_tag = (amax, t._version)
+        t.snvc_amax_tag = _derived.tag(t, amax)
     return t
 
 
 def amax_of(t: torch.Tensor) -> Optional[torch.Tensor]:
-    """The tagged word, if the tensor has not been written to since it was tagged (an in-place update bumps ``_version``)."""
-    tag = getattr(t, "snvc_amax_tag", None)
-    if tag is None or tag[1] != t._version or tag[0].device != t.device:
-        return None
-    return tag[0]
+    """The tagged word, if the tensor has not been written to since it was tagged."""
+    return _derived.tagged(t, getattr(t, "snvc_amax_tag", None))
 
 
 def twin_ok(t: torch.Tensor) -> bool:
@@ -918,17 +926,14 @@ def twin_empty(like: torch.Tensor) -> torch.Tensor:
 
 
 def tag_twin(t: torch.Tensor, pair: torch.Tensor, mul_dev: torch.Tensor) -> torch.Tensor:
-    """Remember ``t``'s split twin (``pair`` holds t * mul_dev) on the tensor object; void once t is written to (``_version``)."""
-    t.snvc_twin_tag = (pair, mul_dev, t._version)
+    """Remember ``t``'s split twin (``pair`` holds t * mul_dev) on the tensor object; void once t is written to."""
+    t.snvc_twin_tag = _derived.tag(t, (pair, mul_dev))
     return t
 
 
 def twin_of(t: torch.Tensor):
     """(pair, mul_dev) tagged by the pass that wrote ``t``, or None."""
-    tag = getattr(t, "snvc_twin_tag", None)
-    if tag is None or tag[2] != t._version or tag[0].device != t.device:
-        return None
-    return tag[0], tag[1]
+    return _derived.tagged(t, getattr(t, "snvc_twin_tag", None))
 
 
 def split_scale_bound(rows: int, c: int, device, a=None, amax_p=None, b=None, l1=None, amax_x=None, cc=None, amax_r=None) -> torch.Tensor:
@@ -1010,6 +1015,8 @@ def affine_act(x, scale, shift, residual=None, flags=0, per_sample=False, out=No
         out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     elif not _dense_inner(out) or tuple(out.shape) != tuple(x.shape):
         raise RuntimeError("affine_act `out` must be a channel-dense view of x's shape")
+    else:
+        _written(out)
     if residual is not None and not _dense_inner(residual):
         residual = residual.contiguous()
     n, c = x.shape[0], x.shape[1]
@@ -1046,6 +1053,8 @@ def mul_broadcast(feat, occ, out=None):
         out = torch.empty_like(feat)
     elif not _dense_inner(out) or tuple(out.shape) != tuple(feat.shape):
         raise RuntimeError("mul_broadcast `out` must be a channel-dense view of feat's shape")
+    else:
+        _written(out)
     if feat.numel() == 0:
         return out
     with torch.cuda.device(feat.device):
@@ -1199,6 +1208,7 @@ def to_c8(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         out = torch.empty((n, (c + 7) // 8) + sp + (8,), dtype=torch.float16, device=x.device)
     else:
         _c8_check(out, "out")
+        _written(out)
     if x.numel() == 0:
         return out
     with torch.cuda.device(x.device):
@@ -1331,6 +1341,7 @@ class Conv3dLayerF16:
             _c8_check(out, "out")
             if tuple(out.shape) != (n, self.cout // 8) + out_sp + (8,):
                 raise RuntimeError("conv3d `out` must be a C8 view of the output shape")
+            _written(out)
         if residual is not None:
             _c8_check(residual, "residual")
             if tuple(residual.shape) != (n, self.cout // 8) + out_sp + (8,):
@@ -1381,6 +1392,7 @@ def to_split(x: torch.Tensor, exp: int = 0, out: Optional[torch.Tensor] = None, 
         out = torch.empty((n, 2, (c + 7) // 8) + sp + (8,), dtype=torch.float16, device=x.device)
     else:
         _split_check(out, "out")
+        _written(out)
     if x.numel() == 0:
         return out
     with torch.cuda.device(x.device):
@@ -1408,6 +1420,7 @@ def affine_act_split(raw, scale, shift, out_exp: int, residual=None, res_exp: in
         _split_check(out, "out")
         if tuple(out.shape) != shape:
             raise RuntimeError("affine_act_split: out has the wrong shape")
+        _written(out)
     want_res = bool(flags & (EPI_ADD_PRE | EPI_ADD_POST))
     if want_res != (residual is not None):
         raise RuntimeError("affine_act_split: a residual exactly when EPI_ADD_PRE / EPI_ADD_POST is set")
@@ -1716,19 +1729,12 @@ class Conv3dLayerX3:
     def folded(self, scale, bias, x_exp: int, out_exp: int):
         """(scale', bias') of the epilogue with the exponents folded in: conv sums are in units of 2^(x_exp + w_exp), the
         stored result in units of 2^out_exp.  Cached per (scale, bias, exponents)."""
-        key = (None if scale is None else (scale.data_ptr(), scale._version), None if bias is None else (bias.data_ptr(), bias._version),
-               x_exp, out_exp)
-        hit = self._affine.get(key)
-        if hit is not None and (hit[2] is not scale or hit[3] is not bias):
-            hit = None      # another tensor at a recycled address (the entry keeps its sources alive, so this only follows a clear())
-        if hit is None:
+        def build():
             dev = self.weight.device
             sc = (scale.detach().float() if scale is not None else torch.ones(self.cout, device=dev)) * (2.0 ** (out_exp - x_exp - self.w_exp))
             bi = (bias.detach().float() if bias is not None else torch.zeros(self.cout, device=dev)) * (2.0 ** out_exp)
-            if len(self._affine) > 8:
-                self._affine.clear()
-            hit = self._affine[key] = (sc.contiguous(), bi.contiguous(), scale, bias)
-        return hit[:2]
+            return sc.contiguous(), bi.contiguous()
+        return _derived.derived(self._affine, (x_exp, out_exp), (scale, bias), build)
 
     def __call__(self, x, x_exp: int = 0, scale=None, bias=None, residual=None, flags: int = 0, out=None, out_exp: int = 0,
                  out_f32=None, to_f32: bool = False, head=None, overflow=None, x_mul_dev=None, res_exp: Optional[int] = None,
@@ -1751,12 +1757,15 @@ class Conv3dLayerX3:
                 out_f32 = torch.empty((n, self.cout) + out_sp, dtype=torch.float32, device=x.device)
             elif tuple(out_f32.shape) != (n, self.cout) + out_sp or out_f32.dtype != torch.float32 or not _dense_inner(out_f32):
                 raise RuntimeError("out_f32 must be a float32 [N,Cout,D,H,W] tensor, dense below dim 0")
+            else:
+                _written(out_f32)
         elif out is None:
             out = torch.empty((n, 2, self.cout // 8) + out_sp + (8,), dtype=torch.float16, device=x.device)
         else:
             _split_check(out, "out")
             if tuple(out.shape) != (n, 2, self.cout // 8) + out_sp + (8,):
                 raise RuntimeError("conv3d `out` must be a split C8 tensor of the output shape")
+            _written(out)
         if residual is not None:
             _split_check(residual, "residual")
             if tuple(residual.shape) != (n, 2, self.cout // 8) + out_sp + (8,):
@@ -1880,6 +1889,8 @@ class Conv3dLayerX3:
             out = torch.empty(shape, dtype=torch.float32, device=x.device)
         elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
             raise RuntimeError("forward_tail `out` must be a contiguous float32 [N, 27, 8, Din, Hin, Win] tensor")
+        else:
+            _written(out)
         if residual is not None:
             _split_check(residual, "residual")
             if tuple(residual.shape) != (n, 2, self.cout // 8) + out_sp + (8,):
@@ -1932,6 +1943,8 @@ def deconv_tail_gather(t: torch.Tensor, bias: Optional[torch.Tensor] = None, res
         out = torch.empty(shape, dtype=torch.float32, device=t.device)
     elif tuple(out.shape) != shape or out.dtype != torch.float32 or not out.is_contiguous():
         raise RuntimeError("out must be a contiguous float32 tensor of the output shape")
+    else:
+        _written(out)
     if residual is not None:
         _gpu(residual, "residual")
         if residual.dtype != torch.float32 or residual.numel() != out.numel() or not residual.is_contiguous():
@@ -1959,6 +1972,7 @@ def mul_broadcast_split(feat, occ, out=None):
         _split_check(out, "out")
         if tuple(out.shape) != tuple(feat.shape):
             raise RuntimeError("mul_broadcast_split `out` must have feat's shape")
+        _written(out)
     if feat.numel() == 0:
         return out
     with torch.cuda.device(feat.device):
@@ -1982,6 +1996,7 @@ def mul_broadcast_c8(feat, occ, out=None):
         _c8_check(out, "out")
         if tuple(out.shape) != tuple(feat.shape):
             raise RuntimeError("mul_broadcast_c8 `out` must have feat's shape")
+        _written(out)
     if feat.numel() == 0:
         return out
     with torch.cuda.device(feat.device):

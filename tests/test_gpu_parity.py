@@ -643,6 +643,16 @@ def test_folded_head_tail_vs_separate_layers():
             # parameters change -> the folded layer is rebuilt
             hd.weight.mul_(0.5)
             check(md.fused(xd, residual=rd, head=hd).cpu().numpy(), 0.5 * ref1.numpy(), TIGHT, "folded head after an update")
+            # BatchNorm's parameters replaced by new ones whose version counters hold the same values -> rebuilt as well
+            nw, nb = md[1].weight.detach() * 2.0 + 0.25, md[1].bias.detach() - 0.5
+            for new, old in ((nw, md[1].weight), (nb, md[1].bias)):
+                while new._version < old._version:
+                    new.add_(0.0)
+                assert new._version == old._version
+            md[1].weight, md[1].bias = torch.nn.Parameter(nw), torch.nn.Parameter(nb)
+            y2 = F.batch_norm(conv, md[1].running_mean.cpu(), md[1].running_var.cpu(), nw.cpu(), nb.cpu(), False, 0.0, md[1].eps)
+            check(md.fused(xd, residual=rd, head=hd).cpu().numpy(), F.conv3d(y2 + res, hd.weight.cpu()).numpy(), TIGHT,
+                  "folded head after a BatchNorm parameter swap")
 
 
 def test_conv_avgpool_d4_fused_vs_separate():

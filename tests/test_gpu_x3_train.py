@@ -45,6 +45,25 @@ def test_affine_act_twin(flags_res, shape):
     assert ops.twin_of(got) is None
 
 
+def test_tags_die_with_a_write_through_out():
+    """A twin / amax tag is voided when a kernel of this package overwrites the tensor through ``out=`` (raw-pointer writes bump the
+    version counter like an in-place torch op): a stale twin would be convolved instead of the tensor, a stale maximum would push the
+    weight gradient's half operands to inf."""
+    from snvc_amd import ops
+    r = np.random.default_rng(7)
+    n, c, sp = 1, 32, (3, 4, 20)
+    raw, raw2 = _t(r.standard_normal((n, c) + sp)), _t(r.standard_normal((n, c) + sp) * 100)
+    scale, shift = _t(r.uniform(0.5, 2, (1, c))), _t(r.standard_normal((1, c)))
+    occ = _t(r.uniform(0, 1, (n, 1) + sp))
+    for overwrite in (lambda t: ops.affine_act(raw2, scale, shift, None, ops.EPI_RELU, out=t), lambda t: ops.mul_broadcast(raw2, occ, out=t)):
+        am = ops.amax_word(dev())
+        got = ops.affine_act(raw, scale, shift, None, ops.EPI_RELU, amax=am, twin_mul=ops.split_scale_of(raw))
+        ops.tag_amax(got, am)
+        assert ops.twin_of(got) is not None and ops.amax_of(got) is am
+        assert overwrite(got) is got
+        assert ops.twin_of(got) is None and ops.amax_of(got) is None
+
+
 @pytest.mark.parametrize("flags_res", [("relu", False), ("relu+pre", True), ("pre", True)])
 @pytest.mark.parametrize("want_g", [False, True])
 def test_act_backward_apply_twin(flags_res, want_g):

@@ -3,6 +3,7 @@ include/snvc_hip.h declares, argument validation happens before any device work,
 modules have the reference's state-dict keys, CPU tensors are refused (no CPU fallback), and the
 one host-side op (points_in_boxes_cpu) matches the oracle."""
 import ctypes
+import math
 import os
 import re
 
@@ -169,6 +170,26 @@ def test_points_in_boxes_cpu_host_op(L):
     assert np.array_equal(idmap, exp_id) and idmap.dtype == np.int32
 
 
+def test_cache_validity_is_decided_in_one_module():
+    """Whether a derived value or a tensor tag is still valid is decided by snvc_amd/_derived.py alone: `._version` is read only there
+    and in lazy.py's snapshot checks, and `data_ptr()` elsewhere only checks alignment or hands a pointer to a kernel."""
+    pkg = os.path.join(ROOT, "snvc_amd")
+    bad = []
+    for dirpath, _, files in os.walk(pkg):
+        for f in files:
+            if not f.endswith(".py"):
+                continue
+            rel = os.path.relpath(os.path.join(dirpath, f), pkg)
+            if rel == "_derived.py":
+                continue
+            for i, line in enumerate(open(os.path.join(dirpath, f)), 1):
+                if re.search(r"\._version\b", line) and rel != "lazy.py":
+                    bad.append(f"{rel}:{i}: {line.strip()}")
+                if ".data_ptr()" in line and rel != "lazy.py" and not re.search(r"data_ptr\(\) [%+]|c_void_p", line):
+                    bad.append(f"{rel}:{i}: {line.strip()}")
+    assert not bad, "\n".join(bad)
+
+
 def test_plan_caches_follow_parameter_updates():
     """Folded-BatchNorm / packed-weight caches are keyed on tensor versions: autograd-visible in-place
     updates invalidate them by themselves; `.data` writes need invalidate_plans()."""
@@ -185,6 +206,15 @@ def test_plan_caches_follow_parameter_updates():
     assert torch.allclose(S._folded_bn(bn, plan)[0], 2 * sc0)
     S.invalidate_plans()                          # generation counter: every cache of the process
     assert torch.allclose(S._folded_bn(bn, plan)[0], 4 * sc0)
+    # parameters replaced by new ones whose version counters hold the same values: the fold follows the new tensors
+    bn = torch.nn.BatchNorm3d(4).eval()
+    plan = S._Plan()
+    S._folded_bn(bn, plan)
+    w, b = torch.ones(4).mul_(3.0), torch.zeros(4).add_(0.5)
+    assert (w._version, b._version) == (bn.weight._version, bn.bias._version)
+    bn.weight, bn.bias = torch.nn.Parameter(w), torch.nn.Parameter(b)
+    sc, bi = S._folded_bn(bn, plan)
+    assert torch.allclose(sc, torch.full((4,), 3.0) / math.sqrt(1.0 + bn.eps)) and torch.allclose(bi, torch.full((4,), 0.5))
     m = S.convbn_3d(4, 4, 3, 1, 1)
     m[0].__dict__["_snvc_plans"] = {"cpu": S._Plan()}
     S.invalidate_plans(m)                         # per-module form drops the per-device plan table
