@@ -6,9 +6,10 @@
     snvc_amd.extension.iou3d_nms           <->  snvc.extension.iou3d_nms
     snvc_amd.models.submodule              <->  snvc.models.submodule (3D blocks)
     snvc_amd.models.vernier                <->  snvc.models.vernier   (VernierScale 3D trunk)
+    snvc_amd.models.hrnet                  <->  snvc.models.hrnet     (HRNet backbone; install_as_snvc(backbone="hip"))
 
 Everything executes in hand-written HIP kernels from ``libsnvc_hip.so`` (C ABI:
-``include/snvc_hip.h``, ``include/snvc_iou3d.h``).  There is no CPU path: CPU tensors raise, and a missing shared
+``include/snvc_hip.h``, ``include/snvc_iou3d.h``, ``include/snvc_hrnet.h``).  There is no CPU path: CPU tensors raise, and a missing shared
 library raises at first use.
 """
 __version__ = "0.1.0"
@@ -23,14 +24,16 @@ _ALIASES = {
 }
 
 
-def install_as_snvc(backbone: bool = True):
+def install_as_snvc(backbone=True):
     """Make the reference's own import lines resolve to this package: after ``snvc_amd.install_as_snvc()`` (once, before
     the reference's modules are imported) ``from snvc.models.vernier import get_model``,
     ``from snvc.extension.build_cost_volume import build_cost_volume`` ... give the MI355X implementations, while every
-    other ``snvc.*`` module (HRNet, dataset, utils: off the path) still comes from the reference checkout on
+    other ``snvc.*`` module (dataset, utils; HRNet unless ``backbone="hip"``) still comes from the reference checkout on
     ``sys.path``.  ``backbone=True`` also wires ``snvc.models.hrnet.get_model`` into ``VernierScale`` as its feature
     extractor factory when the reference package is importable (vernier.py:57-66), so that
-    ``tools/inference_agnostic.py`` runs with no edit but its DataParallel line."""
+    ``tools/inference_agnostic.py`` runs with no edit but its DataParallel line.
+    ``backbone="hip"`` aliases ``snvc.models.hrnet`` to ``snvc_amd.models.hrnet`` as well, so that the backbone runs on
+    the HIP kernels too and no reference module is needed for the model."""
     import importlib
     import sys
     for ref_name, ours in _ALIASES.items():
@@ -39,6 +42,13 @@ def install_as_snvc(backbone: bool = True):
         parent, _, leaf = ref_name.rpartition(".")
         if parent in sys.modules:                       # `import snvc.models.vernier as v` reads the attribute chain
             setattr(sys.modules[parent], leaf, mod)
+    if backbone == "hip":
+        mod = importlib.import_module("snvc_amd.models.hrnet")
+        sys.modules["snvc.models.hrnet"] = mod
+        try:                                            # `import snvc.models.hrnet as h` reads the attribute chain
+            setattr(importlib.import_module("snvc.models"), "hrnet", mod)
+        except ImportError:                             # no reference checkout: `from snvc.models.hrnet import ...` still works
+            pass
     if backbone:
         try:
             hrnet = importlib.import_module("snvc.models.hrnet")

@@ -13,9 +13,9 @@ reference checkpoint loads with ``strict=True``.  What changes is how ``forward`
   2D neck + heads (conv5, hm1, hm2, coord_head)        the same conv kernels in their depth-1 form
                                          :440-450       (SURVEY 8f N1), fused norm/bias/res/act
 
-The HRNet backbone is outside the path.  ``get_feat_extraction`` is the
-same hook the reference uses (vernier.py:837-839): assign a factory to it or
-pass ``feat_net=`` to the constructor.
+The HRNet backbone comes from ``snvc_amd.models.hrnet`` (HIP convolutions and fusion kernel).  ``get_feat_extraction``
+is the same hook the reference uses (vernier.py:835-839): it builds HRNet for ``hrnet-w32`` / ``hrnet-w48``; assign
+another factory to it or pass ``feat_net=`` to the constructor.
 """
 import numpy as np
 import torch
@@ -45,12 +45,15 @@ class _VoxelGatherFn(torch.autograd.Function):
 
 
 def get_feat_extraction(cfg, is_train=False, **kwargs):
-    """Factory hook for the 2D backbone (reference vernier.py:835-839 builds HRNet here)."""
-    if getattr(cfg, "name", None) == "identity":
+    """Factory hook for the 2D backbone (reference vernier.py:835-839): HRNet-w32 / -w48 from snvc_amd.models.hrnet;
+    ``identity`` (features in) for the benchmarks and tests that start from feature maps."""
+    name = getattr(cfg, "name", None)
+    if name == "identity":
         return nn.Identity()
-    raise NotImplementedError(
-        "the 2D backbone (HRNet) is outside the MI355X hot path; set "
-        "snvc_amd.models.vernier.get_feat_extraction to the reference's factory, or pass feat_net=...")
+    if name in ("hrnet-w32", "hrnet-w48"):
+        from . import hrnet
+        return hrnet.get_model(cfg, is_train, **kwargs)
+    raise NotImplementedError(f"feature extractor {name!r}: hrnet-w32, hrnet-w48 and identity are available")
 
 
 class VernierScale(nn.Module):
