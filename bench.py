@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """Headline benchmark: stereo-pairs/sec, cost-volume build + 3D CNN forward (BASELINE.json).
 
-    python bench.py --gpus N --steps K --warmup W            (starts N ranks itself when N > 1)
+    python bench.py --gpus N --steps K --warmup W            (the headline figure only; starts N ranks itself when N > 1)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py --gpus N --full                          (every leg below: other entry points, rooflines, CPU baseline, ...)
     python bench.py --gpus N --mode train                    (cfg4: fwd + bwd + RCCL gradient all-reduce)
     python bench.py --gpus N --config cfg3                   (BASELINE configs[2]: 64 RoI crops 96^3 sharded over N ranks)
-    python bench.py --headline-only                          (the headline leg + roofline + cpu_baseline, nothing else)
+    python bench.py --full --headline-only                   (the headline leg + roofline + cpu_baseline, nothing else)
     python bench.py ... --dump-outputs DIR                   (also writes the last timed step's output as DIR/cost.npy)
 
 Workload (N=1): BASELINE.json configs[1], "Global scene model: 1242x375, 192 disparities, full 3D hourglass fwd, batch=1 on 1
@@ -16,16 +17,18 @@ build_cost_volume + the 3D stack, inputs resident in HBM.  Multi-GPU = one proce
 sharding, no data-path collective): weak scaling.
 
 Output (benchlib/emit.py holds the rule): ONE bare-JSON line, the result, LAST on stdout of rank 0 -- compact; everything else
-any rank prints is prefixed `[tag] ` (per-rank records on stderr, the long form of the result as `[bench_detail] {...}` and in
-gpurun_out/bench_detail.json).  A provisional result line (headline + roofline + cpu_baseline) goes out as soon as those exist, so
-that a crash in a later leg still leaves a parsable headline; the final line replaces it by coming later.
+any rank prints is prefixed `[tag] ` (per-rank records on stderr, the long form of the result as `[bench_detail] {...}` and, best
+effort, as a file: benchlib/emit.py).  A --full run prints a provisional result line (headline + roofline + cpu_baseline) as soon as
+those exist, so that a crash in a later leg still leaves a parsable headline; the final line replaces it by coming later.
+A plain run (no --full) sets up, runs the one timed leg of `value` and prints what that leg measured: the entries below without a
+"+".  --full runs every other leg as well and adds the entries marked "+":
   value / ms_per_step     GlobalStack.forward_pair, the contract's timing (W warm-up, K steps barrier to barrier, max over ranks)
-  dtype / value_fp32_mfma the arithmetic the step computes in (split mode: fp32 products as three f16 MFMAs) and the strict fp32-MFMA rate
-  roofline                dominant kernel (conv2 + side head), HIP events on the launch stream inside the timed loop
-  roofline_hbm            the HBM-bound kernels: the first layer's expand pass, the any-shift expand, a1 / a2 builders, gather, a10
-  cpu_baseline            CPU oracle (C/OpenMP cost volume + torch-CPU stack) on one full cfg2 pair, rank 0, N=1
-  parity_vs_cpu_baseline  every timed leg's output against that oracle's on the same inputs and weights
-  configs / train / off_fast_path / sustained   the other BASELINE configs on this GPU, cfg4's step, the slow paths, the >= 5 s rate
+  dtype / value_fp32_mfma the arithmetic the step computes in (split mode: fp32 products as three f16 MFMAs) / + the strict fp32-MFMA rate
+  roofline                dominant kernel (conv2 + side head), HIP events on the launch stream inside the timed loop; + its fp32-MFMA form
++ roofline_hbm            the HBM-bound kernels: the first layer's expand pass, the any-shift expand, a1 / a2 builders, gather, a10
++ cpu_baseline            CPU oracle (C/OpenMP cost volume + torch-CPU stack) on one full cfg2 pair, rank 0, N=1
++ parity_vs_cpu_baseline  every timed leg's output against that oracle's on the same inputs and weights
++ configs / train / off_fast_path / sustained   the other BASELINE configs on this GPU, cfg4's step, the slow paths, the >= 5 s rate
 """
 import argparse
 import os
@@ -62,11 +65,14 @@ def parse_args(argv=None):
     ap.add_argument("--crops", type=int, default=64, help="cfg3: crops per step over all ranks")
     ap.add_argument("--crops-per-call", type=int, default=8)
     ap.add_argument("--no-gather", action="store_true", help="cfg3: skip the all-gather of the occupancy volumes")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the `configs` / `train` / `off_fast_path` legs")
-    ap.add_argument("--headline-only", action="store_true", help="value + roofline + cpu_baseline only (no other legs)")
-    ap.add_argument("--breakdown", action="store_true", help="per-layer timing on stderr (extra untimed pass)")
-    ap.add_argument("--no-sustained", action="store_true", help="skip the >= 5 s sustained-rate leg")
+    ap.add_argument("--full", action="store_true",
+                    help="cfg2: every leg beside `value` as well (the step's other entry points and arithmetic, roofline legs, CPU baseline "
+                         "and parity, other configs, training step, slow paths, sustained rate); without it only `value` is measured")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity against it")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip the `configs` / `train` / `off_fast_path` legs")
+    ap.add_argument("--headline-only", action="store_true", help="--full: value + roofline + cpu_baseline only (no other legs)")
+    ap.add_argument("--breakdown", action="store_true", help="--full: per-layer timing on stderr (extra untimed pass)")
+    ap.add_argument("--no-sustained", action="store_true", help="--full: skip the >= 5 s sustained-rate leg")
     ap.add_argument("--sustained-seconds", type=float, default=5.0)
     ap.add_argument("--sustained-steps", type=int, default=2000)
     ap.add_argument("--rehearse", action="store_true",
@@ -79,6 +85,8 @@ def parse_args(argv=None):
         ap.error("--dump-outputs covers the headline step (--mode infer --config cfg2) only")
     if args.steps < 1:
         ap.error("--steps must be >= 1")
+    if not args.full and (args.no_cpu_baseline or args.no_extras or args.headline_only or args.breakdown or args.no_sustained):
+        ap.error("--no-cpu-baseline, --no-extras, --headline-only, --breakdown and --no-sustained select legs of a --full run")
     return args
 
 
@@ -281,7 +289,9 @@ def main(argv=None):
         raise SystemExit("bench.py needs a GPU (the HIP path has no CPU fallback)")
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
-    dist, joined, rccl_note = init_group("nccl", rank, world, device)
+    plain = args.mode == "infer" and args.config == "cfg2" and not args.full        # the headline figure and nothing else
+    # at N = 1 the group is for the collectives of the training legs: a plain run on one GPU makes none and does not set one up
+    dist, joined, rccl_note = (None, 1, None) if plain and world == 1 else init_group("nccl", rank, world, device)
 
     def barrier():
         torch.cuda.synchronize()
@@ -323,7 +333,7 @@ def main(argv=None):
     # ---- the headline: BASELINE configs[1] through GlobalStack.forward_pair
     from benchlib.headline import Headline
     hd = Headline(args, rank, world, device, dist, barrier)
-    hd.run_core()
+    hd.run_value()
     if args.dump_outputs and rank == 0:
         # forward_pair's return value in the last of the K timed steps of `value`: the cost volume [1, 1, D, H, W] a caller receives
         emit.rank_note("dump_outputs", {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, {"cost": hd.outs["value"]})})
@@ -331,9 +341,18 @@ def main(argv=None):
     emit.rank_note("rank_record", hd.rank_record(joined))         # every rank leaves its own line on stderr (prefixed: not JSON)
     line = hd.core_line(joined) if rank == 0 else None
     need = emit.CONTRACT + ("roofline",)
-    oracle_out = {}
     if rank == 0:
         line["ranks"] = records
+    if plain:
+        if rank == 0:
+            emit.detail_note(line, ROOT)
+            emit.emit_result(line, required=need)      # LAST: nothing is printed after this line by this process
+        return finish()
+
+    hd.run_core()
+    oracle_out = {}
+    if rank == 0:
+        hd.add_core(line)
         if world == 1 and not args.no_cpu_baseline:
             need = emit.REQUIRED
             line["cpu_baseline"] = cpu_baseline(outputs=oracle_out)

@@ -71,8 +71,8 @@ class Headline:
             self.dist.all_reduce(t, op=self.dist.ReduceOp.MAX)
             elapsed = float(t.item())
         assert torch.isfinite(out).all()
-        # 23 MB, compared with the CPU oracle (N = 1) and written by --dump-outputs (rank 0, any N)
-        keep = self.rank == 0 and (self.world == 1 or getattr(a, "dump_outputs", None))
+        # 23 MB, compared with the CPU oracle (--full, N = 1) and written by --dump-outputs (rank 0, any N)
+        keep = self.rank == 0 and ((self.world == 1 and a.full) or getattr(a, "dump_outputs", None))
         self.outs[tag] = out.cpu().numpy() if keep else None
         return elapsed
 
@@ -105,19 +105,22 @@ class Headline:
         return res
 
     # ------------------------------------------------------------------------------------------ the legs
-    def run_core(self):
-        """`value` (+ which routes it took) and the two legs the roofline entries need."""
+    def run_value(self):
+        """`value` (+ which routes it took and the split-mode state it left): all a plain run measures."""
         from snvc_amd.models import submodule as S_
         r0, r1 = S_._ROUTES["sheared_first_conv"], S_._ROUTES["x3_tail"]
         self.leg("value", brackets=("conv2",))
         self.sheared_taken = S_._ROUTES["sheared_first_conv"] > r0
         self.x3_taken = S_._ROUTES["x3_tail"] > r1          # conv2 + hourglass on the split-mode (f16x3) kernels
-        self.leg("first_layer_brackets")                     # the first layer's own brackets (prep chains, expand pass) for `roofline_hbm`
-        # the same step with conv2 and the hourglass on the fp32-MFMA kernels (r1-r3's arithmetic: Winograd F(4,3), v_mfma_f32_32x32x2_f32)
-        self.leg("fp32_mfma", arithmetic="fp32")
         st = self.model.__dict__.get("_snvc_x3")
         self.x3_overflow = int(st["flag"].item()) if st is not None else None       # 0: no value was clamped to half's range
         self.x3_exponents = dict(st["exp"]) if st is not None else None
+
+    def run_core(self):
+        """The two legs the roofline entries of --full need."""
+        self.leg("first_layer_brackets")                     # the first layer's own brackets (prep chains, expand pass) for `roofline_hbm`
+        # the same step with conv2 and the hourglass on the fp32-MFMA kernels (r1-r3's arithmetic: Winograd F(4,3), v_mfma_f32_32x32x2_f32)
+        self.leg("fp32_mfma", arithmetic="fp32")
 
     def run_more(self):
         """The same step on the other entry points (all N; cheap: 20 steps each)."""
@@ -198,7 +201,7 @@ class Headline:
         return None, None
 
     def core_line(self, joined, power_probe=None):
-        """The result line from the core legs alone (metric, value, roofline, roofline_hbm, fp32_mfma)."""
+        """The result line from the `value` leg alone (metric, value, dtype, config, roofline)."""
         a, L, world = self.args, self.legs, self.world
         x3, sheared = self.x3_taken, self.sheared_taken
         elapsed = L["value"]["s"]
@@ -212,10 +215,7 @@ class Headline:
         executed = _tflops(DOM_FLOP * (share_x3 if x3 else share), dom_ms)
         alg = _tflops(DOM_FLOP, dom_ms)
         peak = PEAK_F16_MFMA_TFLOPS if x3 else PEAK_F32_MFMA_TFLOPS
-        f32_ms = L["fp32_mfma"]["conv2"]
-        exec_f32 = _tflops(DOM_FLOP * share, f32_ms)
         traffic, traffic_src = self._traffic()
-        fl = L["first_layer_brackets"]
         line = {
             "metric": "stereo-pairs/sec (cost-volume build + 3D CNN fwd)",
             "value": world * a.steps / elapsed,
@@ -230,14 +230,13 @@ class Headline:
             # the arithmetic type the path computes in: fp32 tensors in and out; in split mode every fp32 product is three f16 MFMAs on
             # (hi, lo) half pairs with fp32 accumulation (22 significand bits).  `value_fp32_mfma` is the strict fp32-MFMA figure.
             "dtype": DTYPE_SPLIT if x3 else "f32",
-            "value_fp32_mfma": world * a.steps / L["fp32_mfma"]["s"],
             "data": "synthetic",
             "config": {
                 "workload": "cfg2 global scene model: 1 pair/GPU, features [1,32,96,312] (1242x375 /4), 192 disparities -> concat volume "
                             "[1,64,192,96,312] -> conv3d x2 + hourglass(32) + classifier",
                 "arithmetic": ("fp32 tensors in and out; conv2 + hourglass in SPLIT MODE (" + ("taken" if x3 else "NOT taken") + "): activations / "
                                "weights travel as (hi, lo) pairs of halves (22 significant bits), each fp32 product = three half-precision MFMAs "
-                               "with fp32 accumulation; `value_fp32_mfma` / `fp32_mfma` repeat the step on the fp32-MFMA kernels"),
+                               "with fp32 accumulation; `value_fp32_mfma` / `fp32_mfma` (--full) repeat the step on the fp32-MFMA kernels"),
                 "arithmetic_note": ("split mode holds the fp32 layers to fp32 accuracy (5e-7 of the range vs float64 per layer; the fp32 Winograd "
                                     "kernels: 2e-6) and to the SAME per-layer 2e-5 / stack 1e-4 tolerances as the fp32 kernels "
                                     "(tests/test_gpu_fullsize_oracle.py, parity_vs_cpu_baseline below)"),
@@ -280,10 +279,22 @@ class Headline:
                 "avg_launch_ms": dom_ms,
                 "traffic": traffic, "traffic_source": traffic_src,
                 "power_probe": power_probe,
-                "fp32_mfma_form": {"kernel": "conv3d_wino_dma_kernel<4x4x32, side head> (Winograd F(4,3), v_mfma_f32_32x32x2_f32)",
-                                   "avg_launch_ms": f32_ms, "achieved": exec_f32, "peak": PEAK_F32_MFMA_TFLOPS,
-                                   "frac": _div(exec_f32, PEAK_F32_MFMA_TFLOPS)},
             },
+            "step_tflops_algorithmic": STEP_FLOP / (elapsed / a.steps) / 1e12,
+        }
+        return line
+
+    def add_core(self, line):
+        """The entries of ``run_core``'s legs: the strict fp32-MFMA rate and form, the first layer's HBM roofline."""
+        a, L, world = self.args, self.legs, self.world
+        f32_ms = L["fp32_mfma"]["conv2"]
+        exec_f32 = _tflops(DOM_FLOP * wino_executed_share(3, W), f32_ms)
+        fl = L["first_layer_brackets"]
+        line["value_fp32_mfma"] = world * a.steps / L["fp32_mfma"]["s"]
+        line["roofline"]["fp32_mfma_form"] = {
+            "kernel": "conv3d_wino_dma_kernel<4x4x32, side head> (Winograd F(4,3), v_mfma_f32_32x32x2_f32)",
+            "avg_launch_ms": f32_ms, "achieved": exec_f32, "peak": PEAK_F32_MFMA_TFLOPS, "frac": _div(exec_f32, PEAK_F32_MFMA_TFLOPS)}
+        line.update({
             "roofline_hbm": {
                 # the headline path's own HBM-bound kernel: conv1's result written along the shear (one 0.74 GB write stream)
                 "kernel": "sheared_expand_split_kernel: the first layer's output of the headline path, written along the shear",
@@ -299,9 +310,7 @@ class Headline:
                         "arithmetic='fp32'): Winograd F(4,3) / polyphase kernels on v_mfma_f32_32x32x2_f32 -- rounds 1-3's arithmetic)",
                 "value": world * a.steps / L["fp32_mfma"]["s"], "ms_per_step": 1e3 * L["fp32_mfma"]["s"] / a.steps,
                 "conv2_ms": f32_ms, "expand_ms": L["fp32_mfma"]["conv1"],
-            },
-            "step_tflops_algorithmic": STEP_FLOP / (elapsed / a.steps) / 1e12,
-        }
+            }})
         return line
 
     def add_more(self, line):

@@ -1,7 +1,8 @@
 """bench.py's output rule (benchlib/emit.py), held to the driver's view of a run: stdout, then `---- stderr ----`, then stderr; the
 LAST line json.loads accepts is the result.  r5 lost its driver measurement to `rank_record` JSON lines on stderr
 (BENCH_r05.json: "the bench printed no result line").  CPU only: the launcher / group / timing protocol / emission run end to
-end through ``bench.py --rehearse`` (gloo, a sleep as the step, no kernel)."""
+end through ``bench.py --rehearse`` (gloo, a sleep as the step, no kernel).  One GPU test runs a plain ``bench.py`` (no --full) in this
+process."""
 import glob
 import json
 import os
@@ -154,3 +155,39 @@ def test_dump_outputs_is_refused_where_there_is_no_headline_step():
     for extra in (["--rehearse"], ["--mode", "train"], ["--config", "cfg3"]):
         rc, out, err = _run(["--steps", "2", "--warmup", "1", "--dump-outputs", "unused"] + extra)
         assert rc == 2 and "--dump-outputs" in err, (extra, err[-500:])
+
+
+def test_full_is_off_by_default_and_the_leg_options_need_it():
+    """A plain run measures `value` alone; the options that pick among the other legs only mean something with --full."""
+    import bench
+    assert bench.parse_args(["--steps", "2", "--warmup", "1"]).full is False
+    legs = ["--no-cpu-baseline", "--no-extras", "--headline-only", "--breakdown", "--no-sustained"]
+    args = bench.parse_args(["--full"] + legs)
+    assert args.full and args.no_cpu_baseline and args.no_extras and args.headline_only and args.breakdown and args.no_sustained
+    for flag in legs:
+        with pytest.raises(SystemExit):
+            bench.parse_args([flag])
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_line_and_nothing_of_full(capsys, monkeypatch, tmp_path):
+    """bench.py without --full, in this process: the contract's line from the one timed leg, last and alone, and the dumped output."""
+    import numpy as np
+    import bench
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE"):
+        monkeypatch.delenv(k, raising=False)
+    bench.main(["--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    cap = capsys.readouterr()
+    text = _capture(cap.out, cap.err)
+    last = emit.last_json_line(text)
+    assert last is not None and len(_bare_json_lines(text)) == 1 and cap.out.strip().splitlines()[-1].startswith("{")
+    for k in emit.CONTRACT + ("roofline",):
+        assert k in last, k
+    assert "provisional" not in last
+    full_only = {"value_fp32_mfma", "fp32_mfma", "roofline_hbm", "cpu_baseline", "parity_vs_cpu_baseline", "overflow_check", "two_launch_tail",
+                 "reference_api", "general_shift", "built_right_half", "materialized", "train", "configs", "off_fast_path", "sustained"}
+    assert not full_only & set(last), full_only & set(last)
+    assert last["steps"] == 3 and last["warmup"] == 1 and last["dtype"].startswith("f32") and last["roofline"]["achieved"] > 0
+    assert last["value"] > 0 and abs(last["value"] * last["ms_per_step"] / 1e3 - 1.0) < 1e-6
+    cost = np.load(tmp_path / "cost.npy")
+    assert cost.shape == (1, 1, bench.D, bench.H, bench.W) and cost.dtype == np.float32 and np.isfinite(cost).all()
