@@ -232,7 +232,8 @@ typedef struct {
     int32_t ksize_d;    /* kernel extent along D: 0 = cubic (= ksize); 1 = depth-1 layer, i.e. an nn.Conv2d(k, stride,
                            padding=(k-1)/2) of the 2D BEV neck (snvc/models/vernier.py:296-313, submodule.py:11-29,
                            270-361) run on the [N,C,1,H,W] view of its NCHW tensors: Din = Dout = 1, k in {1,3}, stride
-                           in {1,2} applied to H and W only, weight [Cout,Cin,k,k] */
+                           in {1,2} applied to H and W only, weight [Cout,Cin,k,k]; also k = 3, stride 1, dilation 2,
+                           pad 2 (the dilated layers of the DSGN image backbone, submodule.py:363-460), direct form only */
     int32_t ksize_h;    /* kernel extent along H of a depth-1 layer: 0 = ksize; 3 with ksize = 7 is the 3 x 7 layer of the
                            sheared first convolution (weight [Cout,Cin,3,7], padding (1,3)); anything else unsupported */
     int64_t x_batch_stride, y_batch_stride, res_batch_stride; /* elements; 0 = dense */

@@ -2220,7 +2220,7 @@ enum Kind {
     K5D2_M1, K5D2_M2,
     K7_M1, K7_M2,
     DC_M1, DC_M2, DCP_M1,
-    P1_M1S, P1S2_M1S, P3_M1S, P3S2_M1S, P7_M1S,                          // depth-1 (2D) layers, 1 x 4 x 32 tiles
+    P1_M1S, P1S2_M1S, P3_M1S, P3S2_M1S, P7_M1S, P3D2_M1S,                // depth-1 (2D) layers, 1 x 4 x 32 tiles
     KIND_NONE
 };
 
@@ -2253,6 +2253,9 @@ using CfgP3M1s   = ConvCfg<3, 1, 1, 1, 1, 4, 16, true, 2, 0, 1>;
 using CfgP3S2M1s = ConvCfg<3, 2, 1, 1, 1, 4, 8, true, 2, 0, 1>;
 // 3 (H) x 7 (W), stride 1: the sheared first convolution of the global model (sheared_conv.hip; desc.ksize_h = 3, ksize = 7)
 using CfgP7M1s   = ConvCfg<7, 1, 1, 1, 1, 4, 8, true, 2, 0, 1, 3>;
+// 3 x 3, dilation 2, padding 2, stride 1: layer4 of the DSGN image backbone (snvc/models/submodule.py:363-460, BasicBlock with
+// dilation 2).  The taps are two rows / two columns apart; the staged tile grows by the wider halo (8 x 40 floats per channel)
+using CfgP3D2M1s = ConvCfg<3, 1, 2, 1, 1, 4, 16, true, 2, 0, 1>;
 using CfgWino   = WinoCfg<2, 4, 2>;          // k3/s1 fast path: 2 x 4 rows x 64 voxels, 2 input channels per chunk
 using CfgWinoBig = WinoCfg<4, 4, 2>;        // LDS-DMA staged, two row pairs per wave: large layers
 using CfgWino8  = WinoCfg<2, 4, 2, 2>;
@@ -2300,17 +2303,21 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
     } else if (d.ksize_d == 1) {
         // depth-1 layer: nn.Conv2d(k, stride, padding=(k-1)/2) on an [N,C,1,H,W] view; the stride applies to H and W only
         // (k = 1, stride 2 is BasicBlock's downsample path, hrnet.py:56-69)
-        if (d.Din != 1 || d.Dout != 1 || d.dilation != 1 || d.pad != (d.ksize - 1) / 2)
-            return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: ksize_d = 1 needs Din = Dout = 1, dilation 1, pad = (ksize-1)/2");
+        // dilation 2 (pad 2) is built for 3 x 3 / stride 1 only: the dilated layers of the DSGN image backbone
+        const bool dil2 = d.dilation == 2 && d.ksize == 3 && d.stride == 1 && d.ksize_h == 0 && d.pad == 2;
+        if (d.Din != 1 || d.Dout != 1 || !(dil2 || (d.dilation == 1 && d.pad == (d.ksize - 1) / 2)))
+            return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: ksize_d = 1 needs Din = Dout = 1 and dilation 1, pad = (ksize-1)/2 "
+                                              "(or ksize 3, stride 1, dilation 2, pad 2)");
         const int kh_ = d.ksize_h ? d.ksize_h : d.ksize;      // kernel extent along H (its padding is (ksize_h-1)/2)
         if (kh_ != d.ksize && !(d.ksize == 7 && kh_ == 3 && d.stride == 1))
             return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: ksize_h != ksize is built for the 3 x 7 depth-1 layer only");
         if (d.ksize == 7 && kh_ != 3)
             return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: depth-1 ksize 7 is built as the 3 x 7 layer (ksize_h = 3)");
-        const int eH = (d.Hin + 2 * ((kh_ - 1) / 2) - kh_) / d.stride + 1, eW = (d.Win + 2 * d.pad - d.ksize) / d.stride + 1;
+        const int eH = dil2 ? d.Hin : (d.Hin + 2 * ((kh_ - 1) / 2) - kh_) / d.stride + 1,
+                  eW = dil2 ? d.Win : (d.Win + 2 * d.pad - d.ksize) / d.stride + 1;
         if (d.Hout != eH || d.Wout != eW)
             return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d: output size does not match the convolution arithmetic");
-        const int key = d.ksize * 10 + d.stride;
+        const int key = dil2 ? 312 : d.ksize * 10 + d.stride;
         // one 32-channel group per workgroup on 1 x 4 x 32 tiles whatever the layer (see CfgP*s above)
         (void)wide;
         switch (key) {
@@ -2319,6 +2326,7 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
             case 31: p = plan_of<CfgP3M1s>(P3_M1S); break;
             case 32: p = plan_of<CfgP3S2M1s>(P3S2_M1S); break;
             case 71: p = plan_of<CfgP7M1s>(P7_M1S); break;
+            case 312: p = plan_of<CfgP3D2M1s>(P3D2_M1S); break;
             default: return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: depth-1 layers are built for ksize 1 and 3 (stride 1 and 2) and 3 x 7 (stride 1)");
         }
         p.tiles_d = 1; p.tiles_h = ceil_div(d.Hout, p.TH); p.tiles_w = ceil_div(d.Wout, 32);
@@ -2967,6 +2975,7 @@ int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *
         case P3_M1S: launch_conv<CfgP3M1s, true>(a, grid, st); break;
         case P3S2_M1S: launch_conv<CfgP3S2M1s, true>(a, grid, st); break;
         case P7_M1S: launch_conv<CfgP7M1s>(a, grid, st); break;
+        case P3D2_M1S: launch_conv<CfgP3D2M1s, true>(a, grid, st); break;
         case DC_M1:
             if (!a.vec && vec8) { a.vec = 1; launch_deconv<CfgDCM1v8>(a, grid, st); }
             else launch_deconv<CfgDCM1>(a, grid, st);

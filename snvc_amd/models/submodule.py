@@ -29,7 +29,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import ops
+from .. import _dsgn, ops
 from .._derived import derived, fresh, invalidate_all, stamp
 from ..ops import EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID
 
@@ -1545,13 +1545,15 @@ def _affine2d(conv, norm, plan: _Plan):
 
 
 def fused_conv2d(conv: nn.Conv2d, norm, x: torch.Tensor, *, relu=False, sigmoid=False, residual=None,
-                 residual_after_act=False, transposed_input=False) -> torch.Tensor:
+                 residual_after_act=False, transposed_input=False, out=None) -> torch.Tensor:
     """act(norm(conv(x)) [+ residual]) [+ residual] for the 2D neck (reference submodule.py:11-29, hrnet.py:25-69)
     on the depth-1 HIP kernels.  conv: Conv2d(k in {1,3}, stride in {1,2}, padding=(k-1)/2) -- or a Conv2d whose
     kernel covers its whole input (the coordinate head's last layer, vernier.py:87), run as a 1x1 layer.
     ``transposed_input``: returns ``conv(x.transpose(2, 3))`` as a transposed VIEW of the convolution of x itself with the
     kernel's two spatial axes swapped (a convolution commutes with swapping H and W if its kernel is swapped too): the
-    copy that ``permute(0, 1, 3, 2).contiguous()`` would make of the C-channel input is not made (vernier.py:441-442)."""
+    copy that ``permute(0, 1, 3, 2).contiguous()`` would make of the C-channel input is not made (vernier.py:441-442).
+    A Conv2d(k3, stride 1, dilation 2, padding 2) (layer4 of the DSGN backbone) runs on the direct depth-1 form, for inference
+    only.  ``out``: an [N,Cout,H,W] channel slice of a wider buffer to write the result into (inference only)."""
     plan = _plan2d(conv, x.device)
     w = conv.weight
     kh, kw = conv.kernel_size
@@ -1562,9 +1564,16 @@ def fused_conv2d(conv: nn.Conv2d, norm, x: torch.Tensor, *, relu=False, sigmoid=
                                 residual_after_act=residual_after_act)
         plan = conv.__dict__.setdefault("_snvc_plans2d_t", {}).setdefault(x.device, _Plan())
 
+    dilated = tuple(conv.dilation) != (1, 1)
+
     def build():
-        if conv.groups != 1 or tuple(conv.dilation) != (1, 1):
-            raise NotImplementedError("grouped / dilated Conv2d is not in the 2D neck")
+        if dilated:
+            if conv.groups != 1 or (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.dilation)) != \
+                    ((3, 3), (1, 1), (2, 2), (2, 2)) or transposed_input:
+                raise NotImplementedError(f"dilated Conv2d {conv}: only 3x3 / stride 1 / dilation 2 / padding 2 is on the path")
+            return ops.Conv3dLayer(w.detach(), 3, 1, 2, 2, False, planar=True)
+        if conv.groups != 1:
+            raise NotImplementedError("grouped Conv2d is not in the 2D neck")
         if whole:      # one output pixel: a 1x1 layer over the flattened (c, h, w) input
             return ops.Conv3dLayer(w.detach().reshape(w.size(0), -1, 1, 1, 1), 1, 1, 0, 1, False, planar=True)
         k, st = kh, conv.stride[0]
@@ -1578,14 +1587,19 @@ def fused_conv2d(conv: nn.Conv2d, norm, x: torch.Tensor, *, relu=False, sigmoid=
         flags |= EPI_ADD_POST if residual_after_act else EPI_ADD_PRE
     x5 = x.reshape(x.size(0), -1, 1, 1, 1) if whole else x.unsqueeze(2)
     r5 = residual.unsqueeze(2) if residual is not None else None
+    o5 = out.unsqueeze(2) if out is not None else None
     if _train2d(x, conv, norm, residual):
+        if dilated or out is not None:
+            raise NotImplementedError("a dilated Conv2d / an `out` slice has no HIP backward: inference only")
         kind = ("whole",) if whole else ("conv", kh, conv.stride[0])
         y = _conv2d_train(conv, norm, x5.contiguous(), r5.contiguous() if r5 is not None else None, flags, plan, kind, layer)
         return y.squeeze(2)
+    if dilated:
+        _ROUTES["conv2d_dilated_direct"] += 1
     scale, bias = _affine2d(conv, norm, plan)
     if isinstance(norm, nn.GroupNorm):
-        return _group_norm_2d(layer(x5, scale, bias), norm, r5, flags).squeeze(2)
-    y = layer(x5, scale, bias, r5, flags).squeeze(2)
+        return _group_norm_2d(layer(x5, scale, bias, out=o5), norm, r5, flags).squeeze(2)
+    y = layer(x5, scale, bias, r5, flags, out=o5).squeeze(2)
     return y.transpose(2, 3) if transposed_input else y
 
 
@@ -1746,3 +1760,198 @@ def basicdownsample(in_planes, out_planes):
     """snvc/models/hrnet.py:56-69"""
     return nn.Sequential(nn.Conv2d(in_planes, out_planes, kernel_size=1, stride=2, bias=False),
                          nn.BatchNorm2d(out_planes))
+
+
+# ------------------------------------------------------------------------------------------
+# DSGN image backbone (reference submodule.py:52-74, 363-512): the stereo feature extractor of the global model.  Same
+# constructors, module tree and ordered state-dict keys as the reference for every cfg.backbone, so a reference
+# checkpoint loads with strict=True.  On a float32 GPU tensor with nothing to differentiate and eval-mode BatchNorm2d /
+# GroupNorm everywhere, forward runs on the HIP kernels:
+#
+#   reference                                           here
+#   --------------------------------------------------- ---------------------------------------------------------------
+#   convbn + ReLU, BasicBlock (residual add, no ReLU)   one depth-1 conv launch each: norm folded (GroupNorm: conv ->
+#                                                         statistics -> normalise), ReLU / residual in the epilogue;
+#                                                         layer4's 3x3 dilation-2 layers on the dilated direct form
+#   layer2 / layer3 / layer4 outputs, torch.cat         the last block of each writes its channel slice of the concat
+#                                                         buffer; the next layer reads its input from that slice
+#   branch1..4: AvgPool2d(64/32/16/8), convbn, ReLU,    ONE pooling launch (snvc_dsgn_spp_pool) for the four windows,
+#     F.interpolate(bilinear) each                        four 1x1 launches, ONE upsampling launch into the four slices
+#   rpnconv, lastconv                                   one launch per convolution, reading the concat buffer
+#
+# Anything else (autograd with something that requires grad, train-mode BatchNorm, DSGN_HIP[0] = False) runs the modules'
+# own torch forward.  Every decision is counted in _ROUTES as "dsgn_hip" / "dsgn_torch"; the dilated layers count
+# "conv2d_dilated_direct".  The HIP route is inference only: training through it would need a dilated depth-1 weight
+# gradient.  There is no CPU path: a CPU input raises.
+# ------------------------------------------------------------------------------------------
+DSGN_HIP = [True]       # False: feature_extraction / BasicBlock take the modules' torch forward
+
+
+class BasicBlock(nn.Module):
+    """reference submodule.py:52-74 (the DSGN backbone's block; HRNet's is BasicBlock2d)"""
+    expansion = 1
+
+    def __init__(self, inplanes, planes, stride, downsample, pad, dilation, gn=False):
+        super().__init__()
+        self.conv1 = nn.Sequential(convbn(inplanes, planes, 3, stride, pad, dilation, gn=gn), nn.ReLU(inplace=True))
+        self.conv2 = convbn(planes, planes, 3, 1, pad, dilation, gn=gn)
+        self.downsample = downsample
+        self.stride = stride
+
+    def forward(self, x):
+        return _dsgn_block(self, x, _dsgn_hip_ok(x, self))
+
+
+def _dsgn_hip_ok(x: torch.Tensor, module: nn.Module) -> bool:
+    """The HIP route of the DSGN backbone: a float32 GPU tensor, nothing to differentiate, every norm a GroupNorm or an
+    eval-mode BatchNorm2d with running statistics, and DSGN_HIP[0]."""
+    if not x.is_cuda:
+        raise RuntimeError("DSGN backbone input must be a GPU tensor: Not implemented on the CPU")
+    ok = (DSGN_HIP[0] and x.dtype == torch.float32 and not _wants_grad2d(x, module)
+          and all(isinstance(n, nn.GroupNorm) or (isinstance(n, nn.BatchNorm2d) and not n.training and n.running_mean is not None)
+                  for n in _norms2d(module)))
+    _ROUTES["dsgn_hip" if ok else "dsgn_torch"] += 1
+    return ok
+
+
+def _dsgn_block(b: BasicBlock, x, hip, out=None):
+    """bn2(conv2(relu(bn1(conv1(x))))) + (x or downsample(x)), no ReLU after the add (submodule.py:65-74)."""
+    if hip:
+        residual = x if b.downsample is None else fused_conv2d(b.downsample[0], b.downsample[1], x)
+        y = fused_conv2d(b.conv1[0][0], b.conv1[0][1], x, relu=True)
+        return fused_conv2d(b.conv2[0], b.conv2[1], y, residual=residual, out=out)
+    y = b.conv2(b.conv1(x))
+    if b.downsample is not None:
+        x = b.downsample(x)
+    y += x
+    return y
+
+
+def _dsgn_layer(seq, x, hip, out=None):
+    for i, b in enumerate(seq):
+        x = _dsgn_block(b, x, hip, out=out if i == len(seq) - 1 else None)
+    return x
+
+
+def _dsgn_head(seq, x):
+    """A Sequential of convbn / bare Conv2d / ReLU (rpnconv, lastconv) on the HIP route: one launch per convolution, the
+    ReLU that follows it in the epilogue."""
+    mods = list(seq)
+    for i, m in enumerate(mods):
+        if isinstance(m, nn.ReLU):
+            continue
+        relu = i + 1 < len(mods) and isinstance(mods[i + 1], nn.ReLU)
+        conv, norm = (m[0], m[1]) if isinstance(m, nn.Sequential) else (m, None)
+        x = fused_conv2d(conv, norm, x, relu=relu)
+    return x
+
+
+BACKBONES = {   # backbone -> (first_dim, dims, nr_convs, branch_dim, lastconv_dim), submodule.py:375-410
+    "reslike-det": (64, (64, 128, 192, 256), (3, 6, 12, 4), 32, (256, 32)),
+    "reslike-det-small": (64, (32, 64, 128, 192), (3, 6, 12, 4), 32, (256, 32)),
+    "reslike-det-small-fixfirst": (16, (32, 64, 128, 192), (3, 6, 12, 4), 32, (256, 32)),
+    "reslike50-det-small-fixfirst": (16, (32, 64, 128, 256), (3, 4, 6, 3), 32, (256, 32)),
+    "reslike50-det-tiny": (8, (16, 32, 64, 128), (3, 4, 6, 3), 32, (128, 32)),
+}
+
+
+class feature_extraction(nn.Module):
+    """reference submodule.py:363-512: the DSGN ResNet-like trunk with the SPP head.  forward(x) returns
+    (output_feature, rpn_feature), None where the configuration has no such head."""
+
+    def __init__(self, cfg):
+        super().__init__()
+        self.cfg = cfg
+        self.RPN3D_ENABLE = self.cfg.RPN3D_ENABLE
+        self.cat_img_feature = getattr(self.cfg, "cat_img_feature", False)
+        self.rpn_onemore_conv = getattr(self.cfg, "RPN_ONEMORE_CONV", False)
+        self.rpn_onemore_dim = getattr(self.cfg, "RPN_ONEMORE_DIM", 256)
+        self.img_feature_relu = getattr(self.cfg, "img_feature_relu", True)
+        self.branch = getattr(self.cfg, "branch", True)
+        self.backbone = getattr(self.cfg, "backbone", "reslike-det-small")
+        if self.backbone not in BACKBONES:
+            raise ValueError("Invalid backbone {}.".format(self.backbone))
+        first_dim, dims, nr_convs, branch_dim, lastconv_dim = BACKBONES[self.backbone]
+        gn = cfg.GN
+        self.inplanes = first_dim
+        fgn = gn if first_dim >= 32 else False
+        self.firstconv = nn.Sequential(convbn(3, first_dim, 3, 2, 1, 1, gn=fgn), nn.ReLU(inplace=True),
+                                       convbn(first_dim, first_dim, 3, 1, 1, 1, gn=fgn), nn.ReLU(inplace=True),
+                                       convbn(first_dim, first_dim, 3, 1, 1, 1, gn=fgn), nn.ReLU(inplace=True))
+        self.layer1 = self._make_layer(BasicBlock, dims[0], nr_convs[0], 1, 1, 1, gn=gn if dims[0] >= 32 else False)
+        self.layer2 = self._make_layer(BasicBlock, dims[1], nr_convs[1], 2, 1, 1, gn=gn)
+        self.layer3 = self._make_layer(BasicBlock, dims[2], nr_convs[2], 1, 1, 1, gn=gn)
+        self.layer4 = self._make_layer(BasicBlock, dims[3], nr_convs[3], 1, 1, 2, gn=gn)
+        if self.branch:
+            for i, k in enumerate((64, 32, 16, 8)):
+                setattr(self, f"branch{i + 1}", nn.Sequential(nn.AvgPool2d((k, k), stride=(k, k)),
+                                                              convbn(dims[3], branch_dim, 1, 1, 0, 1, gn=gn, groups=min(32, branch_dim)),
+                                                              nn.ReLU(inplace=True)))
+        concat_dim = dims[1] + dims[2] + dims[3] + (branch_dim * 4 if self.branch else 0)
+        self.PlaneSweepVolume = getattr(cfg, "PlaneSweepVolume", True)
+        if self.PlaneSweepVolume:
+            self.lastconv = nn.Sequential(convbn(concat_dim, lastconv_dim[0], 3, 1, 1, 1, gn=gn), nn.ReLU(inplace=True),
+                                          nn.Conv2d(lastconv_dim[0], lastconv_dim[1], kernel_size=1, padding=0, stride=1, bias=False))
+        if self.cfg.RPN3D_ENABLE and self.cat_img_feature:
+            last_groups = 32 if self.cfg.RPN_CONVDIM % 32 == 0 else 16
+            if self.rpn_onemore_conv:
+                rpnconvs = [convbn(concat_dim, self.rpn_onemore_dim, 3, 1, 1, 1, gn=gn), nn.ReLU(inplace=True),
+                            convbn(self.rpn_onemore_dim, self.cfg.RPN_CONVDIM, 3, 1, 1, 1, gn=gn, groups=last_groups)]
+            else:
+                rpnconvs = [convbn(concat_dim, self.cfg.RPN_CONVDIM, 3, 1, 1, 1, gn=gn, groups=last_groups)]
+            if self.img_feature_relu:
+                rpnconvs.append(nn.ReLU(inplace=True))
+            self.rpnconv = nn.Sequential(*rpnconvs)
+        self._dims, self._branch_dim, self._concat_dim = dims, branch_dim, concat_dim
+
+    def _make_layer(self, block, planes, blocks, stride, pad, dilation, gn=False):
+        """submodule.py:462-476"""
+        downsample = None
+        if stride != 1 or self.inplanes != planes * block.expansion:
+            downsample = nn.Sequential(nn.Conv2d(self.inplanes, planes * block.expansion, kernel_size=1, stride=stride, bias=False),
+                                       nn.BatchNorm2d(planes * block.expansion) if not gn else nn.GroupNorm(32, planes * block.expansion))
+        layers = [block(self.inplanes, planes, stride, downsample, pad, dilation, gn=gn)]
+        self.inplanes = planes * block.expansion
+        layers += [block(self.inplanes, planes, 1, None, pad, dilation, gn=gn) for _ in range(1, blocks)]
+        return nn.Sequential(*layers)
+
+    def _branches(self):
+        return [getattr(self, f"branch{i}") for i in (1, 2, 3, 4)]
+
+    def _forward_torch(self, x):
+        """submodule.py:478-512 with the modules' own forward."""
+        output = _dsgn_layer(self.layer1, self.firstconv(x), False)
+        output_raw = _dsgn_layer(self.layer2, output, False)
+        output_mid = _dsgn_layer(self.layer3, output_raw, False)
+        output_skip = _dsgn_layer(self.layer4, output_mid, False)
+        parts = [output_raw, output_mid, output_skip]
+        if self.branch:
+            size = (output_skip.size(2), output_skip.size(3))
+            ups = [F.interpolate(b(output_skip), size, mode="bilinear", align_corners=self.cfg.align_corners) for b in self._branches()]
+            parts += ups[::-1]                              # branch4, branch3, branch2, branch1
+        concat_feature = torch.cat(parts, 1)
+        rpn_feature = self.rpnconv(concat_feature) if self.RPN3D_ENABLE and self.cat_img_feature else None
+        output_feature = self.lastconv(concat_feature) if self.PlaneSweepVolume else None
+        return output_feature, rpn_feature
+
+    def _forward_hip(self, x):
+        y = x
+        for i in (0, 2, 4):
+            y = fused_conv2d(self.firstconv[i][0], self.firstconv[i][1], y, relu=True)
+        y = _dsgn_layer(self.layer1, y, True)
+        d1, d2, d3 = self._dims[1:]
+        n, h, w = y.size(0), (y.size(2) + 1) // 2, (y.size(3) + 1) // 2       # layer2's stride-2 output extent
+        cat = torch.empty((n, self._concat_dim, h, w), dtype=torch.float32, device=x.device)
+        raw = _dsgn_layer(self.layer2, y, True, out=cat[:, :d1])
+        mid = _dsgn_layer(self.layer3, raw, True, out=cat[:, d1:d1 + d2])
+        skip = _dsgn_layer(self.layer4, mid, True, out=cat[:, d1 + d2:d1 + d2 + d3])
+        if self.branch:
+            pools = _dsgn.spp_pool(skip)                   # windows 8, 16, 32, 64: the inputs of branch4 .. branch1
+            maps = [fused_conv2d(b[1][0], b[1][1], p, relu=True) for b, p in zip(self._branches()[::-1], pools)]
+            _dsgn.spp_upsample(maps, cat[:, d1 + d2 + d3:], self.cfg.align_corners)
+        rpn_feature = _dsgn_head(self.rpnconv, cat) if self.RPN3D_ENABLE and self.cat_img_feature else None
+        output_feature = _dsgn_head(self.lastconv, cat) if self.PlaneSweepVolume else None
+        return output_feature, rpn_feature
+
+    def forward(self, x):
+        return self._forward_hip(x) if _dsgn_hip_ok(x, self) else self._forward_torch(x)

@@ -308,6 +308,9 @@ class Conv3dLayer:
         if self.transposed:
             return tuple(2 * s for s in in_spatial)
         eff = self.dilation * (self.ksize - 1) + 1
+        if getattr(self, "planar", False) and self.dilation > 1:     # 3 x 3, dilation 2, pad 2: "same" along H and W
+            return (in_spatial[0], (in_spatial[1] + 2 * self.pad - eff) // self.stride + 1,
+                    (in_spatial[2] + 2 * self.pad - eff) // self.stride + 1)
         if getattr(self, "planar", False):      # the stride and the padding apply to H and W only
             kh = getattr(self, "ksize_h", 0) or self.ksize
             return (in_spatial[0], (in_spatial[1] + 2 * ((kh - 1) // 2) - kh) // self.stride + 1,
