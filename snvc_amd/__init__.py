@@ -7,6 +7,7 @@
     snvc_amd.models.submodule              <->  snvc.models.submodule (3D blocks)
     snvc_amd.models.vernier                <->  snvc.models.vernier   (VernierScale 3D trunk)
     snvc_amd.models.hrnet                  <->  snvc.models.hrnet     (HRNet backbone; install_as_snvc(backbone="hip"))
+    snvc_amd.models.loss3d                 <->  snvc.models.loss3d    (training losses)
 
 Everything executes in hand-written HIP kernels from ``libsnvc_hip.so`` (C ABI:
 ``include/snvc_hip.h``, ``include/snvc_iou3d.h``, ``include/snvc_hrnet.h``).  There is no CPU path: CPU tensors raise, and a missing shared
@@ -21,6 +22,7 @@ _ALIASES = {
     "snvc.extension.iou3d_nms.iou3d_nms_utils": "snvc_amd.extension.iou3d_nms.iou3d_nms_utils",
     "snvc.models.submodule": "snvc_amd.models.submodule",
     "snvc.models.vernier": "snvc_amd.models.vernier",
+    "snvc.models.loss3d": "snvc_amd.models.loss3d",
 }
 
 

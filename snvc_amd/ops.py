@@ -1118,9 +1118,29 @@ def zero_stuff2x(x):
     return y
 
 
+class _DisparityRegression(torch.autograd.Function):
+    """``disparity_regression`` with a gradient for ``x`` (none for ``depth``: the reference's depth levels are constants)."""
+
+    @staticmethod
+    def forward(ctx, x, depth):
+        ctx.save_for_backward(depth)
+        ctx.planes = x.size(1)
+        return disparity_regression(x.detach(), depth)
+
+    @staticmethod
+    def backward(ctx, gy):
+        from . import _loss
+        (depth,) = ctx.saved_tensors
+        return _loss.disparity_regression_backward(gy.to(torch.float32).contiguous(), depth.contiguous(), ctx.planes), None
+
+
 def disparity_regression(x, depth):
-    """disparityregression.forward (submodule.py:81-83): [N,D,H,W] x [D] -> [N,H,W]."""
+    """disparityregression.forward (submodule.py:81-83): [N,D,H,W] x [D] -> [N,H,W].  Differentiable with respect to ``x``."""
     _gpu(x, "x"); _gpu(depth, "depth")
+    if x.requires_grad and torch.is_grad_enabled():
+        if x.dim() != 4 or x.dtype != torch.float32 or depth.dtype != torch.float32 or depth.numel() != x.size(1):
+            raise RuntimeError("disparity_regression: the autograd form needs float32 x [N,D,H,W] and float32 depth [D]")
+        return _DisparityRegression.apply(x, depth)
     x, depth = x.contiguous(), depth.contiguous()
     n, d, h, w = x.shape
     if depth.numel() != d:
