@@ -14,7 +14,6 @@ blocks (``convbn_3d``, ``hourglass``) and the composition pattern of VernierScal
     cost = conv1x1x1(v)           C  -> 1                        classifier
 """
 import itertools
-import math
 import warnings
 import weakref
 
@@ -24,9 +23,10 @@ import torch.nn as nn
 from ..extension.build_cost_volume import _BuildCostVolume, build_cost_volume  # noqa: F401  (re-exported)
 from .. import ops
 from .._derived import derived, fresh, stamp
-from .submodule import (_ROUTES, ConvBNReLU3d, HipConv3d, SplitOverflow, _FactoredFirstConvFn, _ShearedFirstConvBNFn,
-                        _ShearedFirstConvFn, _folded_bn, _is_channel_head as _is_head_conv, _Plan, convbn_3d, folded_head_weights,
-                        hourglass, overflow_guard, sheared_geometry, sheared_kernels, EPI_RELU)
+from .submodule import (_ROUTES, SCRATCH_ATTRS, WORKSPACE_ATTRS, X3_GROUP_NORM, ConvBNReLU3d, HipConv3d, SplitModePolicy, SplitOverflow,
+                        SplitT, _FactoredFirstConvFn, _ShearedFirstConvBNFn, _ShearedFirstConvFn, _folded_bn,
+                        _is_channel_head as _is_head_conv, _Plan, convbn_3d, folded_head_weights, hourglass, overflow_guard, plan_for,
+                        sheared_geometry, sheared_kernels, x3_exponent, x3_norm_bound, EPI_RELU, SHEAR_CLASS_KDS)
 
 _PREP_EPOCH = itertools.count(1)      # stamps of the per-model first-layer prep buffers (see _forward_pair_steps)
 
@@ -42,7 +42,22 @@ def _factored_plans(conv: nn.Module, c: int) -> dict:
     return plans
 
 
-class GlobalStack(nn.Module):
+def _mark(timing, name, which):
+    """Record the start (0) / end (1) event of bracket ``name`` on the current stream, if the caller asked for that bracket."""
+    if timing is not None and name in timing:
+        timing[name][which].record()
+
+
+def _run(gen):
+    """A generator run to its end: its return value."""
+    try:
+        while True:
+            next(gen)
+    except StopIteration as done:
+        return done.value
+
+
+class GlobalStack(SplitModePolicy, nn.Module):
     def __init__(self, c=32, gn=False):
         super().__init__()
         self.conv1 = ConvBNReLU3d(convbn_3d(2 * c, c, 3, 1, 1, gn=gn), nn.ReLU(inplace=True))
@@ -95,21 +110,18 @@ class GlobalStack(nn.Module):
 
     def release_workspace(self):
         """Drop the persistent inference workspace (2.2 GB at cfg2)."""
-        self.__dict__.pop("_snvc_ws", None)
-        self.__dict__.pop("_snvc_prep_ws", None)
+        for name in WORKSPACE_ATTRS:
+            self.__dict__.pop(name, None)
 
     def train(self, mode: bool = True):
         if mode:
             self.release_workspace()
         return super().train(mode)
 
-    def __getstate__(self):          # copy.deepcopy / torch.save(model): the workspace is scratch, not state
+    def __getstate__(self):          # copy.deepcopy / torch.save(model): workspace, packed split-mode layers, overflow flag, streams are scratch
         state = self.__dict__.copy()
-        state.pop("_snvc_ws", None)
-        state.pop("_snvc_x3", None)      # packed split-mode layers: rebuilt on first use
-        state.pop("_snvc_x3_guard", None)    # the overflow flag, its pinned host copy and an event
-        state.pop("_snvc_streams", None)
-        state.pop("_snvc_prep_ws", None)
+        for name in SCRATCH_ATTRS:
+            state.pop(name, None)
         return state
 
     # ------------------------------------------------------------------------------------------ split mode ("f16x3", r4)
@@ -118,28 +130,15 @@ class GlobalStack(nn.Module):
     # is three v_mfma_f32_32x32x16_f16 with fp32 accumulation, measured 5e-7 of the range against float64 where the fp32
     # Winograd kernels measure 2e-6 -- on a matrix pipe 16 times faster than the fp32 one.  ``arithmetic``: "auto" (default:
     # split mode when the stack qualifies), "fp32" (the fp32-MFMA kernels everywhere), "x3" (split mode or an error).
-    # A split tensor's exponent is chosen from its BatchNorm's parameters; a value beyond that range is clamped by the epilogue
-    # and FLAGGED.  ``overflow_check`` = "call" (default, r5): the flag is read before the result leaves the call -- the copy is
-    # queued behind the last layer that can clamp, the host waits for it after queueing the rest, so the GPU never idles -- and
-    # a flagged call is REDONE on the fp32-MFMA kernels ("auto": with a warning, and split mode stays off for this model;
-    # "x3": RuntimeError).  No clamped result is ever returned.  "deferred" (r4's behaviour, for measuring what the check
-    # costs): the flag is only posted; ``check_overflow()`` or the next call looks at it.
+    # What happens when a value leaves a split tensor's range (``overflow_check``, ``check_overflow()``, ``reset_split_mode()``):
+    # split_mode.SplitModePolicy.
     arithmetic = "auto"
-    overflow_check = "call"
     # the first layer's 0.74 GB split pair written with non-temporal stores (SNVC_EPI_STREAM_OUT): the expand pass alone gains 9 % (182 ->
     # 165 us back to back) but the step LOSES 0.013 ms (tools/ab_step.py, profiles/r5/ab_step_v5.txt): conv2 reads the pair right
     # behind it.  Off.
     stream_out = False
     split_prep = True    # split mode: the sheared first layer's depth-1 3 x 7 layers (G, G') on the half pipe too (False: fp32 MFMA, as r4)
     fused_tail = True    # split mode: conv5's epilogue contracts its result with the folded one-channel tail (False: r4's two launches)
-    X3_SIGMAS = 64.0     # a tensor's exponent is chosen so that |beta| + X3_SIGMAS * |gamma| of its BatchNorm stays below 2^15
-
-    @staticmethod
-    def _x3_exponent(bound: float) -> int:
-        """e with bound * 2^e <= 2^15 (half overflows at 65504; a value beyond the bound is clamped and FLAGGED)."""
-        if not (bound > 0.0) or not math.isfinite(bound):
-            return 0
-        return max(-14, min(14, 15 - math.frexp(bound)[1]))
 
     def _x3_state(self, device):
         """Packed split-mode layers, folded affines and per-tensor exponents of conv2 + the hourglass, or None when the stack
@@ -159,19 +158,13 @@ class GlobalStack(nn.Module):
         st = self.__dict__.get("_snvc_x3")
         if st is not None and fresh(st["stamp"], tensors, (device,)):
             return st
-
-        def bound(nm):
-            g = nm.weight.detach().abs() if nm.weight is not None else torch.ones(1, device=device)
-            b = nm.bias.detach().abs() if nm.bias is not None else torch.zeros(1, device=device)
-            return float((b + self.X3_SIGMAS * g).max().item())
-        b = {k: bound(sq[1]) for k, sq in seqs.items()}
-        st = {"stamp": stamp(tensors, (device,)), "exp": {"v1": self._x3_exponent(bound(self.conv1[0][1]))}, "layers": {}, "affine": {}}
-        st["exp"].update({k: self._x3_exponent(v) for k, v in b.items()})
+        e = {k: x3_exponent(x3_norm_bound(sq[1], plan_for(sq[0], "_x3", device))) for k, sq in [("v1", self.conv1[0])] + list(seqs.items())}
+        st = {"stamp": stamp(tensors, (device,)), "exp": e, "layers": {}, "affine": {}}
         geo = {"conv2": (1, False), "h1": (2, False), "h2": (1, False), "h3": (2, False), "h4": (1, False), "h5": (2, True)}
         for k, sq in seqs.items():
             w = sq[0].weight.detach().to(device)
             st["layers"][k] = ops.Conv3dLayerX3(w, 3, geo[k][0], 1, 1, geo[k][1])
-            st["affine"][k] = _folded_bn(sq[1], sq[0].__dict__.setdefault("_snvc_plans", {}).setdefault(device, _Plan()))
+            st["affine"][k] = _folded_bn(sq[1], plan_for(sq[0], "", device))
         # `post` = relu(bn(conv5(o)) + pre) exists only inside conv5's epilogue (below); its exponent comes from a HARD bound, not from
         # the statistical one: |conv5(o)| <= (sum of |w| over a parity class's taps and all input channels) * max|o|, and o / pre cannot
         # exceed what their own (checked) exponents allow.  conv5 then cannot clamp once the layers before it have not, so the overflow
@@ -189,7 +182,7 @@ class GlobalStack(nn.Module):
         sc5, bi5 = st["affine"]["h5"]
         hard = float(((sc5.double().abs() * l1.to(sc5.device) * (65504.0 / 2.0 ** st["exp"]["h4"]) + bi5.double().abs()).max()
                       + 65504.0 / 2.0 ** st["exp"]["h2"]).item())
-        st["exp"]["post"] = min(self._x3_exponent(hard), st["exp"]["h2"])
+        st["exp"]["post"] = min(x3_exponent(hard), st["exp"]["h2"])
         # the folded tail classifier(bn(conv6(post)) + v): a transposed layer to one channel whose per-voxel tap contraction is part
         # of conv5's epilogue (snvc_f16x3_deconv3d_tail_forward); `post` is never stored
         st["tail"] = st["tail_bias"] = None
@@ -211,7 +204,7 @@ class GlobalStack(nn.Module):
     def _x3_select(self, device, arithmetic=None):
         """The split-mode state if this call runs in split mode, else None."""
         mode = arithmetic or self.arithmetic
-        if mode == "fp32" or torch.is_grad_enabled() or self.training or self.__dict__.get("_snvc_x3_off"):
+        if mode == "fp32" or torch.is_grad_enabled() or self.training or self.split_off:
             if mode == "x3":
                 raise RuntimeError("arithmetic='x3' needs inference (no autograd, eval mode) and no earlier overflow")
             return None
@@ -220,36 +213,7 @@ class GlobalStack(nn.Module):
             if mode == "x3":
                 raise RuntimeError("arithmetic='x3': the stack does not qualify (32 channels, eval-mode BatchNorm3d everywhere)")
             return None
-        if st["guard"].event is not None and self._overflowed(st["guard"], mode, "an earlier call's result clamped it"):
-            return None                           # overflow_check = "deferred": the previous call's flag
-        return st
-
-    def _overflowed(self, guard, mode, what):
-        """Look at a posted flag (synchronous).  True: a value was clamped -- split mode is switched off for this model."""
-        if not guard.wait():
-            return False
-        return self._leave_split_mode(mode, what)
-
-    def _leave_split_mode(self, mode, what):
-        self.__dict__["_snvc_x3_off"] = True
-        msg = ("snvc_amd: split-mode (f16x3) overflow -- an activation exceeded |beta| + %g |gamma| of its BatchNorm; %s.  "
-               "This model now runs on the fp32-MFMA kernels (reset_split_mode() turns split mode back on)." % (self.X3_SIGMAS, what))
-        if mode == "x3":
-            raise RuntimeError("arithmetic='x3': " + msg)
-        warnings.warn(msg)
-        return True
-
-    def check_overflow(self) -> bool:
-        """With ``overflow_check = "deferred"``: wait for the last split-mode call's flag.  True if that call's result was
-        clamped (the model leaves split mode, as in the checked mode); always False in the default checked mode."""
-        hit = False
-        for guard in self.__dict__.get("_snvc_x3_guard", {}).values():
-            hit |= self._overflowed(guard, "auto", "the last result clamped it")
-        return hit
-
-    def reset_split_mode(self):
-        """Turn split mode back on after an overflow switched it off (e.g. after loading matching statistics)."""
-        self.__dict__.pop("_snvc_x3_off", None)
+        return st if self.split_guard(device, mode) is not None else None      # None: overflow_check = "deferred", the previous call's flag
 
     def _tail_x3(self, st, v1s, timing=None):
         """conv2 (+ side head) -> hourglass -> folded one-channel tail on a split-C8 first-layer result ``v1s`` (exponent
@@ -258,12 +222,10 @@ class GlobalStack(nn.Module):
         n, dev = v1s.size(0), v1s.device
         d, h, w = v1s.shape[3:6]
         hg = self.hg_conv3d
-        if timing is not None and "conv2" in timing:
-            timing["conv2"][0].record()
+        _mark(timing, "conv2", 0)
         v2s, hv = L["conv2"](v1s, E["v1"], *A["conv2"], flags=EPI_RELU, out_exp=E["conv2"], head=self.classifier.weight, overflow=flag,
                              out=self._buffer("v2s", (n, 2, 4, d, h, w, 8), dev, torch.float16))
-        if timing is not None and "conv2" in timing:
-            timing["conv2"][1].record()
+        _mark(timing, "conv2", 1)
         _ROUTES["side_head"] += 1
         o = L["h1"](v2s, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)                  # 1/2 res, 2C channels
         pre = L["h2"](o, E["h1"], *A["h2"], flags=EPI_RELU, out_exp=E["h2"], overflow=flag)                     # relu(bn(conv))   :153-156
@@ -297,24 +259,19 @@ class GlobalStack(nn.Module):
 
     def _gn_qualifies(self, device, arithmetic=None):
         """The overflow guard if this call can run a GroupNorm stack in split mode (see _gn_tail_x3), else None."""
-        from .submodule import X3_GROUP_NORM, overflow_guard
         mode = arithmetic or self.arithmetic
         norms = [m for m in self.modules() if isinstance(m, (nn.GroupNorm, nn.modules.batchnorm._BatchNorm))]
         if (not norms or not all(isinstance(m, nn.GroupNorm) for m in norms) or not X3_GROUP_NORM[0] or mode == "fp32"
-                or torch.is_grad_enabled() or self.training or self.__dict__.get("_snvc_x3_off") or device.type != "cuda"
+                or torch.is_grad_enabled() or self.training or self.split_off or device.type != "cuda"
                 or self.conv1[0][0].out_channels % 32 != 0):
             return None
-        guard = overflow_guard(self, device)
-        if guard.event is not None and self._overflowed(guard, mode, "an earlier call's result clamped it"):
-            return None
-        return guard
+        return self.split_guard(device, mode)
 
     def _gn_tail_x3(self, v1, timing=None, arithmetic=None):
         """A GroupNorm stack (``GlobalStack(gn=True)``) behind its fp32 first-layer result, in split mode (r5): nothing folds here
         (every norm needs its own conv result's statistics), so the layers run one by one through ``fused_conv3d_x3``'s GroupNorm
         form -- conv2, the hourglass, conv6 + cost0 -- and the 1x1x1 classifier on the fp32 kernel.  Returns None when the
         call does not qualify.  A flagged call raises SplitOverflow (``_checked`` redoes it in fp32)."""
-        from .submodule import SplitT, x3_exponent, x3_norm_bound, _Plan
         if isinstance(v1, SplitT):          # conv1 ran in split mode already (_forward_volume_unchecked): its guard is the caller's
             v1s, guard = v1, self.__dict__["_snvc_x3_guard"][v1.t.device]
         else:
@@ -324,15 +281,13 @@ class GlobalStack(nn.Module):
             if guard is None:
                 return None
             norm1 = self.conv1[0][1]
-            b1 = x3_norm_bound(norm1, self.conv1[0][0].__dict__.setdefault("_snvc_plans_x3", {}).setdefault(v1.device, _Plan()))
+            b1 = x3_norm_bound(norm1, plan_for(self.conv1[0][0], "_x3", v1.device))
             e1 = x3_exponent(b1)
             n, c = v1.size(0), v1.size(1)
             v1s = SplitT(ops.to_split(v1, e1, out=self._buffer("v1s", (n, 2, c // 8) + tuple(v1.shape[2:]) + (8,), v1.device, torch.float16)), e1, b1)
-        if timing is not None and "conv2" in timing:
-            timing["conv2"][0].record()
+        _mark(timing, "conv2", 0)
         v2 = self.conv2.fused_x3(v1s, flag=guard.flag)
-        if timing is not None and "conv2" in timing:
-            timing["conv2"][1].record()
+        _mark(timing, "conv2", 1)
         out, _, _ = self.hg_conv3d.forward_x3(v2, residual=v2, flag=guard.flag)
         guard.post()                      # nothing clamps behind this point
         cost = self.classifier(ops.from_split(out.t, out.exp))      # Conv3d(C, 1, k1): the fp32 kernel (the split one-channel form is k3)
@@ -357,7 +312,6 @@ class GlobalStack(nn.Module):
         G[u] = P_-1[u - 4] + P_0[u] + P_+1[u + 4], and G' (the last column: no kw = +1 taps) = P_-1[u - 4] + P_0[u].  One depth-1 3 x 3
         layer with 3 (kw) x 3 (depth class) x Cout output channels, folded in fp64 like sheared_kernels."""
         if "sheared4" not in plans:
-            from .submodule import SHEAR_CLASS_KDS
             w = wr.detach().double()                                        # [Cout, C, kd, kh, kw]
             cout, c = w.shape[0], w.shape[1]
             k = torch.zeros((3, 3, cout, c, 3, 3), dtype=torch.float64, device=w.device)      # [kw][cls][co][c][kh][1 - kd]
@@ -447,7 +401,6 @@ class GlobalStack(nn.Module):
         computes for a train-mode BatchNorm at batch 1 (snvc_sheared_expand_stats: the raw result is never stored).  Per sample:
         statistics, then the expand pass applies scale / shift + ReLU and writes the split pair the split-mode GroupNorm tail reads.
         Returns None when the call does not qualify (another spacing, rows the sheared kernels do not cover, split mode off)."""
-        from .submodule import SplitT, x3_exponent, x3_norm_bound
         conv, norm = self.conv1[0][0], self.conv1[0][1]
         guard = self._gn_qualifies(left.device, arithmetic)
         if guard is None:
@@ -466,7 +419,7 @@ class GlobalStack(nn.Module):
         off, wu, off_col, wu_col = sheared_geometry(q, m0, d, w)
         g = lay_g(ops.sheared_upsample(right, q, wu, off).unsqueeze(2)).squeeze(2)
         gcol = lay_col(ops.sheared_upsample(right, q, wu_col, off_col).unsqueeze(2)).squeeze(2)
-        b1 = x3_norm_bound(norm, conv.__dict__.setdefault("_snvc_plans_x3", {}).setdefault(left.device, _Plan()))
+        b1 = x3_norm_bound(norm, plan_for(conv, "_x3", left.device))
         e1 = x3_exponent(b1)
         v1s = self._buffer("v1s", (n, 2, c // 8, d, h, w, 8), left.device, torch.float16)
         gam = norm.weight.detach() if norm.weight is not None else None
@@ -495,11 +448,9 @@ class GlobalStack(nn.Module):
             self.__dict__["_snvc_last_v1"] = "v1"       # the fp32 first-layer result is in the workspace too
             return self._tail_x3(st, v1s, timing)
         self.__dict__["_snvc_last_v1"] = "v1"
-        if timing is not None and "conv2" in timing:
-            timing["conv2"][0].record()
+        _mark(timing, "conv2", 0)
         v, hv = self.conv2.fused(v1, out=self._buffer("v2", shape, v1.device), side_head=self.classifier)
-        if timing is not None and "conv2" in timing:
-            timing["conv2"][1].record()
+        _mark(timing, "conv2", 1)
         return self._tail(v, hv)
 
     def forward(self, volume):
@@ -514,18 +465,12 @@ class GlobalStack(nn.Module):
                     _lazy.CONSUMER.ref = weakref.ref(self)      # the next build_cost_volume starts this model's first-layer prep
                     pre = volume.take_prefetch(self)
                     if pre is not None:                         # build_cost_volume already ran the step up to its host sync
-                        try:
-                            try:
-                                while True:
-                                    next(pre)
-                            except StopIteration as done:
-                                _ROUTES["lazy_prefetch_resumed"] += 1
-                                return done.value
-                        except SplitOverflow:
-                            self._leave_split_mode(self.arithmetic, "this call was redone in fp32")
-                            _ROUTES["x3_overflow_redo"] += 1
-                            return self._forward_pair_unchecked(left, right, shift, ds, shift_checked=True, spacing=volume.spacing,
-                                                                arithmetic="fp32")
+                        def resume():
+                            cost = _run(pre)
+                            _ROUTES["lazy_prefetch_resumed"] += 1
+                            return cost
+                        return self.checked(self.arithmetic, resume, lambda: self._forward_pair_unchecked(
+                            left, right, shift, ds, shift_checked=True, spacing=volume.spacing, arithmetic="fp32"))
                     return self.forward_pair(left, right, shift, ds, shift_checked=True, spacing=volume.spacing)
             # built from these two features: its maximum is theirs (interpolation weights are in [0, 1]), if they are untouched
             # ... and the volume itself: one that was written to in place (vol.mul_(8)) no longer has their maximum
@@ -560,14 +505,9 @@ class GlobalStack(nn.Module):
         return gen
 
     def _checked(self, fn, arithmetic, *args, **kw):
-        """Run a split-mode capable entry point; a call whose overflow flag came back set is redone on the fp32-MFMA kernels
-        (its clamped result never leaves).  One extra step, once per model: split mode stays off afterwards."""
-        try:
-            return fn(*args, arithmetic=arithmetic, **kw)
-        except SplitOverflow:
-            self._leave_split_mode(arithmetic or self.arithmetic, "this call was redone in fp32")
-            _ROUTES["x3_overflow_redo"] += 1
-            return fn(*args, arithmetic="fp32", **kw)
+        """Run a split-mode capable entry point under ``SplitModePolicy.checked``: a flagged call is redone with arithmetic="fp32"."""
+        return self.checked(arithmetic or self.arithmetic, lambda: fn(*args, arithmetic=arithmetic, **kw),
+                            lambda: fn(*args, arithmetic="fp32", **kw))
 
     def _forward_volume(self, volume, timing=None, arithmetic=None, scale_from=None):
         return self._checked(self._forward_volume_unchecked, arithmetic, volume, timing=timing, scale_from=scale_from)
@@ -583,35 +523,27 @@ class GlobalStack(nn.Module):
         shape = (n, c2 // 2) + tuple(volume.shape[2:])
         gguard = self._gn_qualifies(volume.device, arithmetic) if (volume.dtype == torch.float32 and c2 % 16 == 0) else None
         if gguard is not None:      # GroupNorm stack (r5): the volume split once, conv1 and everything behind it in split mode
-            from .submodule import SplitT
             mul = ops.split_scale_for(*(scale_from if scale_from is not None else (volume,)))
             vs = ops.to_split(volume, mul_dev=mul, out=self._buffer("vol_s", (n, 2, c2 // 8) + tuple(volume.shape[2:]) + (8,), volume.device,
                                                                       torch.float16))
-            if timing is not None and "conv1" in timing:
-                timing["conv1"][0].record()
+            _mark(timing, "conv1", 0)
             v1s = self.conv1.fused_x3(SplitT(vs, 0, None, mul), flag=gguard.flag)
-            if timing is not None and "conv1" in timing:
-                timing["conv1"][1].record()
+            _mark(timing, "conv1", 1)
             return self._gn_tail_x3(v1s, timing, arithmetic)
         st = self._x3_select(volume.device, arithmetic) if (volume.dtype == torch.float32 and c2 % 16 == 0) else None
         if st is not None:
-            from .submodule import SplitT
             mul = ops.split_scale_for(*(scale_from if scale_from is not None else (volume,)))
             vs = ops.to_split(volume, mul_dev=mul, out=self._buffer("vol_s", (n, 2, c2 // 8) + tuple(volume.shape[2:]) + (8,), volume.device,
                                                                       torch.float16))
             v1s = self._buffer("v1s", (n, 2, c2 // 16) + tuple(volume.shape[2:]) + (8,), volume.device, torch.float16)
-            if timing is not None and "conv1" in timing:
-                timing["conv1"][0].record()
+            _mark(timing, "conv1", 0)
             self.conv1.fused_x3(SplitT(vs, 0, None, mul), out=v1s, out_exp=st["exp"]["v1"], flag=st["flag"])
-            if timing is not None and "conv1" in timing:
-                timing["conv1"][1].record()
+            _mark(timing, "conv1", 1)
             self.__dict__["_snvc_last_v1"] = "v1s"
             return self._tail_x3(st, v1s, timing)
-        if timing is not None and "conv1" in timing:
-            timing["conv1"][0].record()
+        _mark(timing, "conv1", 0)
         v = self.conv1.fused(volume, out=self._buffer("v1", shape, volume.device))
-        if timing is not None and "conv1" in timing:
-            timing["conv1"][1].record()
+        _mark(timing, "conv1", 1)
         return self._conv2_tail(v, shape, timing, arithmetic)
 
     @staticmethod
@@ -724,12 +656,7 @@ class GlobalStack(nn.Module):
 
     def _forward_pair_unchecked(self, *args, **kw):
         """``_forward_pair_steps`` run to its end."""
-        gen = self._forward_pair_steps(*args, **kw)
-        try:
-            while True:
-                next(gen)
-        except StopIteration as done:
-            return done.value
+        return _run(self._forward_pair_steps(*args, **kw))
 
     def _forward_pair_steps(self, left, right, shift, downsample=1, factored=True, timing=None, shift_checked=False, sheared=True,
                             fused_bn=True, spacing="unknown", commuted=True, arithmetic=None, pause=False):
@@ -761,10 +688,6 @@ class GlobalStack(nn.Module):
         ``timing``: optional dict ``{"volume": (start, end), "conv1": (start, end)}`` of events recorded on the
         current stream around the cost-volume launch and the first 3D convolution (the dominant kernel); used by
         bench.py for the roofline figures."""
-        def mark(name, which):
-            if timing is not None and name in timing:
-                timing[name][which].record()
-
         conv, bn = self.conv1[0][0], self.conv1[0][1]
         training_graph = torch.is_grad_enabled() and (left.requires_grad or right.requires_grad or conv.weight.requires_grad)
         if (training_graph and factored and timing is None and downsample == 1 and left.dtype == torch.float32
@@ -776,7 +699,7 @@ class GlobalStack(nn.Module):
                 assert nonneg
             else:
                 assert torch.all(shift >= 0.)
-            plan = conv.__dict__.setdefault("_snvc_plans", {}).setdefault(left.device, _Plan())
+            plan = plan_for(conv, "", left.device)
             if structure is not None and not self._sheared_fits(structure[0], structure[1], shift.size(1), left.size(3), True):
                 structure = None           # rows the sheared kernels do not cover (csrc/sheared_conv.hip's LDS limits): general path
             if (structure is not None and isinstance(bn, nn.BatchNorm3d) and bn.training and left.size(3) % 8 == 0
@@ -814,13 +737,13 @@ class GlobalStack(nn.Module):
                     return self.forward(vol)
                 return self._forward_volume(vol, None, arithmetic, scale_from=(left, right) if downsample == 1 else None)
             assert torch.all(shift >= 0.)        # the wrapper's own check (a sync) stays outside the event pair
-            mark("volume", 0)
+            _mark(timing, "volume", 0)
             vol = ops.cost_volume_forward(left, right, shift, downsample)
-            mark("volume", 1)
+            _mark(timing, "volume", 1)
             if torch.is_grad_enabled():
-                mark("conv1", 0)
+                _mark(timing, "conv1", 0)
                 v = self.conv1(vol)
-                mark("conv1", 1)
+                _mark(timing, "conv1", 1)
                 del vol
                 return self._tail(self.conv2(v))
             return self._forward_volume(vol, timing, arithmetic, scale_from=(left, right))
@@ -919,7 +842,7 @@ class GlobalStack(nn.Module):
         structure, guess, ready, ready_general = (spacing if known else None), None, None, None
         if ticket is not None:
             guess = plans.get("spacing_seen")    # (q, m0, D, W) of the previous call, or ("general", D, W): a guess, checked below
-            mark("volume", 0)
+            _mark(timing, "volume", 0)
             dims = (shift.size(1), left.size(3))
             if sheared and guess is not None and guess[0] != "general" and guess[2:] == dims:
                 ready = sheared_inputs(guess[0], guess[1])
@@ -946,11 +869,11 @@ class GlobalStack(nn.Module):
         if structure is not None:
             q, m0 = structure
             if ready is None or tuple(guess[:2]) != tuple(structure):
-                mark("volume", 0)
+                _mark(timing, "volume", 0)
                 ready = sheared_inputs(q, m0)    # first call, or the spacing changed: the guess is dropped
             g, gcol, off, off_col = ready
-            mark("volume", 1)
-            mark("conv1", 0)
+            _mark(timing, "volume", 1)
+            _mark(timing, "conv1", 0)
             st = self._x3_select(left.device, arithmetic)
             if st is not None and c % 8 == 0:
                 # split mode: the expand pass writes the (hi, lo) pair conv2 reads (same bytes as the fp32 tensor, no layout pass)
@@ -961,7 +884,7 @@ class GlobalStack(nn.Module):
                 except ops.Unsupported:
                     st = None
                 else:
-                    mark("conv1", 1)
+                    _mark(timing, "conv1", 1)
                     _ROUTES["sheared_first_conv"] += 1
                     self.__dict__["_snvc_last_v1"] = "v1s"
                     return self._tail_x3(st, v1s, timing)
@@ -971,18 +894,18 @@ class GlobalStack(nn.Module):
             except ops.Unsupported:              # a limit _sheared_fits does not mirror: same answer on the general paths
                 structure = None
             else:
-                mark("conv1", 1)
+                _mark(timing, "conv1", 1)
                 _ROUTES["sheared_first_conv"] += 1
                 return self._conv2_tail(v, shape, timing, arithmetic)
         if can_commute:
             # any other shift array: interpolation along w commutes with the convolution -- three 2D convolutions of the right
             # feature, three interpolations per output voxel, the warped volume is not built either (csrc/sheared_conv.hip)
             if ready_general is None:
-                mark("volume", 0)
+                _mark(timing, "volume", 0)
                 ready_general = commuted_inputs()
             p_, q_, e_ = ready_general
-            mark("volume", 1)
-            mark("conv1", 0)
+            _mark(timing, "volume", 1)
+            _mark(timing, "conv1", 0)
             st = self._x3_select(left.device, arithmetic)
             if st is not None and c % 8 == 0:       # split mode: the expand pass writes the (hi, lo) pair conv2 reads
                 v1s = self._buffer("v1s", (shape[0], 2, c // 8) + tuple(shape[2:]) + (8,), left.device, torch.float16)
@@ -992,7 +915,7 @@ class GlobalStack(nn.Module):
                 except ops.Unsupported:
                     pass
                 else:
-                    mark("conv1", 1)
+                    _mark(timing, "conv1", 1)
                     _ROUTES["commuted_first_conv"] += 1
                     self.__dict__["_snvc_last_v1"] = "v1s"
                     return self._tail_x3(st, v1s, timing)
@@ -1002,16 +925,16 @@ class GlobalStack(nn.Module):
             except ops.Unsupported:              # rows that do not fit the LDS (grows with D): build the right half instead
                 pass
             else:
-                mark("conv1", 1)
+                _mark(timing, "conv1", 1)
                 _ROUTES["commuted_first_conv"] += 1
                 return self._conv2_tail(v, shape, timing, arithmetic)
-        mark("volume", 0)
+        _mark(timing, "volume", 0)
         try:
             vol_r = ops.cost_volume_forward_right(right, shift, out=self._buffer("vol_r", shape, left.device))   # [N,C,D,H,W]
         except ops.Unsupported:                  # rows beyond the row builder's width: the materialised volume, as the reference
             return self.forward_pair(left, right, shift, downsample, factored=False, timing=timing, arithmetic=arithmetic)
-        mark("volume", 1)
-        mark("conv1", 0)
+        _mark(timing, "volume", 1)
+        _mark(timing, "conv1", 0)
         v = plans["right"](vol_r, scale, bias, None, ops.EPI_RELU, self._buffer("v1", shape, left.device), depth_planes=planes)
-        mark("conv1", 1)
+        _mark(timing, "conv1", 1)
         return self._conv2_tail(v, shape, timing, arithmetic)

@@ -32,6 +32,8 @@ import torch.nn.functional as F
 from .. import _dsgn, ops
 from .._derived import derived, fresh, invalidate_all, stamp
 from ..ops import EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID
+from .split_mode import (X3_GROUP_NORM, X3_SIGMAS, OverflowGuard, SplitModePolicy, SplitOverflow, SplitT,  # noqa: F401  (re-exported)
+                         overflow_guard, x3_exponent, x3_norm_bound, x3_ok)
 
 
 def _first_arg(k):
@@ -48,7 +50,6 @@ def _cubic(v, what):
 
 # How often each fused route was taken (tests assert on it: a silent regression to a slower or to a torch route shows)
 import collections
-import math
 _ROUTES = collections.Counter()
 TRAIN_EXACT_K57 = [False]     # True: k5 / k7 layers under autograd on the direct kernels (exact fp32 FMA chains) instead of Winograd
 
@@ -73,14 +74,27 @@ def invalidate_plans(module: Optional[nn.Module] = None) -> None:
 # Every per-module cache this package hangs on a module's __dict__ (packed weights, folded norms, the factored first
 # convolution's split weights for inference and training, the persistent inference workspace, the device copy of the
 # coordinate maps).  invalidate_plans() drops exactly these; tests/test_host_cpu.py checks that no other `_snvc_*`
-# name is written anywhere in the package.
-CACHE_ATTRS = ("_snvc_plans", "_snvc_plans_f16", "_snvc_plans_x3", "_snvc_plans2d", "_snvc_plans2d_t", "_snvc_factored", "_snvc_factored_train", "_snvc_ws",
-               "_snvc_coor_maps", "_snvc_x3", "_snvc_x3_off", "_snvc_x3_guard", "_snvc_last_v1", "_snvc_streams", "_snvc_lazy_warned", "_snvc_prep_ws", "_snvc_prep_epoch")
+# name is written anywhere in the package.  The ONE declaration: name -> what it is.  "scratch": device buffers, streams and
+# events that copy.deepcopy / pickle must not carry (rebuilt on first use); "workspace": scratch that release_workspace() gives back.
+_ATTRS = {"_snvc_plans": "plans", "_snvc_plans_f16": "plans", "_snvc_plans_x3": "plans", "_snvc_plans2d": "plans", "_snvc_plans2d_t": "plans",
+          "_snvc_factored": "cache", "_snvc_factored_train": "cache", "_snvc_ws": "workspace", "_snvc_coor_maps": "cache", "_snvc_x3": "scratch",
+          "_snvc_x3_off": "state", "_snvc_x3_guard": "scratch", "_snvc_last_v1": "state", "_snvc_streams": "scratch", "_snvc_lazy_warned": "state",
+          "_snvc_prep_ws": "workspace", "_snvc_prep_epoch": "state"}
+CACHE_ATTRS = tuple(_ATTRS)
+WORKSPACE_ATTRS = tuple(k for k, v in _ATTRS.items() if v == "workspace")
+SCRATCH_ATTRS = tuple(k for k, v in _ATTRS.items() if v in ("workspace", "scratch"))
+_PLAN_ATTR = {k[len("_snvc_plans"):]: k for k, v in _ATTRS.items() if v == "plans"}      # plan_for's kinds: "", "_f16", "_x3", "2d", "2d_t"
 
 
 class _Plan(dict):
     """The values derived from one conv(+norm) pair's parameters (packed weights, folded affine, ...): a store for
     ``_derived.derived``, each entry rebuilt when its sources change."""
+
+
+def plan_for(module: nn.Module, kind: str, device) -> _Plan:
+    """The module's plan of one kind -- "" (fp32), "_f16", "_x3", "2d", "2d_t" -- for ``device``: one per device (replicas made by
+    nn.DataParallel share __dict__ entries)."""
+    return module.__dict__.setdefault(_PLAN_ATTR[kind], {}).setdefault(device, _Plan())
 
 
 def _conv_geometry(conv: nn.Module):
@@ -949,8 +963,8 @@ def fused_conv3d(conv: nn.Module, norm: Optional[nn.Module], x: torch.Tensor, *,
     layer's epilogue and the C-channel tensor is never written (``snvc_conv3d_forward_head``); otherwise the two
     layers run one after the other.  Returns ``head(result)``.
     """
-    if plan is None:  # one plan per device (replicas made by nn.DataParallel share __dict__ entries)
-        plan = conv.__dict__.setdefault("_snvc_plans", {}).setdefault(x.device, _Plan())
+    if plan is None:
+        plan = plan_for(conv, "", x.device)
     if conv.weight.device != x.device:
         raise RuntimeError(f"conv3d weight is on {conv.weight.device} but the input is on {x.device}")
     flags = (EPI_RELU if relu else 0) | (EPI_SIGMOID if sigmoid else 0)
@@ -1005,7 +1019,7 @@ def fused_conv3d_avgpool_d4(conv: nn.Module, norm: Optional[nn.Module], x: torch
     (``SNVC_EPI_AVGPOOL_D4``: the full-resolution tensor is never written); otherwise the layer and the pool run one
     after the other."""
     if not torch.is_grad_enabled() and x.is_cuda and _is_frozen_norm(norm):
-        plan = conv.__dict__.setdefault("_snvc_plans", {}).setdefault(x.device, _Plan())
+        plan = plan_for(conv, "", x.device)
         layer = _get_layer(conv, plan)
         scale, bias = _folded_bn(norm, plan) if norm is not None else (None, None)
         y = ops.conv3d_forward_avgpool_d4(layer, x, scale, bias, EPI_RELU if relu else 0)
@@ -1033,7 +1047,7 @@ def fused_conv3d_f16(conv: nn.Module, norm: Optional[nn.Module], x: torch.Tensor
         raise NotImplementedError("the fp16-storage mode needs eval-mode BatchNorm3d (GroupNorm / batch statistics: fp32 path)")
     if conv.weight.device != x.device:
         raise RuntimeError(f"conv3d weight is on {conv.weight.device} but the input is on {x.device}")
-    plan = conv.__dict__.setdefault("_snvc_plans_f16", {}).setdefault(x.device, _Plan())
+    plan = plan_for(conv, "_f16", x.device)
     layer = _get_layer(conv, plan, ops.Conv3dLayerF16)
     scale, bias = _folded_bn(norm, plan) if norm is not None else (None, None)
     flags = (EPI_RELU if relu else 0) | (EPI_SIGMOID if sigmoid else 0)
@@ -1042,108 +1056,8 @@ def fused_conv3d_f16(conv: nn.Module, norm: Optional[nn.Module], x: torch.Tensor
     return layer(x, scale, bias, residual, flags, out)
 
 
-# ------------------------------------------------------------------------------------------
-# split mode ("f16x3", r4): inference with frozen statistics on the snvc_f16x3_* kernels -- the fp32 layers at fp32 accuracy on
-# the half-precision matrix pipe (csrc/conv3d_f16.hip, F16Cfg::PL).  A tensor travels as SplitT: the (hi, lo) pair,
-# the power of two its values are stored times (an int exponent, or a one-element device tensor when the range is only known
-# from the data), and the bound |value| is promised to stay below (None for data-scaled tensors: they cannot overflow).
-# ------------------------------------------------------------------------------------------
-X3_SIGMAS = 64.0     # a BatchNorm output is promised to stay below |beta| + X3_SIGMAS * |gamma|
-
-
-class SplitT:
-    __slots__ = ("t", "exp", "mul_dev", "bound")
-
-    def __init__(self, t, exp=0, bound=None, mul_dev=None):
-        self.t, self.exp, self.bound, self.mul_dev = t, exp, bound, mul_dev
-
-    def slice_groups(self, lo: int, hi: int):
-        """Channel groups [lo, hi) of the pair (a view: split tensors are [N, 2, C/8, D, H, W, 8])."""
-        return SplitT(self.t[:, :, lo:hi], self.exp, self.bound, self.mul_dev)
-
-
-class SplitOverflow(RuntimeError):
-    """Raised INSIDE a split-mode call whose overflow flag came back set: the call's result (an activation clamped to half's
-    range) is dropped and the model's public entry point redoes the call on the fp32-MFMA kernels.  Never reaches the caller
-    unless split mode was demanded (arithmetic / precision = "x3")."""
-
-
-class OverflowGuard:
-    """The overflow flag of a model's split-mode calls: an int32 on the device that every clamping epilogue ORs into, its pinned
-    host copy and the event behind the copy.
-
-    ``post()`` is queued right after the LAST layer that can clamp (the layers behind it write float32); ``wait()`` is called
-    once the rest of the call has been queued: the host then waits for the flag while the GPU still has those last layers to
-    run, so the check costs no GPU idle time and the result never leaves the call unchecked (r4 looked at the flag one call
-    late).  ``check="deferred"`` models post without waiting; ``pending()`` is the synchronous look a caller can take then."""
-
-    def __init__(self, device):
-        self.flag = torch.zeros(1, dtype=torch.int32, device=device)
-        self.host = torch.zeros(1, dtype=torch.int32).pin_memory()
-        self.event = None
-
-    def post(self):
-        self.host.copy_(self.flag, non_blocking=True)
-        self.event = torch.cuda.Event()
-        self.event.record()
-
-    def wait(self) -> bool:
-        """True if a value was clamped since the last look (the device flag is cleared again then)."""
-        ev, self.event = self.event, None
-        if ev is None:
-            return False
-        ops.spin_wait(ev)
-        if int(self.host.item()) == 0:
-            return False
-        self.flag.zero_()
-        return True
-
-    pending = wait
-
-
-def overflow_guard(module, device) -> OverflowGuard:
-    """The module's guard for ``device`` (kept across rebuilds of the packed split-mode state: a pending flag is never dropped)."""
-    guards = module.__dict__.setdefault("_snvc_x3_guard", {})
-    g = guards.get(device)
-    if g is None:
-        g = guards[device] = OverflowGuard(device)
-    return g
-
-
-def x3_exponent(bound: float) -> int:
-    """e with bound * 2^e <= 2^15 (half overflows at 65504; a value beyond the bound is clamped and FLAGGED)."""
-    if not (bound > 0.0) or not math.isfinite(bound):
-        return 0
-    return max(-14, min(14, 15 - math.frexp(bound)[1]))
-
-
-def x3_norm_bound(norm, plan) -> float:
-    """|beta| + X3_SIGMAS * |gamma| of a frozen BatchNorm3d, maximised over channels (cached with the folded affine); of a
-    GroupNorm likewise (its result is gamma * xhat + beta with xhat normalised per sample and group)."""
-    w, b = norm.weight, norm.bias
-
-    def build():
-        g = w.detach().abs() if w is not None else torch.ones(1)
-        bb = b.detach().abs().to(g.device) if b is not None else torch.zeros(1, device=g.device)
-        return float((bb + X3_SIGMAS * g).max().item())
-    return derived(plan, "x3_bound", (w, b), build)
-
-
-def x3_ok(*modules, group_norm: bool = True) -> bool:
-    """Every norm a frozen BatchNorm3d (eval mode, running statistics) or -- r5, ``group_norm`` -- a GroupNorm (its statistics are
-    taken from the layer's fp32 result, see fused_conv3d_x3); nothing to differentiate."""
-    if torch.is_grad_enabled():
-        return False
-    for m in modules:
-        for n in m.modules():
-            if isinstance(n, nn.GroupNorm) and not (group_norm and X3_GROUP_NORM[0]):
-                return False
-            if isinstance(n, nn.modules.batchnorm._BatchNorm) and (n.training or n.running_mean is None):
-                return False
-    return True
-
-
-X3_GROUP_NORM = [True]      # False: GroupNorm models stay on the fp32-MFMA kernels (r4's behaviour; kept for measuring)
+# split mode: the tensor tag, the exponent rule, the overflow flag and the overflow policy are models/split_mode.py (re-exported
+# at the top of this module); below, the layers
 
 
 def fused_conv3d_x3(conv: nn.Module, norm: Optional[nn.Module], x: SplitT, *, relu=False, sigmoid=False, residual: Optional[SplitT] = None,
@@ -1151,7 +1065,7 @@ def fused_conv3d_x3(conv: nn.Module, norm: Optional[nn.Module], x: SplitT, *, re
     """``fused_conv3d`` in split mode: returns a SplitT (or, ``to_f32`` / a one-channel layer, a float32 tensor).  The result's
     exponent is ``out_exp`` if given (a slice of a larger pair must share the pair's), else chosen from the bound
     |beta| + X3_SIGMAS |gamma| (+ the residual's bound)."""
-    plan = conv.__dict__.setdefault("_snvc_plans_x3", {}).setdefault(x.t.device, _Plan())
+    plan = plan_for(conv, "_x3", x.t.device)
     layer = _get_layer(conv, plan, ops.Conv3dLayerX3)
     scale = bias = None
     bound = None
@@ -1211,37 +1125,37 @@ def _fused_conv3d_x3_gn(plan, layer, norm, x: SplitT, relu, sigmoid, residual, r
     return SplitT(y, e, bound)
 
 
-class ConvBN3d(nn.Sequential):
+class _Fused3d:
+    """``fused`` / ``fused_f16`` / ``fused_x3``: one layer on the fp32, the fp16-storage and the split-mode kernels.  A class says
+    which (conv, norm) pair it is (``_conv_norm``) and which keywords it adds (``_fused_kw``)."""
+    _fused_kw = {}
+
+    def forward(self, x):
+        return self.fused(x)
+
+    def fused(self, x, **kw):
+        return fused_conv3d(*self._conv_norm(), x, **{**self._fused_kw, **kw})
+
+    def fused_f16(self, x, **kw):
+        return fused_conv3d_f16(*self._conv_norm(), x, **{**self._fused_kw, **kw})
+
+    def fused_x3(self, x, **kw):
+        return fused_conv3d_x3(*self._conv_norm(), x, **{**self._fused_kw, **kw})
+
+
+class ConvBN3d(_Fused3d, nn.Sequential):
     """``Sequential(Conv3d | ConvTranspose3d, BatchNorm3d | GroupNorm)`` -- the object convbn_3d
     returns in the reference (keys ``0.weight``, ``1.weight``, ``1.bias``, ``1.running_mean``, ...)."""
 
-    def forward(self, x):
-        return self.fused(x)
-
-    def fused(self, x, **kw):
-        return fused_conv3d(self[0], self[1], x, **kw)
-
-    def fused_f16(self, x, **kw):
-        return fused_conv3d_f16(self[0], self[1], x, **kw)
-
-    def fused_x3(self, x, **kw):
-        return fused_conv3d_x3(self[0], self[1], x, **kw)
+    def _conv_norm(self):
+        return self[0], self[1]
 
 
-class HipConv3d(nn.Conv3d):
+class HipConv3d(_Fused3d, nn.Conv3d):
     """A bare nn.Conv3d(bias=False) (classifier, fg_cls_head[2], part_reg_head[2]) on the HIP kernel."""
 
-    def forward(self, x):
-        return self.fused(x)
-
-    def fused(self, x, **kw):
-        return fused_conv3d(self, None, x, **kw)
-
-    def fused_f16(self, x, **kw):
-        return fused_conv3d_f16(self, None, x, **kw)
-
-    def fused_x3(self, x, **kw):
-        return fused_conv3d_x3(self, None, x, **kw)
+    def _conv_norm(self):
+        return self, None
 
 
 def convbn_3d(in_planes, out_planes, kernel_size, stride, pad, dilation=1, gn=False, groups=32):
@@ -1256,23 +1170,12 @@ def _deconvbn_3d(cin, cout, gn):
                     nn.BatchNorm3d(cout) if not gn else nn.GroupNorm(32, cout))
 
 
-class ConvBNReLU3d(nn.Sequential):
+class ConvBNReLU3d(_Fused3d, nn.Sequential):
     """``Sequential(convbn_3d(...), ReLU(inplace=True))``: the ReLU is folded into the conv epilogue."""
+    _fused_kw = {"relu": True}
 
-    def forward(self, x):
-        return self[0].fused(x, relu=True)
-
-    def fused(self, x, **kw):
-        kw.setdefault("relu", True)
-        return self[0].fused(x, **kw)
-
-    def fused_f16(self, x, **kw):
-        kw.setdefault("relu", True)
-        return self[0].fused_f16(x, **kw)
-
-    def fused_x3(self, x, **kw):
-        kw.setdefault("relu", True)
-        return self[0].fused_x3(x, **kw)
+    def _conv_norm(self):
+        return self[0]._conv_norm()
 
 
 class disparityregression(nn.Module):
@@ -1320,23 +1223,21 @@ class hourglass(nn.Module):
         o = self.conv6.fused(post, residual=residual, out=out, head=head, head_residual=head_residual)   # :166
         return o, pre, post
 
+    def _graph(self, f, x, presqu, postsqu, residual, **last):
+        """The inference graph over ``f(layer, x, **kw)``, the layer call of one arithmetic."""
+        o = f(self.conv1, x)
+        pre = f(self.conv2, o, relu=True, residual=postsqu)
+        o = f(self.conv4, f(self.conv3, pre))
+        post = f(self.conv5, o, relu=True, residual=presqu if presqu is not None else pre)
+        return f(self.conv6, post, residual=residual, **last), pre, post
+
     def forward_x3(self, x, residual=None, out=None, out_exp=None, flag=None):
         """The same graph in split mode (SplitT in / out; presqu / postsqu = None as the callers on the path use it)."""
-        o = self.conv1.fused_x3(x, flag=flag)
-        pre = self.conv2.fused_x3(o, relu=True, flag=flag)
-        o = self.conv4.fused_x3(self.conv3.fused_x3(pre, flag=flag), flag=flag)
-        post = self.conv5.fused_x3(o, relu=True, residual=pre, flag=flag)
-        o = self.conv6.fused_x3(post, residual=residual, out=out, out_exp=out_exp, flag=flag)
-        return o, pre, post
+        return self._graph(lambda seq, t, **kw: seq.fused_x3(t, flag=flag, **kw), x, None, None, residual, out=out, out_exp=out_exp)
 
     def forward_f16(self, x, presqu=None, postsqu=None, residual=None, out=None):
         """The same graph on C8 half tensors (fp16-storage mode)."""
-        o = self.conv1.fused_f16(x)
-        pre = self.conv2.fused_f16(o, relu=True, residual=postsqu)
-        o = self.conv4.fused_f16(self.conv3.fused_f16(pre))
-        post = self.conv5.fused_f16(o, relu=True, residual=presqu if presqu is not None else pre)
-        o = self.conv6.fused_f16(post, residual=residual, out=out)
-        return o, pre, post
+        return self._graph(lambda seq, t, **kw: seq.fused_f16(t, **kw), x, presqu, postsqu, residual, out=out)
 
 
 def get_hg_down_sample(channel_in, channel_out, gn, downsample=True):
@@ -1369,38 +1270,27 @@ class hourglass_downsample_16(nn.Module):
         self.conv11 = get_hg_up_sample(c * 2, c * 2, gn)
         self.conv12 = get_hg_up_sample(c * 2, c, gn)
 
-    def forward(self, x, residual=None, out=None):
-        o2 = self.conv2(self.conv1(x))
-        o4 = self.conv4(self.conv3(o2))
-        o6 = self.conv6(self.conv5(o4))
-        o8 = self.conv8(self.conv7(o6))
-        i10 = self.conv9.fused(o8, residual=o6)     # out_conv9 + out_conv6   :258-259
-        i11 = self.conv10.fused(i10, residual=o4)   # out_conv10 + out_conv4  :261-262
-        i12 = self.conv11.fused(i11, residual=o2)   # out_conv11 + out_conv2  :264-266
-        return self.conv12.fused(i12, residual=residual, out=out)
-
-    def forward_x3(self, x, residual=None, out=None, out_exp=None, flag=None):
-        """The same graph in split mode (SplitT in / out)."""
-        f = lambda seq, t, **kw: seq.fused_x3(t, flag=flag, **kw)                              # noqa: E731
+    def _graph(self, f, x, residual, **last):
+        """The graph over ``f(layer, x, **kw)``, the layer call of one arithmetic."""
         o2 = f(self.conv2, f(self.conv1, x))
         o4 = f(self.conv4, f(self.conv3, o2))
         o6 = f(self.conv6, f(self.conv5, o4))
         o8 = f(self.conv8, f(self.conv7, o6))
-        i10 = f(self.conv9, o8, residual=o6)
-        i11 = f(self.conv10, i10, residual=o4)
-        i12 = f(self.conv11, i11, residual=o2)
-        return f(self.conv12, i12, residual=residual, out=out, out_exp=out_exp)
+        i10 = f(self.conv9, o8, residual=o6)        # out_conv9 + out_conv6   :258-259
+        i11 = f(self.conv10, i10, residual=o4)      # out_conv10 + out_conv4  :261-262
+        i12 = f(self.conv11, i11, residual=o2)      # out_conv11 + out_conv2  :264-266
+        return f(self.conv12, i12, residual=residual, **last)
+
+    def forward(self, x, residual=None, out=None):
+        return self._graph(lambda seq, t, **kw: seq.fused(t, **kw), x, residual, out=out)
+
+    def forward_x3(self, x, residual=None, out=None, out_exp=None, flag=None):
+        """The same graph in split mode (SplitT in / out)."""
+        return self._graph(lambda seq, t, **kw: seq.fused_x3(t, flag=flag, **kw), x, residual, out=out, out_exp=out_exp)
 
     def forward_f16(self, x, residual=None, out=None):
         """The same graph on C8 half tensors (fp16-storage mode)."""
-        o2 = self.conv2.fused_f16(self.conv1.fused_f16(x))
-        o4 = self.conv4.fused_f16(self.conv3.fused_f16(o2))
-        o6 = self.conv6.fused_f16(self.conv5.fused_f16(o4))
-        o8 = self.conv8.fused_f16(self.conv7.fused_f16(o6))
-        i10 = self.conv9.fused_f16(o8, residual=o6)
-        i11 = self.conv10.fused_f16(i10, residual=o4)
-        i12 = self.conv11.fused_f16(i11, residual=o2)
-        return self.conv12.fused_f16(i12, residual=residual, out=out)
+        return self._graph(lambda seq, t, **kw: seq.fused_f16(t, **kw), x, residual, out=out)
 
 
 # ------------------------------------------------------------------------------------------
@@ -1527,10 +1417,6 @@ def _conv2d_train(conv, norm, x5, res5, flags, plan, kind, layer):
     return _Conv2dNormActFn.apply(x5, conv.weight, conv.bias, gamma, beta, res5, conv, norm, flags, plan, kind, layer)
 
 
-def _plan2d(conv: nn.Module, device) -> _Plan:
-    return conv.__dict__.setdefault("_snvc_plans2d", {}).setdefault(device, _Plan())
-
-
 def _affine2d(conv, norm, plan: _Plan):
     """(scale, bias) of the epilogue: folded eval BatchNorm2d and / or the conv's own bias."""
     scale = bias = None
@@ -1554,7 +1440,7 @@ def fused_conv2d(conv: nn.Conv2d, norm, x: torch.Tensor, *, relu=False, sigmoid=
     copy that ``permute(0, 1, 3, 2).contiguous()`` would make of the C-channel input is not made (vernier.py:441-442).
     A Conv2d(k3, stride 1, dilation 2, padding 2) (layer4 of the DSGN backbone) runs on the direct depth-1 form, for inference
     only.  ``out``: an [N,Cout,H,W] channel slice of a wider buffer to write the result into (inference only)."""
-    plan = _plan2d(conv, x.device)
+    plan = plan_for(conv, "2d", x.device)
     w = conv.weight
     kh, kw = conv.kernel_size
     whole = (kh, kw) == tuple(x.shape[2:]) and tuple(conv.padding) == (0, 0) and (kh, kw) != (1, 1)
@@ -1562,7 +1448,7 @@ def fused_conv2d(conv: nn.Conv2d, norm, x: torch.Tensor, *, relu=False, sigmoid=
         if whole or kh != kw or residual is not None or isinstance(norm, nn.GroupNorm) or _train2d(x, conv, norm, residual):
             return fused_conv2d(conv, norm, x.transpose(2, 3).contiguous(), relu=relu, sigmoid=sigmoid, residual=residual,
                                 residual_after_act=residual_after_act)
-        plan = conv.__dict__.setdefault("_snvc_plans2d_t", {}).setdefault(x.device, _Plan())
+        plan = plan_for(conv, "2d_t", x.device)
 
     dilated = tuple(conv.dilation) != (1, 1)
 
@@ -1617,7 +1503,7 @@ def fused_deconv2d(conv: nn.ConvTranspose2d, norm, x: torch.Tensor, *, relu=Fals
     if (tuple(conv.kernel_size), tuple(conv.stride), tuple(conv.padding), tuple(conv.output_padding)) != ((3, 3), (2, 2), (1, 1), (1, 1)) \
             or conv.groups != 1 or conv.bias is not None:
         raise NotImplementedError("the 2D neck's up-sampling layers are ConvTranspose2d(k3,s2,p1,op1,bias=False)")
-    plan = _plan2d(conv, x.device)
+    plan = plan_for(conv, "2d", x.device)
     layer = derived(plan, "layer", (conv.weight,), lambda: ops.Conv3dLayer(conv.weight.detach().contiguous(), 3, 2, 1, 1, True, planar=True))
     flags = (EPI_RELU if relu else 0) | (EPI_ADD_PRE if residual is not None else 0)
     r5 = residual.unsqueeze(2) if residual is not None else None

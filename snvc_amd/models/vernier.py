@@ -22,8 +22,9 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .submodule import (BasicBlock2d, ConvBNReLU3d, HipConv3d, basicdownsample, convbn, convbn_3d, hourglass,
-                        hourglass2d, hourglass2d_downsample_16, hourglass_downsample_16)
+from .submodule import (_ROUTES, BasicBlock2d, ConvBNReLU3d, HipConv3d, SplitModePolicy, SplitOverflow, SplitT, basicdownsample, convbn,
+                        convbn_3d, hourglass, hourglass2d, hourglass2d_downsample_16, hourglass_downsample_16, plan_for, x3_exponent,
+                        x3_norm_bound, x3_ok)
 
 
 class _VoxelGatherFn(torch.autograd.Function):
@@ -56,7 +57,7 @@ def get_feat_extraction(cfg, is_train=False, **kwargs):
     raise NotImplementedError(f"feature extractor {name!r}: hrnet-w32, hrnet-w48 and identity are available")
 
 
-class VernierScale(nn.Module):
+class VernierScale(SplitModePolicy, nn.Module):
     def __init__(self, cfg, is_train=False, feat_net=None):
         super().__init__()
         self.cfg = cfg
@@ -161,13 +162,13 @@ class VernierScale(nn.Module):
     # precision: "auto" (default: the 3D trunk in split mode at inference when it qualifies), "f32" (fp32-MFMA kernels only),
     # "x3" (split mode or an error), "f16" (the fp16-STORAGE mode of BASELINE configs[4]: forward() gathers into C8 halves)
     precision = "auto"
+    _split_attr, _split_where, _check_raises = "precision", " in the local trunk", True      # SplitModePolicy's texts for this model
 
     def construct_voxel_x3(self, left, right, grid_proj_left, grid_proj_right):
         """``construct_voxel`` written directly as the split C8 pair the split-mode trunk starts from (r4): the scale comes from
         the two feature maps' own maximum (a bilinear sample is a convex combination of feature values), so the fp32 voxel tensor,
         the pass that looked for its maximum and the layout pass are gone -- same bits as ``to_split(construct_voxel(...))`` with
         that scale.  Returns a ``SplitT``, or None when this call does not run in split mode (``trunk_3d`` decides the same way)."""
-        from .submodule import SplitT
         nh, nw, nl = self.cfg.n_sample_h, self.cfg.n_sample_w, self.cfg.n_sample_l
         if (torch.is_grad_enabled() or not left.is_cuda or left.dtype != torch.float32 or grid_proj_left.size(2) != nh * nw * nl
                 or self._x3_local(None, left.device, 2 * left.size(1)) is None):
@@ -184,12 +185,11 @@ class VernierScale(nn.Module):
         mode, else None: inference only, every norm a frozen BatchNorm3d or (r5) a GroupNorm, channels a multiple of 32, no part_reg_head.
         ``voxel``: the fp32 gather result, an already split ``SplitT`` (``construct_voxel_x3``), or None with ``device`` /
         ``channels`` given (the question asked before the gather runs)."""
-        from .submodule import SplitT, x3_ok
         mode = getattr(self, "precision", "auto")
         want = mode == "x3"
         if mode in ("f32", "f16"):
             return None
-        if self.__dict__.get("_snvc_x3_off"):
+        if self.split_off:
             if want:
                 raise RuntimeError("precision='x3': split mode was switched off by an earlier overflow (reset_split_mode())")
             return None
@@ -207,49 +207,13 @@ class VernierScale(nn.Module):
             if want:
                 raise RuntimeError("precision='x3': the trunk does not qualify (inference, eval-mode BatchNorm3d or GroupNorm, 2F % 64 == 0)")
             return None
-        from .submodule import overflow_guard
-        guard = overflow_guard(self, device)
-        if guard.event is not None and self._x3_overflowed(guard, "an earlier call's result clamped it"):
-            return None                               # overflow_check = "deferred": the previous call's flag
-        return guard
-
-    # "call" (default, r5): the overflow flag is read before the trunk's results leave the call, and a flagged call is redone on
-    # the fp32-MFMA kernels; "deferred": the flag is only posted (check_overflow() or the next call looks) -- see GlobalStack
-    overflow_check = "call"
-
-    def _x3_overflowed(self, guard, what):
-        if not guard.wait():
-            return False
-        return self._leave_split_mode(what)
-
-    def _leave_split_mode(self, what):
-        import warnings
-        from .submodule import X3_SIGMAS
-        self.__dict__["_snvc_x3_off"] = True
-        msg = ("snvc_amd: split-mode (f16x3) overflow in the local trunk -- an activation exceeded |beta| + %g |gamma| of its "
-               "BatchNorm; %s.  This model now runs on the fp32-MFMA kernels (reset_split_mode() turns split mode back on)."
-               % (X3_SIGMAS, what))
-        if getattr(self, "precision", "auto") == "x3":
-            raise RuntimeError("precision='x3': " + msg)
-        warnings.warn(msg)
-        return True
-
-    def check_overflow(self) -> bool:
-        """With ``overflow_check = "deferred"``: wait for the last split-mode call's flag; True if its result was clamped."""
-        hit = False
-        for guard in self.__dict__.get("_snvc_x3_guard", {}).values():
-            hit |= self._x3_overflowed(guard, "the last result clamped it")
-        return hit
-
-    def reset_split_mode(self):
-        self.__dict__.pop("_snvc_x3_off", None)
+        return self.split_guard(device, mode)         # None: overflow_check = "deferred", the previous call's flag
 
     def trunk_3d_x3(self, voxel, st):
         """``trunk_3d`` (reference vernier.py:415-438) in split mode: the same fp32 layers, every product three
         half-precision MFMAs on (hi, lo) pairs with fp32 accumulation.  ``voxel`` is the fp32 gather result; it is scaled by a
         power of two derived from its own maximum on the device (no host round trip) and split once; every later tensor's
         exponent comes from its folded BatchNorm.  Returns the same float32 tensors as ``trunk_3d``."""
-        from .submodule import SplitT, x3_exponent, x3_norm_bound, _Plan
         guard, flag = st, st.flag
         if isinstance(voxel, SplitT):            # construct_voxel_x3: the gather wrote the pair itself
             vs = voxel
@@ -263,7 +227,7 @@ class VernierScale(nn.Module):
 
         def nb(seq):        # the bound of a ConvBN3d's result
             conv, norm = seq[0], seq[1]
-            return x3_norm_bound(norm, conv.__dict__.setdefault("_snvc_plans_x3", {}).setdefault(voxel.device, _Plan()))
+            return x3_norm_bound(norm, plan_for(conv, "_x3", voxel.device))
         # the two halves of the concat of :433 share one exponent: both bounds are known from the parameters alone
         b_v3 = nb(self.conv1[0]) + nb(self.conv2[0]) + nb(self.conv3[0])
         last = self.hg_conv3d.conv6 if self.small else self.hg_conv3d.conv12
@@ -284,7 +248,6 @@ class VernierScale(nn.Module):
         ops.mul_broadcast_split(img.t, occ, out=cat[:, :, g:])                   # cat([v, img * occ])  :433
         v = self.conv4.fused_x3(SplitT(cat, e_cat, max(vh.bound, img.bound)), to_f32=True)      # :435, float32 NCDHW
         v = ops.avgpool_depth4(v)                                                # :436
-        from .submodule import _ROUTES, SplitOverflow
         if self.overflow_check == "call" and guard.wait():      # waited for while the last three layers still run
             raise SplitOverflow()
         _ROUTES["x3_local_trunk"] += 1
@@ -292,16 +255,13 @@ class VernierScale(nn.Module):
 
     def trunk_3d(self, voxel):
         """reference vernier.py:415-438 -> (voxel_BEV [N, F*nh/4, nw, nl], occupancy [N,1,nh,nw,nl], offset)."""
-        from .submodule import SplitT
         if not torch.is_grad_enabled():
             st = self._x3_local(voxel)
-            if st is not None:
-                from .submodule import SplitOverflow, _ROUTES
-                try:
-                    return self.trunk_3d_x3(voxel, st)
-                except SplitOverflow:       # this call's clamped result is dropped; the fp32 layers below redo it
-                    self._leave_split_mode("this call was redone in fp32")
-                    _ROUTES["x3_overflow_redo"] += 1
+            if st is not None:      # a flagged call's clamped result is dropped; the fp32 layers redo it
+                return self.checked(self.precision, lambda: self.trunk_3d_x3(voxel, st), lambda: self._trunk_3d_f32(voxel))
+        return self._trunk_3d_f32(voxel)
+
+    def _trunk_3d_f32(self, voxel):
         if isinstance(voxel, SplitT):            # split by construct_voxel_x3, but the trunk has left split mode since (overflow flag)
             voxel = ops.from_split(voxel.t) / voxel.mul_dev
         n, c2 = voxel.size(0), voxel.size(1)
@@ -411,7 +371,6 @@ class VernierScale(nn.Module):
         """reference vernier.py:362-458 -> (heatmaps, occupancy, offset, coordinates, bbox)"""
         if depth is not None:
             raise NotImplementedError
-        from .submodule import SplitT
         if not isinstance(voxel, SplitT) and voxel.dtype == torch.float16:        # a C8 tensor from construct_voxel_f16: fp16-storage mode
             voxel_BEV, occupancy, offset = self.trunk_3d_f16(voxel)
         else:

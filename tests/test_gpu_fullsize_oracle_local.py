@@ -122,7 +122,7 @@ def test_trunk_outputs_vs_oracle_all_elements(case, precision):
 def test_every_split_mode_layer_on_the_oracles_input(case):
     """The layers the default inference path runs (split mode, f16x3), each on the oracle's input of that layer."""
     from snvc_amd import ops
-    from snvc_amd.models.submodule import SplitT, x3_exponent, x3_norm_bound, _Plan
+    from snvc_amd.models.submodule import SplitT, plan_for, x3_exponent, x3_norm_bound
     o = case
     m = _model(o, "auto")
     g = lambda k: o[k].to(dev())                                                                                  # noqa: E731
@@ -132,7 +132,7 @@ def test_every_split_mode_layer_on_the_oracles_input(case):
         if bound_of is None:
             mul = ops.split_scale_for(t)
             return SplitT(ops.to_split(t, mul_dev=mul), 0, None, mul)
-        b = sum(x3_norm_bound(s[0][1], s[0][0].__dict__.setdefault("_snvc_plans_x3", {}).setdefault(dev(), _Plan())) for s in bound_of)
+        b = sum(x3_norm_bound(s[0][1], plan_for(s[0][0], "_x3", dev())) for s in bound_of)
         e = x3_exponent(b)
         return SplitT(ops.to_split(t, e), e, b)
 

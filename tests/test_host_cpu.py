@@ -113,6 +113,37 @@ def test_invalidate_plans_clears_every_cache():
     assert "_snvc_ws" not in m.__dict__
 
 
+def test_both_models_share_one_split_mode_policy():
+    """GlobalStack and VernierScale take what they do about a split-mode overflow from split_mode.SplitModePolicy: neither class
+    body defines a policy method of its own, and there is one place that catches SplitOverflow."""
+    from snvc_amd.models import split_mode, submodule as S
+    from snvc_amd.models.stereo_volume import GlobalStack
+    from snvc_amd.models.vernier import VernierScale
+    assert S.SplitModePolicy is split_mode.SplitModePolicy and S.x3_exponent is split_mode.x3_exponent
+    for name in ("check_overflow", "reset_split_mode", "overflowed", "leave", "checked", "split_guard"):
+        assert getattr(GlobalStack, name) is getattr(VernierScale, name) is getattr(split_mode.SplitModePolicy, name), name
+    for cls in (GlobalStack, VernierScale):
+        own = set(vars(cls))
+        assert not own & {"_leave_split_mode", "_overflowed", "_x3_overflowed", "check_overflow", "reset_split_mode", "overflow_check",
+                          "X3_SIGMAS", "_x3_exponent"}, own
+    src = "".join(open(os.path.join(ROOT, "snvc_amd", "models", f)).read() for f in sorted(os.listdir(os.path.join(ROOT, "snvc_amd", "models")))
+                  if f.endswith(".py"))
+    assert len(re.findall(r"except SplitOverflow\b", src)) == 1
+
+
+def test_one_exponent_rule_and_one_sigma_count():
+    """The overflow guarantee needs every exponent to come from the same rule and the same sigma count: one definition of
+    ``x3_exponent`` and one literal 64.0 in the package's Python sources."""
+    src = ""
+    for dirpath, _, files in os.walk(os.path.join(ROOT, "snvc_amd")):
+        for f in files:
+            if f.endswith(".py"):
+                src += open(os.path.join(dirpath, f)).read()
+    assert len(re.findall(r"def _?x3_exponent\b", src)) == 1
+    lines = re.findall(r"^.*(?<![\w.])64\.0(?!\d).*$", src, re.M)
+    assert len(lines) == 1 and lines[0].startswith("X3_SIGMAS = 64.0"), lines
+
+
 def test_product_never_imports_the_oracle():
     for dirpath, _, files in os.walk(os.path.join(ROOT, "snvc_amd")):
         for f in files:
