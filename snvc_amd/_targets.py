@@ -1,0 +1,53 @@
+"""ctypes binding of the training-target entry points of ``libsnvc_hip.so`` (``include/snvc_targets.h``); the public class
+is ``snvc_amd.geometry.TargetGenerator``.
+
+Kept apart from ``_lib.SIGNATURES`` (the table of ``include/snvc_hip.h``): this header versions itself through
+``snvc_targets_abi_version()``.  The symbols are resolved on ``_lib.lib()``'s handle at first use, so importing this module
+loads nothing.
+"""
+import ctypes
+
+from . import _lib
+
+_ABI = 1   # snvc_targets_abi_version() this binding was written against
+
+c_i64 = ctypes.c_int64
+c_p = ctypes.c_void_p
+c_int = ctypes.c_int
+
+MAX_PARTS = 9          # SNVC_TARGETS_MAX_PARTS
+MAX_SAMPLES = 7000     # SNVC_TARGETS_MAX_SAMPLES
+
+
+class TargetsGrid(ctypes.Structure):
+    """Mirror of ``snvc_targets_grid`` (include/snvc_targets.h)."""
+    _fields_ = [(n, ctypes.c_int32) for n in ("nh", "nw", "nl", "num_parts", "sigma", "grid_type")] + [
+        ("spacing", ctypes.c_double * 3), ("grid_range", ctypes.c_double * 3), ("ranges", ctypes.c_double * 6)]
+
+
+_grid_p = ctypes.POINTER(TargetsGrid)
+
+# name -> (restype, argtypes); kept next to the header so the symbol test can walk it
+SIGNATURES = {
+    "snvc_targets_abi_version": (c_int, []),
+    "snvc_targets_workspace_bytes": (c_i64, [c_i64]),
+    "snvc_targets_fields": (c_int, [_grid_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "snvc_targets_occupancy": (c_int, [_grid_p, c_p, c_p, c_i64, c_p, c_int, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p]),
+}
+
+_bound = None
+
+
+def lib() -> ctypes.CDLL:
+    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
+    global _bound
+    if _bound is None:
+        handle = _lib.lib()
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(handle, name)  # AttributeError if the .so is stale
+            fn.restype = res
+            fn.argtypes = args
+        if handle.snvc_targets_abi_version() != _ABI:
+            raise RuntimeError("libsnvc_hip.so targets ABI version mismatch; rebuild it")
+        _bound = handle
+    return _bound

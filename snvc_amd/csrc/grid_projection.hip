@@ -12,21 +12,10 @@
 // All arithmetic is fp64 in the reference's operation order (products summed k-ascending the way a
 // BLAS micro-kernel does, with FMA), so the float32 results agree bit for bit except where the
 // fp64 value sits within rounding noise of a float32 tie.
-#include "common.hpp"
+#include "grid_point.hpp"
 
 namespace snvc {
 namespace {
-
-struct GridSpec {
-    double x0, xs, x1, y0, ys, y1, z0, zs, z1;   // start, step, stop per axis (numpy.linspace)
-    int nh, nw, nl;
-};
-
-__device__ __forceinline__ double lin(int i, int n, double start, double step, double stop) {
-#pragma clang fp contract(off)
-    if (n > 1 && i == n - 1) return stop;     // numpy pins the end point
-    return (double)i * step + start;
-}
 
 __global__ void __launch_bounds__(256)
 grid_projection_kernel(const double *__restrict__ samples, const double *__restrict__ P_left,
@@ -37,27 +26,9 @@ grid_projection_kernel(const double *__restrict__ samples, const double *__restr
     const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (v >= V) return;
     const int il = (int)(v % g.nl), iw = (int)((v / g.nl) % g.nw), ih = (int)(v / ((int64_t)g.nl * g.nw));
-    const double gx = lin(iw, g.nw, g.x0, g.xs, g.x1);
-    const double gy = lin(ih, g.nh, g.y0, g.ys, g.y1);
-    const double gz = lin(il, g.nl, g.z0, g.zs, g.z1);
-    const double *s = samples + n * 7;
-    double ry, cx, cy, cz;
-    {
-#pragma clang fp contract(off)
-        ry = s[6] + 0.5 * 3.141592653589793;
-        cx = s[3];
-        cy = s[4] - s[0] * 0.5;
-        cz = s[5];
-    }
-    const double c = cos(ry), sn = sin(ry);
-    // rot @ pts (k-ascending FMA chain), then + translation (separately rounded add)
-    double X = fma(sn, gz, fma(0.0, gy, c * gx));
-    double Y = fma(0.0, gz, fma(1.0, gy, 0.0 * gx));
-    double Z = fma(c, gz, fma(0.0, gy, (-sn) * gx));
-    {
-#pragma clang fp contract(off)
-        X = X + cx; Y = Y + cy; Z = Z + cz;
-    }
+    const GridPose pose = grid_pose(samples + n * 7);
+    double X, Y, Z;
+    grid_point_cam(g, pose, ih, iw, il, X, Y, Z);
     if (grid_cam) {
         double *gc = grid_cam + (n * V + v) * 3;
         gc[0] = X; gc[1] = Y; gc[2] = Z;
@@ -92,12 +63,7 @@ int snvc_grid_projection(const double *samples, const double *P_left, const doub
     if (N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_grid_projection: more than 65535 instances");
     if (!samples || !P_left || !P_right || !trans_l || !trans_r || !ranges_host || !out_l || !out_r)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_grid_projection: null pointer");
-    GridSpec g;
-    g.nh = nh; g.nw = nw; g.nl = nl;
-    // numpy.linspace: step = (stop - start) / (num - 1)
-    g.x0 = ranges_host[0]; g.x1 = ranges_host[1]; g.xs = nw > 1 ? (g.x1 - g.x0) / (double)(nw - 1) : 0.0;
-    g.y0 = ranges_host[2]; g.y1 = ranges_host[3]; g.ys = nh > 1 ? (g.y1 - g.y0) / (double)(nh - 1) : 0.0;
-    g.z0 = ranges_host[4]; g.z1 = ranges_host[5]; g.zs = nl > 1 ? (g.z1 - g.z0) / (double)(nl - 1) : 0.0;
+    const GridSpec g = make_grid_spec(ranges_host, nh, nw, nl);
     const int64_t V = (int64_t)nh * nw * nl;
     dim3 grid((unsigned)ceil_div<int64_t>(V, 256), (unsigned)N);
     grid_projection_kernel<<<grid, 256, 0, as_stream(stream)>>>(samples, P_left, P_right, trans_l, trans_r, out_l, out_r,

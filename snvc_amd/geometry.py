@@ -1,4 +1,4 @@
-"""Device-side producer of the path's coordinates.
+"""Device-side producers of the path's coordinates and of its training targets.
 
 Drop-in for the three ``refinementDataset`` methods that turn box proposals into the
 ``grid_proj_left`` / ``grid_proj_right`` tensors VernierScale consumes
@@ -6,13 +6,16 @@ Drop-in for the three ``refinementDataset`` methods that turn box proposals into
 :848-868 ``_generate_grid_proj``).  The reference computes them with numpy float64 on the host
 (786 k points x 2 cameras per instance) and ships 2 x 6.3 MB per instance to the GPU; here they are
 generated where they are used, from 31 doubles per instance.
+
+``TargetGenerator`` does the same for what the losses compare against: ``_generate_displacement_field`` (:870-903), the
+per-part heat maps, the occupancy grid and the part positions, from the boxes and the frame's point cloud.
 """
 import ctypes
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _targets
 from ._lib import check
 
 
@@ -59,3 +62,106 @@ class GridProjector:
                     self.nl, p(out_l), p(out_r), p(g3), n,
                     ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)), "snvc_grid_projection")
         return (out_l, out_r, g3) if with_grid_3d else (out_l, out_r)
+
+
+class TargetGenerator:
+    """Device-side ``refinementDataset._generate_displacement_field`` (KITTIRefinement_dataset.py:870-903).
+
+    ``cfg`` needs what the reference reads from its cfg / ``df_params`` (:88-95): ``grid_resolution`` = (nh, nw, nl),
+    ``spacing`` = (dy, dx, dz), ``grid_range`` (``df_params['range']``), ``x_range`` / ``y_range`` / ``z_range``, ``sigma``
+    (a positive integer), ``num_parts`` (at most 9) and ``grid_type`` ('2D' or '3D')."""
+
+    def __init__(self, cfg):
+        assert cfg.num_parts <= 9, "Only support less than or equal to 9 object parts"
+        if isinstance(cfg.num_parts, bool) or int(cfg.num_parts) != cfg.num_parts or cfg.num_parts < 1:
+            raise ValueError(f"num_parts must be an integer in 1 .. 9, got {cfg.num_parts!r}")
+        if isinstance(cfg.sigma, bool) or not isinstance(cfg.sigma, (int, np.integer)) or cfg.sigma < 1:
+            raise ValueError(f"sigma must be a positive integer (the heat-map window is 6 sigma + 1 cells), got {cfg.sigma!r}")
+        if cfg.grid_type not in ("2D", "3D"):
+            raise ValueError(f"grid_type must be '2D' or '3D', got {cfg.grid_type!r}")
+        self.nh, self.nw, self.nl = (int(v) for v in cfg.grid_resolution)
+        self.num_parts, self.sigma, self.grid_type = int(cfg.num_parts), int(cfg.sigma), cfg.grid_type
+        spacing = np.asarray(cfg.spacing, dtype=np.float64).reshape(3)
+        grid_range = np.asarray(cfg.grid_range, dtype=np.float64).reshape(3)
+        if min(self.nh, self.nw, self.nl) < 1 or not (spacing > 0).all():
+            raise ValueError("grid_resolution and spacing must be positive")
+        g = self.grid = _targets.TargetsGrid()
+        g.nh, g.nw, g.nl, g.num_parts, g.sigma, g.grid_type = self.nh, self.nw, self.nl, self.num_parts, self.sigma, int(self.grid_type[0])
+        g.spacing[:], g.grid_range[:] = spacing.tolist(), grid_range.tolist()
+        g.ranges[:] = [float(v) for v in (*cfg.x_range, *cfg.y_range, *cfg.z_range)]
+
+    def field_shape(self, n):
+        if self.grid_type == "2D":
+            return (n, self.num_parts, self.nl, self.nw)
+        return (n, self.num_parts, self.nh, self.nw, self.nl)
+
+    def generate(self, samples, gt_label, points, device, velo_to_rect=None, frame=None, point_offsets=None,
+                 with_point_masks=False):
+        """samples [N,7] (h,w,l,x,y,z,ry); gt_label [7], or [N,7] for one label per sample; points [P,3] float32 or float64,
+        in rectified-camera coordinates, or in Velodyne coordinates with velo_to_rect = (V2C [3,4], R0 [3,3]).  frame [N] and
+        point_offsets [F+1] (host integers) give sample n the rows point_offsets[frame[n]] : point_offsets[frame[n] + 1].
+        numpy or torch inputs.  Returns (fields, meta) like ``_generate_displacement_field``, on ``device``: fields float32
+        [N,parts,nl,nw] ('2D') or [N,parts,nh,nw,nl] ('3D'); meta['occupancy'] float32 [N,nh,nw,nl] in {-1, 0, 1};
+        meta['gt_corners_local'] float32 [N,parts,3]; with_point_masks adds the bool [N,Pmax] meta['in_roi'] and
+        meta['in_fg'] (row n indexes sample n's rows of ``points``), the reference's pc_in_roi / pc_in_roi_fg lists."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise RuntimeError("TargetGenerator.generate needs a GPU device: Not implemented on the CPU")
+
+        def dev64(a, shape):
+            t = torch.as_tensor(np.asarray(a, dtype=np.float64) if not torch.is_tensor(a) else a, dtype=torch.float64)
+            return t.reshape(shape).contiguous().to(device)
+
+        n = len(samples)
+        if n > _targets.MAX_SAMPLES:
+            raise RuntimeError(f"TargetGenerator.generate: {n} samples in one call is above the limit of {_targets.MAX_SAMPLES}")
+        s = dev64(samples, (n, 7))
+        lab = torch.as_tensor(np.asarray(gt_label, dtype=np.float64)) if not torch.is_tensor(gt_label) else gt_label
+        if lab.numel() == 7:
+            lab = lab.reshape(1, 7).expand(n, 7)
+        elif lab.numel() != 7 * n:
+            raise ValueError(f"gt_label must be [7] or [{n},7], got {tuple(lab.shape)}")
+        lab = dev64(lab, (n, 7))
+        pts = points if torch.is_tensor(points) else torch.from_numpy(np.ascontiguousarray(points))
+        if pts.dim() != 2 or pts.shape[1] != 3 or pts.dtype not in (torch.float32, torch.float64):
+            raise ValueError(f"points must be a float32 or float64 [P,3] array, got {pts.dtype} {tuple(pts.shape)}")
+        pts = pts.contiguous().to(device)
+        total = pts.shape[0]
+        slices, pmax = None, total
+        if (frame is None) != (point_offsets is None):
+            raise ValueError("frame and point_offsets come together or not at all")
+        if frame is not None:
+            fr = np.asarray(frame.cpu() if torch.is_tensor(frame) else frame, dtype=np.int64).reshape(n)
+            off = np.asarray(point_offsets.cpu() if torch.is_tensor(point_offsets) else point_offsets, dtype=np.int64).reshape(-1)
+            if off.size < 2 or off[0] < 0 or off[-1] > total or (np.diff(off) < 0).any():
+                raise ValueError(f"point_offsets must ascend within 0 .. {total}")
+            if n and (fr.min() < 0 or fr.max() > off.size - 2):
+                raise ValueError(f"frame must index the {off.size - 1} frames of point_offsets")
+            host = np.stack([off[fr], off[fr + 1] - off[fr]], axis=1)
+            pmax = int(host[:, 1].max()) if n else 0
+            slices = torch.from_numpy(host).contiguous().to(device)
+        v2r = None
+        if velo_to_rect is not None:
+            v2c, r0 = velo_to_rect
+            v2r = torch.cat([dev64(v2c, (12,)), dev64(r0, (9,))])
+
+        fields = torch.empty(self.field_shape(n), dtype=torch.float32, device=device)
+        corners = torch.empty((n, self.num_parts, 3), dtype=torch.float32, device=device)
+        occ = torch.empty((n, self.nh, self.nw, self.nl), dtype=torch.float32, device=device)
+        meta = {"occupancy": occ, "gt_corners_local": corners}
+        in_roi = in_fg = None
+        if with_point_masks:
+            in_roi = torch.empty((n, pmax), dtype=torch.bool, device=device)
+            in_fg = torch.empty((n, pmax), dtype=torch.bool, device=device)
+            meta["in_roi"], meta["in_fg"] = in_roi, in_fg
+        if n:
+            p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else ctypes.c_void_p(0)  # noqa: E731
+            with torch.cuda.device(device):
+                L = _targets.lib()
+                ws = torch.empty(L.snvc_targets_workspace_bytes(n), dtype=torch.uint8, device=device)
+                stream = ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+                g = ctypes.byref(self.grid)
+                check(L.snvc_targets_fields(g, p(s), p(lab), n, p(ws), p(fields), p(corners), stream), "snvc_targets_fields")
+                check(L.snvc_targets_occupancy(g, p(s), p(lab), n, p(pts), int(pts.dtype == torch.float64), total, p(slices), pmax,
+                                               p(v2r), p(ws), p(occ), p(in_roi), p(in_fg), stream), "snvc_targets_occupancy")
+        return fields, meta
