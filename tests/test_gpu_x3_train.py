@@ -26,17 +26,29 @@ def _t(a):
 def test_affine_act_twin(flags_res, shape):
     """y is the non-twin pass's y bit for bit; the pair is to_split(y) bit for bit (full waves through the LDS transpose, tail waves
     stored directly); the maximum left in the words is max|y|"""
+    _affine_act_twin(flags_res, shape, False)
+
+
+@pytest.mark.parametrize("flags_res", [("relu+pre", True), ("post", True)])
+@pytest.mark.parametrize("shape", [(3, 16, (3, 5, 68)), (2, 8, (2, 3, 258))])
+def test_affine_act_twin_per_sample(flags_res, shape):
+    """the same with scale / shift per (n, c) (GroupNorm): a twin pass that indexed them by channel alone would differ from the plain one"""
+    _affine_act_twin(flags_res, shape, True)
+
+
+def _affine_act_twin(flags_res, shape, per_sample):
     from snvc_amd import ops
     name, with_res = flags_res
     flags = {"relu": ops.EPI_RELU, "relu+pre": ops.EPI_RELU | ops.EPI_ADD_PRE, "post": ops.EPI_ADD_POST, "none": 0}[name]
     n, c, sp = shape
     r = np.random.default_rng(5)
     raw, res = _t(r.standard_normal((n, c) + sp) * 3), (_t(r.standard_normal((n, c) + sp)) if with_res else None)
-    scale, shift = _t(r.uniform(0.5, 2, (1, c))), _t(r.standard_normal((1, c)))
-    ref = ops.affine_act(raw, scale, shift, res, flags)
+    outer = n if per_sample else 1
+    scale, shift = _t(r.uniform(0.5, 2, (outer, c))), _t(r.standard_normal((outer, c)))
+    ref = ops.affine_act(raw, scale, shift, res, flags, per_sample)
     mul = ops.split_scale_of(ref)
     am = ops.amax_word(dev())
-    got = ops.affine_act(raw, scale, shift, res, flags, amax=am, twin_mul=mul)
+    got = ops.affine_act(raw, scale, shift, res, flags, per_sample, amax=am, twin_mul=mul)
     assert torch.equal(got, ref)
     pair, m2 = ops.twin_of(got)
     assert m2 is mul and torch.equal(pair, ops.to_split(ref, mul_dev=mul))
@@ -67,6 +79,17 @@ def test_tags_die_with_a_write_through_out():
 @pytest.mark.parametrize("flags_res", [("relu", False), ("relu+pre", True), ("pre", True)])
 @pytest.mark.parametrize("want_g", [False, True])
 def test_act_backward_apply_twin(flags_res, want_g):
+    _act_backward_apply_twin(flags_res, want_g, False)
+
+
+@pytest.mark.parametrize("flags_res", [("relu+pre", True)])
+@pytest.mark.parametrize("want_g", [False, True])
+def test_act_backward_apply_twin_per_sample(flags_res, want_g):
+    """the same with scale, shift, A, B, Cc per (n, c) (GroupNorm)"""
+    _act_backward_apply_twin(flags_res, want_g, True)
+
+
+def _act_backward_apply_twin(flags_res, want_g, per_sample):
     from snvc_amd import ops
     name, with_res = flags_res
     flags = {"relu": ops.EPI_RELU, "relu+pre": ops.EPI_RELU | ops.EPI_ADD_PRE, "pre": ops.EPI_ADD_PRE}[name]
@@ -74,22 +97,23 @@ def test_act_backward_apply_twin(flags_res, want_g):
     r = np.random.default_rng(6)
     raw, gy = _t(r.standard_normal((n, c) + sp) * 3), _t(r.standard_normal((n, c) + sp) * 1e-4)
     res = _t(r.standard_normal((n, c) + sp)) if with_res else None
-    scale, shift = _t(r.uniform(0.5, 2, (1, c))), _t(r.standard_normal((1, c)))
-    A, B, Cc = _t(r.standard_normal(c)), _t(r.standard_normal(c) * 1e-5), _t(r.standard_normal(c) * 1e-6)
-    d0, g0 = ops.act_backward_apply(raw, gy, res, scale, shift, A, B, Cc, flags, False, want_g)
+    outer = n if per_sample else 1
+    scale, shift = _t(r.uniform(0.5, 2, (outer, c))), _t(r.standard_normal((outer, c)))
+    A, B, Cc = _t(r.standard_normal(outer * c)), _t(r.standard_normal(outer * c) * 1e-5), _t(r.standard_normal(outer * c) * 1e-6)
+    d0, g0 = ops.act_backward_apply(raw, gy, res, scale, shift, A, B, Cc, flags, per_sample, want_g)
     # max|gy| from the reduction pass, the sums unchanged by it
     amg = ops.amax_word(dev())
-    s1 = ops.act_backward_reduce(raw, gy, res, scale, shift, flags, False, amax_gy=amg)
-    s0 = ops.act_backward_reduce(raw, gy, res, scale, shift, flags, False)
+    s1 = ops.act_backward_reduce(raw, gy, res, scale, shift, flags, per_sample, amax_gy=amg)
+    s0 = ops.act_backward_reduce(raw, gy, res, scale, shift, flags, per_sample)
     assert torch.equal(s0, s1) and amg.max().view(torch.float32).item() == gy.abs().max().item()
     l1 = _t(np.full(c, 2.0))
     ax = ops.amax_word(dev())
     ax[3:4] = (raw.abs().max() / 2).reshape(1).view(torch.int32)          # l1 * X = max|raw|
-    mul = ops.split_scale_bound(c, c, dev(), a=A, amax_p=amg, b=B, l1=l1, amax_x=ax, cc=Cc)
+    mul = ops.split_scale_bound(outer * c, c, dev(), a=A, amax_p=amg, b=B, l1=l1, amax_x=ax, cc=Cc)
     bound = float((A.abs() * gy.abs().max() + B.abs() * raw.abs().max() + Cc.abs()).max())
     m = mul.item()
     assert m == 2.0 ** round(np.log2(m)) and 8192.0 <= bound * m < 16384.0 * (1 + 1e-6)
-    d1, g1 = ops.act_backward_apply(raw, gy, res, scale, shift, A, B, Cc, flags, False, want_g, twin_mul=mul)
+    d1, g1 = ops.act_backward_apply(raw, gy, res, scale, shift, A, B, Cc, flags, per_sample, want_g, twin_mul=mul)
     assert torch.equal(d0, d1) and (not want_g or torch.equal(g0, g1))
     pair, _ = ops.twin_of(d1)
     assert torch.equal(pair, ops.to_split(d0, mul_dev=mul))
