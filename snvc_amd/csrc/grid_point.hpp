@@ -1,5 +1,6 @@
 // The Vernier sampling grid in camera coordinates, shared by grid_projection.hip (the projected coordinates) and
-// targets.hip (the occupancy background test), so that both see the same float64 grid point.
+// targets.hip (the occupancy background test), so that both see the same float64 grid point; and the nine points of a box,
+// shared by targets.hip and roi_crop.hip.
 //
 // Reference: refinementDataset._init_3d_grid / _to_cam (snvc/dataset/KITTIRefinement_dataset.py:267-282,828-846).
 // Arithmetic is fp64 in the reference's operation order (products summed k-ascending the way a BLAS micro-kernel does,
@@ -63,6 +64,31 @@ __device__ __forceinline__ void grid_point_cam(const GridSpec &g, const GridPose
     {
 #pragma clang fp contract(off)
         X = X + p.cx; Y = Y + p.cy; Z = Z + p.cz;
+    }
+}
+
+// Shared by targets.hip (the RoI box, the label and the proposal) and roi_crop.hip (the RoI box whose projection is the crop).
+// _construct_box_3d + _get_cam_cord: the centre and the eight corners.  The reference subtracts numpy.float32(l) / 2,
+// numpy.float32(h) and numpy.float32(w) / 2 from float64 lists, so the box is displaced by the float32 rounding of its size.
+__device__ inline void box_points(double h, double w, double l, double x, double y, double z, double ry, double (*pts)[3]) {
+    const double lf = (double)((float)l * 0.5f), hf = (double)(float)h, wf = (double)((float)w * 0.5f);
+    const double xs[9] = {0.5 * l, l, l, l, l, 0, 0, 0, 0};
+    const double ys[9] = {0.5 * h, 0, h, 0, h, 0, h, 0, h};
+    const double zs[9] = {0.5 * w, w, w, 0, 0, w, w, 0, 0};
+    const double c = cos(ry), s = sin(ry);
+    for (int k = 0; k < 9; ++k) {
+        double cx, cy, cz;
+        {
+#pragma clang fp contract(off)
+            cx = xs[k] - lf; cy = ys[k] - hf; cz = zs[k] - wf;
+        }
+        double X = fma(s, cz, fma(0.0, cy, c * cx));
+        double Y = fma(0.0, cz, fma(1.0, cy, 0.0 * cx));
+        double Z = fma(c, cz, fma(0.0, cy, (-s) * cx));
+        {
+#pragma clang fp contract(off)
+            pts[k][0] = X + x; pts[k][1] = Y + y; pts[k][2] = Z + z;
+        }
     }
 }
 

@@ -47,29 +47,7 @@ struct Params {
 };
 
 // ---------------------------------------------------------------------------------------------------- prologue
-// _construct_box_3d + _get_cam_cord: the centre and the eight corners.  The reference subtracts numpy.float32(l) / 2,
-// numpy.float32(h) and numpy.float32(w) / 2 from float64 lists, so the box is displaced by the float32 rounding of its size.
-__device__ void box_points(double h, double w, double l, double x, double y, double z, double ry, double (*pts)[3]) {
-    const double lf = (double)((float)l * 0.5f), hf = (double)(float)h, wf = (double)((float)w * 0.5f);
-    const double xs[9] = {0.5 * l, l, l, l, l, 0, 0, 0, 0};
-    const double ys[9] = {0.5 * h, 0, h, 0, h, 0, h, 0, h};
-    const double zs[9] = {0.5 * w, w, w, 0, 0, w, w, 0, 0};
-    const double c = cos(ry), s = sin(ry);
-    for (int k = 0; k < 9; ++k) {
-        double cx, cy, cz;
-        {
-#pragma clang fp contract(off)
-            cx = xs[k] - lf; cy = ys[k] - hf; cz = zs[k] - wf;
-        }
-        double X = fma(s, cz, fma(0.0, cy, c * cx));
-        double Y = fma(0.0, cz, fma(1.0, cy, 0.0 * cx));
-        double Z = fma(c, cz, fma(0.0, cy, (-s) * cx));
-        {
-#pragma clang fp contract(off)
-            pts[k][0] = X + x; pts[k][1] = Y + y; pts[k][2] = Z + z;
-        }
-    }
-}
+// box_points (_construct_box_3d + _get_cam_cord: the centre and the eight corners) lives in grid_point.hpp, shared with roi_crop.hip.
 
 // construct_mesh_cuboid: per face (p1, p2, p3, .), normal = (p2 - p1) x (p3 - p2), offset = -p1 . normal
 __device__ void box_planes(const double (*pts)[3], double (*planes)[4]) {
