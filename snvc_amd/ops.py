@@ -255,7 +255,83 @@ def _batch_stride(t: torch.Tensor) -> int:
     return t.stride(0) if t.size(0) > 1 else math.prod(t.shape[1:])
 
 
-class Conv3dLayer:
+def _result(out, shape, dtype, device, message: str, layout=None):
+    """The buffer a launch writes: a new one, or the caller's ``out`` validated -- by ``layout`` (``_c8_check`` / ``_split_check``) and its
+    shape, or without one as a ``dtype`` tensor of that shape dense below dim 0 -- with its version counter bumped (``_written``)."""
+    if out is None:
+        return torch.empty(shape, dtype=dtype, device=device)
+    if layout is not None:
+        layout(out, "out")
+    if tuple(out.shape) != shape or (layout is None and (out.dtype != dtype or not _dense_inner(out))):
+        raise RuntimeError(message)
+    _written(out)
+    return out
+
+
+def _residual(residual, shape, message: str, layout=None):
+    """The residual of a launch, validated like ``_result``'s ``out``; a float32 one (no ``layout``) is made dense below dim 0."""
+    if residual is None:
+        return None
+    if layout is not None:
+        layout(residual, "residual")
+    if tuple(residual.shape) != shape:
+        raise RuntimeError(message)
+    return residual if layout is not None or _dense_inner(residual) else residual.contiguous()
+
+
+def _dense_input(x):
+    """(x dense below dim 0, n, in_spatial) of a float32 [N,C,D,H,W] input."""
+    if not _dense_inner(x):
+        x = x.contiguous()
+    return x, x.size(0), tuple(x.shape[2:])
+
+
+class _ConvGeometry:
+    """What the three 3D layer classes share: the geometry of nn.Conv3d(cin, cout, k, stride, pad, dilation) /
+    nn.ConvTranspose3d(cin, cout, 3, padding=1, output_padding=1, stride=2), the output extents and the launch descriptor."""
+
+    def __init__(self, weight: torch.Tensor, ksize: int, stride: int, pad: int, dilation: int, transposed: bool):
+        self.transposed = bool(transposed)
+        if transposed:
+            self.cin, self.cout = weight.shape[0], weight.shape[1]
+        else:
+            self.cout, self.cin = weight.shape[0], weight.shape[1]
+        self.ksize, self.stride, self.pad, self.dilation = int(ksize), int(stride), int(pad), int(dilation)
+        self.planar, self.ksize_h = False, 0        # depth-1 layers: Conv3dLayer only
+
+    def out_spatial(self, in_spatial):
+        if self.transposed and self.planar:
+            return (in_spatial[0], 2 * in_spatial[1], 2 * in_spatial[2])
+        if self.transposed:
+            return tuple(2 * s for s in in_spatial)
+        eff = self.dilation * (self.ksize - 1) + 1
+        if self.planar and self.dilation > 1:     # 3 x 3, dilation 2, pad 2: "same" along H and W
+            return (in_spatial[0], (in_spatial[1] + 2 * self.pad - eff) // self.stride + 1,
+                    (in_spatial[2] + 2 * self.pad - eff) // self.stride + 1)
+        if self.planar:      # the stride and the padding apply to H and W only
+            kh = self.ksize_h or self.ksize
+            return (in_spatial[0], (in_spatial[1] + 2 * ((kh - 1) // 2) - kh) // self.stride + 1,
+                    (in_spatial[2] + 2 * self.pad - eff) // self.stride + 1)
+        return tuple((s + 2 * self.pad - eff) // self.stride + 1 for s in in_spatial)
+
+    def _desc(self, n, in_spatial, flags, algo, x_bs=0, y_bs=0, r_bs=0) -> Conv3dDesc:
+        """The descriptor of one launch; ``algo``: its kernel form (snvc_conv3d_desc.algo), decided by the caller."""
+        d = Conv3dDesc()
+        d.N, d.Cin = n, self.cin
+        d.Din, d.Hin, d.Win = in_spatial
+        d.Cout = self.cout
+        d.Dout, d.Hout, d.Wout = self.out_spatial(in_spatial)
+        d.ksize, d.stride, d.dilation, d.pad = self.ksize, self.stride, self.dilation, self.pad
+        d.transposed = 1 if self.transposed else 0
+        d.flags = flags
+        d.algo = algo
+        d.ksize_d = 1 if self.planar else 0
+        d.ksize_h = self.ksize_h
+        d.x_batch_stride, d.y_batch_stride, d.res_batch_stride = x_bs, y_bs, r_bs
+        return d
+
+
+class Conv3dLayer(_ConvGeometry):
     """One Conv3d / ConvTranspose3d layer prepared for the HIP kernel: geometry, packed weights.
 
     Geometry follows nn.Conv3d(cin, cout, k, stride, pad, dilation, bias=False) as built by
@@ -272,8 +348,6 @@ class Conv3dLayer:
         _gpu(weight, "weight")
         if weight.dtype != torch.float32:
             raise RuntimeError("conv3d weights must be float32")
-        self.transposed = bool(transposed)
-        self.planar = bool(planar)
         if planar and weight.dim() == 4:
             weight = weight.unsqueeze(2)
         if planar and transposed:
@@ -284,16 +358,13 @@ class Conv3dLayer:
             w3 = torch.zeros(weight.shape[:2] + (3, 3, 3), dtype=torch.float32, device=weight.device)
             w3[:, :, 1] = weight[:, :, 0]
             weight = w3
-        if transposed:
-            self.cin, self.cout = weight.shape[0], weight.shape[1]
-        else:
-            self.cout, self.cin = weight.shape[0], weight.shape[1]
+        super().__init__(weight, ksize, stride, pad, dilation, transposed)
+        self.planar = bool(planar)
         self.ksize_h = int(ksize_h) if planar else 0
         if tuple(weight.shape[2:]) != ((1, self.ksize_h or ksize, ksize) if (planar and not transposed) else (ksize,) * 3):
             raise RuntimeError("only cubic kernels (or depth-1 k x k / ksize_h x k ones with planar=True) are on the path")
-        self.ksize, self.stride, self.pad, self.dilation = int(ksize), int(stride), int(pad), int(dilation)
         self.device = weight.device
-        probe = self._desc(1, (1, 16, 32) if planar else (16, 16, 32), 0)
+        probe = self._desc(1, (1, 16, 32) if planar else (16, 16, 32), 0, 0)
         count = _lib.lib().snvc_conv3d_packed_weight_count(ctypes.byref(probe))
         if count < 0:
             check(1, "snvc_conv3d_packed_weight_count")
@@ -301,35 +372,6 @@ class Conv3dLayer:
         with torch.cuda.device(weight.device):
             check(_lib.lib().snvc_conv3d_pack_weights(ctypes.byref(probe), _ptr(weight.detach().contiguous()),
                                                       _ptr(self.packed), _stream(weight)), "snvc_conv3d_pack_weights")
-
-    def out_spatial(self, in_spatial):
-        if self.transposed and getattr(self, "planar", False):
-            return (in_spatial[0], 2 * in_spatial[1], 2 * in_spatial[2])
-        if self.transposed:
-            return tuple(2 * s for s in in_spatial)
-        eff = self.dilation * (self.ksize - 1) + 1
-        if getattr(self, "planar", False) and self.dilation > 1:     # 3 x 3, dilation 2, pad 2: "same" along H and W
-            return (in_spatial[0], (in_spatial[1] + 2 * self.pad - eff) // self.stride + 1,
-                    (in_spatial[2] + 2 * self.pad - eff) // self.stride + 1)
-        if getattr(self, "planar", False):      # the stride and the padding apply to H and W only
-            kh = getattr(self, "ksize_h", 0) or self.ksize
-            return (in_spatial[0], (in_spatial[1] + 2 * ((kh - 1) // 2) - kh) // self.stride + 1,
-                    (in_spatial[2] + 2 * self.pad - eff) // self.stride + 1)
-        return tuple((s + 2 * self.pad - eff) // self.stride + 1 for s in in_spatial)
-
-    def _desc(self, n, in_spatial, flags, x_bs=0, y_bs=0, r_bs=0) -> Conv3dDesc:
-        d = Conv3dDesc()
-        d.N, d.Cin = n, self.cin
-        d.Din, d.Hin, d.Win = in_spatial
-        d.Cout = self.cout
-        d.Dout, d.Hout, d.Wout = self.out_spatial(in_spatial)
-        d.ksize, d.stride, d.dilation, d.pad = self.ksize, self.stride, self.dilation, self.pad
-        d.transposed = 1 if self.transposed else 0
-        d.flags = flags
-        d.ksize_d = 1 if getattr(self, "planar", False) else 0
-        d.ksize_h = getattr(self, "ksize_h", 0)
-        d.x_batch_stride, d.y_batch_stride, d.res_batch_stride = x_bs, y_bs, r_bs
-        return d
 
     def __call__(self, x, scale=None, bias=None, residual=None, flags=0, out=None, depth_planes=None, exact=False,
                  side_head=None):
@@ -340,29 +382,16 @@ class Conv3dLayer:
         _gpu(x, "x")
         if x.dtype != torch.float32 or x.dim() != 5 or x.size(1) != self.cin:
             raise RuntimeError(f"conv3d input must be float32 [N,{self.cin},D,H,W], got {tuple(x.shape)} {x.dtype}")
-        if not _dense_inner(x):
-            x = x.contiguous()
-        n = x.size(0)
-        in_sp = tuple(x.shape[2:])
+        x, n, in_sp = _dense_input(x)
         out_shape = (n, self.cout) + self.out_spatial(in_sp)
         if min(out_shape[2:]) < 1:
             raise RuntimeError("conv3d output would be empty")
-        if out is None:
-            out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-        else:
-            if tuple(out.shape) != out_shape or out.dtype != torch.float32 or not _dense_inner(out):
-                raise RuntimeError("conv3d `out` must be a float32 channel-dense view of the output shape")
-            _written(out)
-        if residual is not None:
-            if tuple(residual.shape) != out_shape:
-                raise RuntimeError("residual must have the output's shape")
-            if not _dense_inner(residual):
-                residual = residual.contiguous()
+        out = _result(out, out_shape, torch.float32, x.device, "conv3d `out` must be a float32 channel-dense view of the output shape")
+        residual = _residual(residual, out_shape, "residual must have the output's shape")
         if n == 0:
             return out
-        d = self._desc(n, in_sp, flags, _batch_stride(x), _batch_stride(out),
+        d = self._desc(n, in_sp, flags, _algo(exact), _batch_stride(x), _batch_stride(out),
                        _batch_stride(residual) if residual is not None else 0)
-        d.algo = _algo(exact)
         if depth_planes is not None:
             if tuple(depth_planes.shape) != (n, self.cout, 3) + out_shape[3:] or not depth_planes.is_contiguous():
                 raise RuntimeError("depth_planes must be a contiguous [N,Cout,3,H,W] tensor")
@@ -391,15 +420,12 @@ class Conv3dLayer:
         if (self.planar or self.ksize != 3 or self.dilation != 1 or self.stride not in (1, 2) or (self.transposed and self.stride != 2) or self.cout % 32
                 or x.dtype != torch.float32 or x.dim() != 5 or x.size(1) != self.cin or x.size(0) == 0 or _algo() != 0):
             return None
-        if not _dense_inner(x):
-            x = x.contiguous()
-        n, in_sp = x.size(0), tuple(x.shape[2:])
+        x, n, in_sp = _dense_input(x)
         out_shape = (n, self.cout) + self.out_spatial(in_sp)
         if min(out_shape[2:]) < 1:
             return None
         out = torch.empty(out_shape, dtype=torch.float32, device=x.device)
-        d = self._desc(n, in_sp, 0, _batch_stride(x), _batch_stride(out), 0)
-        d.algo = _algo()
+        d = self._desc(n, in_sp, 0, _algo(), _batch_stride(x), _batch_stride(out), 0)
         nbytes = _lib.lib().snvc_conv3d_stats_workspace_bytes(ctypes.byref(d))
         if nbytes < 0:
             return None
@@ -727,15 +753,11 @@ def conv3d_forward_avgpool_d4(layer: "Conv3dLayer", x, scale, bias, flags) -> Op
         return None
     if x.dtype != torch.float32 or x.dim() != 5 or x.size(1) != layer.cin or x.size(2) % 4 != 0 or layer.cout % 32 != 0:
         return None
-    if not _dense_inner(x):
-        x = x.contiguous()
-    n = x.size(0)
-    in_sp = tuple(x.shape[2:])
+    x, n, in_sp = _dense_input(x)
     out = torch.empty((n, layer.cout, in_sp[0] // 4, in_sp[1], in_sp[2]), dtype=torch.float32, device=x.device)
     if n == 0:
         return out
-    d = layer._desc(n, in_sp, flags | _lib.EPI_AVGPOOL_D4, _batch_stride(x), 0, 0)
-    d.algo = _algo()
+    d = layer._desc(n, in_sp, flags | _lib.EPI_AVGPOOL_D4, _algo(), _batch_stride(x), 0, 0)
     with torch.cuda.device(x.device):
         rc = _lib.lib().snvc_conv3d_forward_ex(ctypes.byref(d), _ptr(x), _ptr(layer.packed), _ptr(scale), _ptr(bias), _ptr(None),
                                                _ptr(None), _ptr(out), _stream(x))
@@ -751,10 +773,7 @@ def conv3d_forward_head(layer: "Conv3dLayer", x, scale, bias, residual, flags, h
     if not layer.transposed or layer.cout != 32 or x.size(4) % 2 != 0:
         return None
     _gpu(x, "x")
-    if not _dense_inner(x):
-        x = x.contiguous()
-    n = x.size(0)
-    in_sp = tuple(x.shape[2:])
+    x, n, in_sp = _dense_input(x)
     out_sp = layer.out_spatial(in_sp)
     if residual is not None and (tuple(residual.shape) != (n, layer.cout) + out_sp or not _dense_inner(residual)
                                  or residual.data_ptr() % 16 or _batch_stride(residual) % 4):
@@ -762,8 +781,7 @@ def conv3d_forward_head(layer: "Conv3dLayer", x, scale, bias, residual, flags, h
     out = torch.empty((n, 1) + out_sp, dtype=torch.float32, device=x.device)
     if n == 0:
         return out
-    d = layer._desc(n, in_sp, flags, _batch_stride(x), 0, _batch_stride(residual) if residual is not None else 0)
-    d.algo = _algo()
+    d = layer._desc(n, in_sp, flags, _algo(), _batch_stride(x), 0, _batch_stride(residual) if residual is not None else 0)
     hw = head_weight.detach().reshape(-1).contiguous()
     with torch.cuda.device(x.device):
         rc = _lib.lib().snvc_conv3d_forward_head(ctypes.byref(d), _ptr(x), _ptr(layer.packed), _ptr(scale), _ptr(bias),
@@ -1307,7 +1325,7 @@ X3_Q16_MIN_JOBS = [256]   # 3x3x3 layers: (tile, 32-channel block) jobs from whi
 #                           (432 jobs): 0.008-0.023 ms per step in five interleaved A/B runs (tools/ab_step.py, profiles/r5/ab_step_*.txt)
 
 
-class Conv3dLayerF16:
+class Conv3dLayerF16(_ConvGeometry):
     """A Conv3d / ConvTranspose3d layer prepared for the fp16-storage kernels (snvc_f16_conv3d_*): same
     geometry rules as Conv3dLayer; the fp32 parameter is rounded to half when packed."""
 
@@ -1315,18 +1333,14 @@ class Conv3dLayerF16:
         _gpu(weight, "weight")
         if weight.dtype != torch.float32:
             raise RuntimeError("conv3d weights must be float32 (they are rounded to half when packed)")
-        self.transposed = bool(transposed)
-        if transposed:
-            self.cin, self.cout = weight.shape[0], weight.shape[1]
-        else:
-            self.cout, self.cin = weight.shape[0], weight.shape[1]
+        super().__init__(weight, ksize, stride, pad, dilation, transposed)
         if tuple(weight.shape[2:]) != (ksize,) * 3:
             raise RuntimeError("only cubic kernels are on the path")
-        self.ksize, self.stride, self.pad, self.dilation = int(ksize), int(stride), int(pad), int(dilation)
         # r4: the 7^3, 5^3 and dilated 5^3 layers take the 16x16x32 kernel form (decided here: packing and launch must agree)
         self.q16 = bool(X3_Q16[0] and not transposed and self.stride == 1 and self.cout % 32 == 0 and
                         (self.ksize == 7 or (self.ksize == 5 and (self.dilation == 2 or (self.dilation == 1 and X3_Q16_K5[0])))))
-        probe = self._desc(1, (16, 16, 32), 0)
+        self.form = _lib.ALGO_X3_Q16 if self.q16 else 0
+        probe = self._desc(1, (16, 16, 32), 0, self.form)
         nbytes = _lib.lib().snvc_f16_conv3d_packed_weight_bytes(ctypes.byref(probe))
         if nbytes < 0:
             check(1, "snvc_f16_conv3d_packed_weight_bytes")
@@ -1334,14 +1348,6 @@ class Conv3dLayerF16:
         with torch.cuda.device(weight.device):
             check(_lib.lib().snvc_f16_conv3d_pack_weights(ctypes.byref(probe), _ptr(weight.detach().contiguous()),
                                                           _ptr(self.packed), _stream(weight)), "snvc_f16_conv3d_pack_weights")
-
-    out_spatial = Conv3dLayer.out_spatial
-
-    def _desc(self, *a, **k):
-        d = Conv3dLayer._desc(self, *a, **k)
-        if self.q16:
-            d.algo |= _lib.ALGO_X3_Q16
-        return d
 
     def __call__(self, x, scale=None, bias=None, residual=None, flags=0, out=None):
         """y = epilogue(conv(x)) on C8 tensors.  Cout == 1: returns the fp32 plane [N,1,D,H,W] (Sigmoid allowed)."""
@@ -1353,25 +1359,18 @@ class Conv3dLayerF16:
         out_sp = self.out_spatial(in_sp)
         if min(out_sp) < 1:
             raise RuntimeError("conv3d output would be empty")
+        c8_shape = (n, self.cout // 8) + out_sp + (8,)
         plane = self.cout == 1
         y32 = None
         if plane:
             y32 = torch.empty((n, 1) + out_sp, dtype=torch.float32, device=x.device)
             out = None
-        elif out is None:
-            out = torch.empty((n, self.cout // 8) + out_sp + (8,), dtype=torch.float16, device=x.device)
         else:
-            _c8_check(out, "out")
-            if tuple(out.shape) != (n, self.cout // 8) + out_sp + (8,):
-                raise RuntimeError("conv3d `out` must be a C8 view of the output shape")
-            _written(out)
-        if residual is not None:
-            _c8_check(residual, "residual")
-            if tuple(residual.shape) != (n, self.cout // 8) + out_sp + (8,):
-                raise RuntimeError("residual must have the output's shape")
+            out = _result(out, c8_shape, torch.float16, x.device, "conv3d `out` must be a C8 view of the output shape", _c8_check)
+        residual = _residual(residual, c8_shape, "residual must have the output's shape", _c8_check)
         if n == 0:
             return y32 if plane else out
-        d = self._desc(n, in_sp, flags, _batch_stride(x), _batch_stride(out) if out is not None else 0,
+        d = self._desc(n, in_sp, flags, self.form, _batch_stride(x), _batch_stride(out) if out is not None else 0,
                        _batch_stride(residual) if residual is not None else 0)
         with torch.cuda.device(x.device):
             check(_lib.lib().snvc_f16_conv3d_forward(ctypes.byref(d), _ptr(x), _ptr(self.packed), _ptr(scale), _ptr(bias),
@@ -1658,13 +1657,53 @@ def _ones_zeros(c: int, device):
     return hit
 
 
-class Conv3dLayerX3:
+def x3_form(cout: int, ksize: int, stride: int, dilation: int, transposed: bool, n: int, out_sp, plain: bool, split_out: bool,
+            forced: Optional[int]) -> int:
+    """Kernel form (SNVC_ALGO_X3_*) of one split-mode launch, from the layer's geometry, the launch size and the module knobs (read at
+    call time) alone.  A stride-1 layer gets enough workgroups to cover the 256 CUs about four times.  ``plain``: no residual and a
+    split output -- what the 16x16x32 form (r4) covers.  ``forced``: the layer's ``algo=`` (None: the rule decides)."""
+    if forced is None and stride == 1 and not transposed and ksize in (5, 7) and cout % 32 == 0:
+        # 7^3 / 5^3 / dilated 5^3: the 16x16x32 form (four taps per MFMA, planes serial) when the output is a split tensor and the
+        # launch fills the chip (released conv1 2.47 -> 2.10 ms/crop, conv3 0.49 -> 0.42; the plain 5^3 layer with its quads over
+        # all 125 taps 0.53 -> 0.48 -- slice by slice, 28 tap slots for 25 taps gained nothing over the 26 of 13 tap pairs)
+        tiles5 = n * -(-out_sp[0] // 4) * -(-out_sp[1] // 4) * -(-out_sp[2] // 32) * (cout // 32)
+        q16 = X3_Q16[0] and split_out and tiles5 >= 512 and (ksize == 7 or dilation == 2 or X3_Q16_K5[0])
+        return _lib.ALGO_X3_Q16 if q16 else 0
+    if forced is None and ksize == 3 and cout % 64 == 0 and (stride == 2 or transposed):
+        # half-height tiles when the launch would not fill the chip's 512 workgroup slots a few times over (r5; the hourglass's
+        # quarter-resolution level): stride 2 counts 2x4x32 output tiles, a transposed layer 8 classes of 4x4x32 input tiles
+        if transposed:
+            wgs = 8 * n * -(-out_sp[0] // 8) * -(-out_sp[1] // 8) * -(-out_sp[2] // 64)
+            return _lib.ALGO_X3_SMALL if wgs < X3_SMALL_BELOW["transposed"] else 0
+        wgs = n * -(-out_sp[0] // 2) * -(-out_sp[1] // 4) * -(-out_sp[2] // 32)
+        if X3_Q16_S2[0] and plain and split_out:
+            return _lib.ALGO_X3_Q16      # r5: both planes, three image slots, one workgroup per CU (conv3d_x3s2q_kernel)
+        return _lib.ALGO_X3_SMALL if wgs < X3_SMALL_BELOW["stride2"] else 0
+    if forced is not None or stride != 1 or transposed or ksize != 3 or cout == 1:
+        return forced if forced is not None else 0
+    tiles = n * -(-out_sp[0] // 4) * -(-out_sp[1] // 4) * -(-out_sp[2] // 32)
+    if plain and X3_Q16[0] and cout % 32 == 0 and tiles * (cout // 32) >= X3_Q16_MIN_JOBS[0]:
+        return _lib.ALGO_X3_Q16         # v_mfma_f32_16x16x32_f16: ~15 % faster under the chip's power limit (conv2 0.94 -> 0.81 ms)
+    if cout % 64 == 0 and tiles * (cout // 64) >= 1024:
+        return _lib.ALGO_X3_SERIAL      # 64-channel blocks: the serial-plane form measures 6 % faster (0.424 vs 0.453 ms, hg conv2)
+    if tiles * (cout // 32) >= 1024 or cout == 32 and tiles >= 512:
+        return _lib.ALGO_X3_NARROW if cout != 32 else 0
+    return _lib.ALGO_X3_SMALL
+
+
+def _residual_f32_check(residual_f32, y) -> None:
+    if (residual_f32.dtype != torch.float32 or tuple(residual_f32.shape) != tuple(y.shape) or not _dense_inner(residual_f32)
+            or _batch_stride(residual_f32) != _batch_stride(y)):
+        raise RuntimeError("residual_f32 must be a float32 tensor of the result's shape and layout")
+
+
+class Conv3dLayerX3(_ConvGeometry):
     """nn.Conv3d(k3, p1, stride 1 | 2) / nn.ConvTranspose3d(k3, s2, p1, op1) prepared for the split-mode kernels
     (snvc_f16x3_conv3d_*): the fp32 contraction at fp32 accuracy on the half pipe.  The weights are packed as (hi, lo) of
     w * 2**w_exp  with w_exp chosen so that max|w| lands in [2^13, 2^14): both parts then keep their full 11 bits.
     Stride-1 layers have three kernel forms (64-channel blocks on 4x4x32 tiles; 32-channel blocks; 32-channel blocks on 2x4x32
     tiles) whose packed weights differ: the form is picked per call from the number of workgroups the launch would have
-    (``algo`` forces one), its weights packed on first use."""
+    (``x3_form``; ``algo`` forces one), its weights packed on first use.  ``self.algo``: the form of the last launch, a record only."""
 
     def __init__(self, weight: torch.Tensor, ksize: int = 3, stride: int = 1, pad: int = 1, dilation: int = 1, transposed: bool = False,
                  algo: Optional[int] = None, w_mul_dev: Optional[torch.Tensor] = None):
@@ -1673,12 +1712,7 @@ class Conv3dLayerX3:
         _gpu(weight, "weight")
         if weight.dtype != torch.float32:
             raise RuntimeError("conv3d weights must be float32")
-        self.transposed = bool(transposed)
-        if transposed:
-            self.cin, self.cout = weight.shape[0], weight.shape[1]
-        else:
-            self.cout, self.cin = weight.shape[0], weight.shape[1]
-        self.ksize, self.stride, self.pad, self.dilation = int(ksize), int(stride), int(pad), int(dilation)
+        super().__init__(weight, ksize, stride, pad, dilation, transposed)
         self.forced_algo = algo         # None: chosen per call
         self.algo = int(algo or 0)
         self.w_mul_dev = w_mul_dev
@@ -1699,8 +1733,7 @@ class Conv3dLayerX3:
     def _pack(self, algo: int):
         hit = self._packed.get(algo)
         if hit is None:
-            self.algo = algo
-            probe = self._desc(1, (16, 16, 32), 0)
+            probe = self._desc(1, (16, 16, 32), 0, algo)
             nbytes = _lib.lib().snvc_f16x3_conv3d_packed_weight_bytes(ctypes.byref(probe))
             if nbytes < 0:
                 check(2, "snvc_f16x3_conv3d_packed_weight_bytes")
@@ -1711,43 +1744,19 @@ class Conv3dLayerX3:
             self._packed[algo] = hit
         return hit
 
-    def _pick_form(self, n: int, out_sp, plain: bool = False, split_out: bool = False):
-        """Kernel form of a stride-1 layer for this launch: enough workgroups to cover the 256 CUs about four times.
-        ``plain``: no residual and a split output -- what the 16x16x32 form (r4) covers."""
-        if self.forced_algo is None and self.stride == 1 and not self.transposed and self.ksize in (5, 7) and self.cout % 32 == 0:
-            # 7^3 / 5^3 / dilated 5^3: the 16x16x32 form (four taps per MFMA, planes serial) when the output is a split tensor and the
-            # launch fills the chip (released conv1 2.47 -> 2.10 ms/crop, conv3 0.49 -> 0.42; the plain 5^3 layer with its quads over
-            # all 125 taps 0.53 -> 0.48 -- slice by slice, 28 tap slots for 25 taps gained nothing over the 26 of 13 tap pairs)
-            tiles5 = n * -(-out_sp[0] // 4) * -(-out_sp[1] // 4) * -(-out_sp[2] // 32) * (self.cout // 32)
-            q16 = X3_Q16[0] and split_out and tiles5 >= 512 and (self.ksize == 7 or self.dilation == 2 or X3_Q16_K5[0])
-            return _lib.ALGO_X3_Q16 if q16 else 0
-        if self.forced_algo is None and self.ksize == 3 and self.cout % 64 == 0 and (self.stride == 2 or self.transposed):
-            # half-height tiles when the launch would not fill the chip's 512 workgroup slots a few times over (r5; the hourglass's
-            # quarter-resolution level): stride 2 counts 2x4x32 output tiles, a transposed layer 8 classes of 4x4x32 input tiles
-            if self.transposed:
-                wgs = 8 * n * -(-out_sp[0] // 8) * -(-out_sp[1] // 8) * -(-out_sp[2] // 64)
-                return _lib.ALGO_X3_SMALL if wgs < X3_SMALL_BELOW["transposed"] else 0
-            wgs = n * -(-out_sp[0] // 2) * -(-out_sp[1] // 4) * -(-out_sp[2] // 32)
-            if X3_Q16_S2[0] and plain and split_out:
-                return _lib.ALGO_X3_Q16      # r5: both planes, three image slots, one workgroup per CU (conv3d_x3s2q_kernel)
-            return _lib.ALGO_X3_SMALL if wgs < X3_SMALL_BELOW["stride2"] else 0
-        if self.forced_algo is not None or self.stride != 1 or self.transposed or self.ksize != 3 or self.cout == 1:
-            return self.algo
-        tiles = n * -(-out_sp[0] // 4) * -(-out_sp[1] // 4) * -(-out_sp[2] // 32)
-        if plain and X3_Q16[0] and self.cout % 32 == 0 and tiles * (self.cout // 32) >= X3_Q16_MIN_JOBS[0]:
-            return _lib.ALGO_X3_Q16         # v_mfma_f32_16x16x32_f16: ~15 % faster under the chip's power limit (conv2 0.94 -> 0.81 ms)
-        if self.cout % 64 == 0 and tiles * (self.cout // 64) >= 1024:
-            return _lib.ALGO_X3_SERIAL      # 64-channel blocks: the serial-plane form measures 6 % faster (0.424 vs 0.453 ms, hg conv2)
-        if tiles * (self.cout // 32) >= 1024 or self.cout == 32 and tiles >= 512:
-            return _lib.ALGO_X3_NARROW if self.cout != 32 else 0
-        return _lib.ALGO_X3_SMALL
+    def _launch(self, x, plain: bool = False, split_out: bool = False):
+        """(n, in_sp, out_sp, algo, packed) of a launch on ``x``: the kernel form ``x3_form`` gives it and that form's weights."""
+        n, in_sp = x.size(0), tuple(x.shape[3:6])
+        out_sp = self.out_spatial(in_sp)
+        algo = self.algo = x3_form(self.cout, self.ksize, self.stride, self.dilation, self.transposed, n, out_sp, plain, split_out,
+                                   self.forced_algo)
+        return n, in_sp, out_sp, algo, self._pack(algo)
 
-    out_spatial = Conv3dLayer.out_spatial
-
-    def _desc(self, *a, **k):
-        d = Conv3dLayer._desc(self, *a, **k)
-        d.algo = self.algo
-        return d
+    def _unit_affine(self, device):
+        """(1 / w_mul per channel, zeros) of a device-scaled layer's plain convolution: formed once per weight version."""
+        if self._sc_w is None:
+            self._sc_w, self._bi_0 = _ones_zeros(self.cout, device)[0] / self.w_mul_dev, _ones_zeros(self.cout, device)[1]
+        return self._sc_w, self._bi_0
 
     def folded(self, scale, bias, x_exp: int, out_exp: int):
         """(scale', bias') of the epilogue with the exponents folded in: conv sums are in units of 2^(x_exp + w_exp), the
@@ -1771,34 +1780,21 @@ class Conv3dLayerX3:
         _split_check(x, "x")
         if x.size(2) * 8 != self.cin:
             raise RuntimeError(f"conv3d input must have {self.cin} channels (split C8), got {x.size(2) * 8}")
-        n = x.size(0)
-        in_sp = tuple(x.shape[3:6])
-        out_sp = self.out_spatial(in_sp)
         f32 = to_f32 or out_f32 is not None or self.cout == 1        # a one-channel layer (the occupancy head) writes an fp32 plane
+        # r6: the training step's layers (device-scaled weights) take the 16x16x32 stride-1 form with a float32 result too
+        n, in_sp, out_sp, algo, packed = self._launch(x, plain=residual is None and (not f32 or (self.w_mul_dev is not None and head is None)),
+                                                      split_out=not f32 and head is None)
+        split_shape = (n, 2, self.cout // 8) + out_sp + (8,)
         if f32:
-            if out_f32 is None:
-                out_f32 = torch.empty((n, self.cout) + out_sp, dtype=torch.float32, device=x.device)
-            elif tuple(out_f32.shape) != (n, self.cout) + out_sp or out_f32.dtype != torch.float32 or not _dense_inner(out_f32):
-                raise RuntimeError("out_f32 must be a float32 [N,Cout,D,H,W] tensor, dense below dim 0")
-            else:
-                _written(out_f32)
-        elif out is None:
-            out = torch.empty((n, 2, self.cout // 8) + out_sp + (8,), dtype=torch.float16, device=x.device)
+            out_f32 = _result(out_f32, (n, self.cout) + out_sp, torch.float32, x.device,
+                              "out_f32 must be a float32 [N,Cout,D,H,W] tensor, dense below dim 0")
         else:
-            _split_check(out, "out")
-            if tuple(out.shape) != (n, 2, self.cout // 8) + out_sp + (8,):
-                raise RuntimeError("conv3d `out` must be a split C8 tensor of the output shape")
-            _written(out)
-        if residual is not None:
-            _split_check(residual, "residual")
-            if tuple(residual.shape) != (n, 2, self.cout // 8) + out_sp + (8,):
-                raise RuntimeError("residual must have the output's shape (split C8)")
+            out = _result(out, split_shape, torch.float16, x.device, "conv3d `out` must be a split C8 tensor of the output shape", _split_check)
+        residual = _residual(residual, split_shape, "residual must have the output's shape (split C8)", _split_check)
         if residual_f32 is not None:
             if not f32 or residual is not None or flags & (EPI_ADD_PRE | EPI_ADD_POST) or self.cout == 1:
                 raise RuntimeError("residual_f32 goes with a float32 result and no other residual")
-            if (residual_f32.dtype != torch.float32 or tuple(residual_f32.shape) != (n, self.cout) + out_sp or not _dense_inner(residual_f32)
-                    or _batch_stride(residual_f32) != _batch_stride(out_f32)):
-                raise RuntimeError("residual_f32 must be a float32 tensor of the result's shape and layout")
+            _residual_f32_check(residual_f32, out_f32)
             flags = flags | EPI_ADD_POST
         y_head = None
         if head is not None:
@@ -1807,22 +1803,18 @@ class Conv3dLayerX3:
         # with a float32 result the epilogue works in units of 2^out_exp too (the residual's) and scales back on the way out: exact
         if self.w_mul_dev is not None and scale is None and bias is None and x_exp == 0 and out_exp == 0:
             # the training step's plain convolution: 1 / w_mul per channel is formed once per weight version, one small launch per call
-            if self._sc_w is None:
-                self._sc_w, self._bi_0 = _ones_zeros(self.cout, x.device)[0] / self.w_mul_dev, _ones_zeros(self.cout, x.device)[1]
-            sc, bi = (self._sc_w if x_mul_dev is None else (self._sc_w / x_mul_dev)), self._bi_0
+            sc, bi = self._unit_affine(x.device)
+            if x_mul_dev is not None:
+                sc = sc / x_mul_dev
         else:
             sc, bi = self.folded(scale, bias, x_exp, out_exp)
             if x_mul_dev is not None:           # x holds values * x_mul_dev (a device-side power of two, see split_scale_for); x_exp is 0
                 sc = (sc / x_mul_dev).contiguous()
             if self.w_mul_dev is not None:
                 sc = (sc / self.w_mul_dev).contiguous()
-        # r6: the training step's layers (device-scaled weights) take the 16x16x32 stride-1 form with a float32 result too
-        self.algo = self._pick_form(n, out_sp, plain=residual is None and (not f32 or (self.w_mul_dev is not None and head is None)),
-                                    split_out=not f32 and head is None)
-        packed = self._pack(self.algo)
         if n == 0:
             return out_f32 if f32 else ((out, y_head) if head is not None else out)
-        d = self._desc(n, in_sp, flags, _batch_stride(x), _batch_stride(out_f32 if f32 else out),
+        d = self._desc(n, in_sp, flags, algo, _batch_stride(x), _batch_stride(out_f32 if f32 else out),
                        _batch_stride(residual) if residual is not None else 0)
         null = ctypes.c_void_p(0)
         with torch.cuda.device(x.device):
@@ -1844,22 +1836,16 @@ class Conv3dLayerX3:
         _split_check(x, "x")
         if self.w_mul_dev is None or x.size(2) * 8 != self.cin:
             raise RuntimeError("forward_f32: a device-scaled layer (w_mul_dev) and an input of its channel count")
-        n = x.size(0)
-        in_sp = tuple(x.shape[3:6])
-        out_sp = self.out_spatial(in_sp)
-        if self._sc_w is None:
-            self._sc_w, self._bi_0 = _ones_zeros(self.cout, x.device)[0] / self.w_mul_dev, _ones_zeros(self.cout, x.device)[1]
+        n, in_sp, out_sp, algo, packed = self._launch(x, plain=True, split_out=False)
+        sc, bi = self._unit_affine(x.device)
         y = torch.empty((n, self.cout) + out_sp, dtype=torch.float32, device=x.device)
-        if residual_f32 is not None and (residual_f32.dtype != torch.float32 or tuple(residual_f32.shape) != tuple(y.shape)
-                                         or not _dense_inner(residual_f32) or _batch_stride(residual_f32) != _batch_stride(y)):
-            raise RuntimeError("residual_f32 must be a float32 tensor of the result's shape and layout")
-        self.algo = self._pick_form(n, out_sp, plain=True, split_out=False)
-        packed = self._pack(self.algo)
+        if residual_f32 is not None:
+            _residual_f32_check(residual_f32, y)
         if n == 0:
             return y
-        d = self._desc(n, in_sp, EPI_RELU if relu else 0, _batch_stride(x), _batch_stride(y), 0)
+        d = self._desc(n, in_sp, EPI_RELU if relu else 0, algo, _batch_stride(x), _batch_stride(y), 0)
         with torch.cuda.device(x.device):
-            check(_lib.lib().snvc_f16x3_conv3d_forward_f32(ctypes.byref(d), _ptr(x), _lo_ptr(x), _ptr(packed), _ptr(self._sc_w), _ptr(self._bi_0),
+            check(_lib.lib().snvc_f16x3_conv3d_forward_f32(ctypes.byref(d), _ptr(x), _lo_ptr(x), _ptr(packed), _ptr(sc), _ptr(bi),
                                                            _ptr(x_mul_dev), _ptr(residual_f32), _ptr(y), 1.0, _stream(x)),
                   "snvc_f16x3_conv3d_forward_f32")
         return y
@@ -1871,23 +1857,17 @@ class Conv3dLayerX3:
         _split_check(x, "x")
         if self.w_mul_dev is None or x.size(2) * 8 != self.cin or self.cout % 32:
             return None
-        n = x.size(0)
-        in_sp = tuple(x.shape[3:6])
-        out_sp = self.out_spatial(in_sp)
-        if self._sc_w is None:
-            self._sc_w, self._bi_0 = _ones_zeros(self.cout, x.device)[0] / self.w_mul_dev, _ones_zeros(self.cout, x.device)[1]
-        sc = self._sc_w                        # 1 / x_mul is applied by the kernel (x_mul: a device pointer)
-        self.algo = self._pick_form(n, out_sp, plain=True, split_out=False)
-        packed = self._pack(self.algo)
+        n, in_sp, out_sp, algo, packed = self._launch(x, plain=True, split_out=False)
+        sc, bi = self._unit_affine(x.device)        # 1 / x_mul is applied by the kernel (x_mul: a device pointer)
         raw = torch.empty((n, self.cout) + out_sp, dtype=torch.float32, device=x.device)
-        d = self._desc(n, in_sp, 0, _batch_stride(x), _batch_stride(raw), 0)
+        d = self._desc(n, in_sp, 0, algo, _batch_stride(x), _batch_stride(raw), 0)
         nbytes = _lib.lib().snvc_f16x3_conv3d_stats_workspace_bytes(ctypes.byref(d))
         if nbytes < 0:
             return None
         ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
         out = torch.empty((4, self.cout), dtype=torch.float32, device=x.device)
         with torch.cuda.device(x.device):
-            rc = _lib.lib().snvc_f16x3_conv3d_forward_stats(ctypes.byref(d), _ptr(x), _lo_ptr(x), _ptr(packed), _ptr(sc), _ptr(self._bi_0),
+            rc = _lib.lib().snvc_f16x3_conv3d_forward_stats(ctypes.byref(d), _ptr(x), _lo_ptr(x), _ptr(packed), _ptr(sc), _ptr(bi),
                                                             _ptr(x_mul_dev), _ptr(raw), 1.0, _ptr(gamma), _ptr(beta), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]),
                                                             _ptr(out[3]), _ptr(ws), float(eps), _stream(x))
         if rc == 2:            # SNVC_ERR_UNSUPPORTED: the caller runs the convolution and the statistics pass separately
@@ -1904,9 +1884,7 @@ class Conv3dLayerX3:
         _split_check(x, "x")
         if not self.transposed or self.stride != 2 or x.size(2) * 8 != self.cin or tail.cin != self.cout:
             raise RuntimeError("forward_tail: a ConvTranspose3d(k3,s2,p1,op1) layer whose Cout equals the tail's Cin")
-        n = x.size(0)
-        in_sp = tuple(x.shape[3:6])
-        out_sp = self.out_spatial(in_sp)
+        n, in_sp, out_sp, algo, packed = self._launch(x)
         shape = (n, 27, 8) + in_sp
         if out is None:
             out = torch.empty(shape, dtype=torch.float32, device=x.device)
@@ -1914,16 +1892,11 @@ class Conv3dLayerX3:
             raise RuntimeError("forward_tail `out` must be a contiguous float32 [N, 27, 8, Din, Hin, Win] tensor")
         else:
             _written(out)
-        if residual is not None:
-            _split_check(residual, "residual")
-            if tuple(residual.shape) != (n, 2, self.cout // 8) + out_sp + (8,):
-                raise RuntimeError("residual must have the layer's output shape (split C8)")
+        residual = _residual(residual, (n, 2, self.cout // 8) + out_sp + (8,), "residual must have the layer's output shape (split C8)", _split_check)
         sc, bi = self.folded(scale, bias, x_exp, out_exp)
-        self.algo = self._pick_form(n, out_sp)
-        packed = self._pack(self.algo)
         if n == 0:
             return out
-        d = self._desc(n, in_sp, flags, _batch_stride(x), 0, _batch_stride(residual) if residual is not None else 0)
+        d = self._desc(n, in_sp, flags, algo, _batch_stride(x), 0, _batch_stride(residual) if residual is not None else 0)
         null = ctypes.c_void_p(0)
         with torch.cuda.device(x.device):
             check(_lib.lib().snvc_f16x3_deconv3d_tail_forward(

@@ -621,3 +621,95 @@ def test_f16_storage_16x16x32_forms_vs_torch(case):
         close_f16(got.cpu(), exp.float(), f"{case} flags={flags}")
         was = ops.from_c8(old(xc, scale, bias, flags=flags, **kw), cout)
         close_f16(got.cpu(), was.cpu(), f"{case} flags={flags}: 16x16x32 vs 32x32x16")
+
+
+def _same(a, b):
+    if a is None or b is None:
+        return a is None and b is None
+    if isinstance(a, tuple):
+        return len(a) == len(b) and all(torch.equal(p, q) for p, q in zip(a, b))
+    return torch.equal(a, b)
+
+
+def test_split_layer_form_is_per_call_not_per_object():
+    """One Conv3dLayerX3 object called at sizes and with outputs that take different kernel forms, interleaved, forwards and backwards:
+    every result is bit-equal to that of a fresh object with the form forced by ``algo=``, and ``.algo`` records the form of the last
+    launch.  The forms are what the launch-size rule gives these calls (tests/test_x3_form_host.py holds the rule itself)."""
+    from snvc_amd import _lib as L_, ops
+    torch.manual_seed(31)
+
+    def layer_and_inputs(cin, cout, stride, transposed, *shapes):
+        w = torch.randn((cin, cout, 3, 3, 3) if transposed else (cout, cin, 3, 3, 3), device=dev()) * np.sqrt(2.0 / (cin * 27))
+        return w, [ops.to_split(torch.randn(*s, device=dev()), 1) for s in shapes]
+
+    w1, (x_small, x_big) = layer_and_inputs(32, 32, 1, False, (2, 32, 8, 12, 40), (1, 32, 16, 32, 512))
+    w2, (x_s2,) = layer_and_inputs(32, 64, 2, False, (2, 32, 8, 12, 72))
+    w3, (x_tr,) = layer_and_inputs(64, 64, 2, True, (2, 64, 4, 6, 20))
+    r_small = ops.to_split(torch.randn(2, 32, 8, 12, 40, device=dev()), 1)
+    r_big = ops.to_split(torch.randn(1, 32, 16, 32, 512, device=dev()), 1)
+    geo = {"s1": (w1, 1, False), "s2": (w2, 2, False), "tr": (w3, 2, True)}
+    shared = {k: ops.Conv3dLayerX3(w, 3, st, 1, 1, tr) for k, (w, st, tr) in geo.items()}
+    add = ops.EPI_RELU | ops.EPI_ADD_POST
+    calls = [("s1", L_.ALGO_X3_SMALL, lambda lay: lay(x_small, 1, residual=r_small, flags=add, out_exp=1)),
+             ("s2", L_.ALGO_X3_Q16, lambda lay: lay(x_s2, 1, flags=ops.EPI_RELU, out_exp=1)),
+             ("s1", 0, lambda lay: lay(x_big, 1, residual=r_big, flags=add, out_exp=1)),
+             ("tr", L_.ALGO_X3_SMALL, lambda lay: lay(x_tr, 1, flags=ops.EPI_RELU, out_exp=1)),
+             ("s1", L_.ALGO_X3_Q16, lambda lay: lay(x_big, 1, flags=ops.EPI_RELU, out_exp=1)),
+             ("s2", 0, lambda lay: lay(x_s2, 1, flags=ops.EPI_RELU, to_f32=True))]
+    want = []
+    for key, form, call in calls:
+        w, st, tr = geo[key]
+        want.append(call(ops.Conv3dLayerX3(w, 3, st, 1, 1, tr, algo=form)))
+    for order in (range(len(calls)), reversed(range(len(calls)))):
+        for i in order:
+            key, form, call = calls[i]
+            got = call(shared[key])
+            assert shared[key].algo == form, f"call {i}: form {shared[key].algo:#x}, the rule gives {form:#x}"
+            assert torch.equal(got, want[i]), f"call {i}: differs from a fresh layer with algo={form:#x}"
+
+
+def test_device_scaled_layer_entry_points_in_any_order():
+    """A device-scaled layer (``w_mul_dev``): forward_stats, forward_f32 and __call__ on one object, in that order and in the reverse
+    order, each bit-equal to the same call on a fresh object (the entry points share the packed weights and the unit affine)."""
+    from snvc_amd import ops
+    torch.manual_seed(32)
+    x = torch.relu(torch.randn(2, 32, 8, 12, 40, device=dev()))
+    w = torch.randn(32, 32, 3, 3, 3, device=dev()) * 0.05
+    gamma, beta = torch.rand(32, device=dev()) + 0.5, torch.randn(32, device=dev())
+    mul = ops.split_scale_of(x)
+    xs = ops.to_split(x, mul_dev=mul)
+
+    def fresh():
+        return ops.Conv3dLayerX3(w, w_mul_dev=ops.split_scale_of(w))
+
+    calls = [lambda lay: lay.forward_stats(xs, mul, gamma, beta, 1e-5), lambda lay: lay.forward_f32(xs, mul),
+             lambda lay: lay(xs, 0, None, None, to_f32=True, x_mul_dev=mul)]
+    want = [call(fresh()) for call in calls]
+    assert want[1] is not None and want[2] is not None
+    for order in ((0, 1, 2), (2, 1, 0)):
+        lay = fresh()
+        for i in order:
+            assert _same(calls[i](lay), want[i]), f"entry point {i} in order {order}"
+
+
+def test_fp32_layer_variant_bits_are_per_call():
+    """A Conv3dLayer called under conv_variant(ALGO_DIRECT) and outside it, alternating: each result bit-equal to a fresh object's in the
+    same setting (the kernel form is an argument of the launch descriptor, not something a call leaves behind)."""
+    from snvc_amd import _lib as L_, ops
+    torch.manual_seed(33)
+    x = torch.randn(2, 8, 6, 7, 33, device=dev())
+    w = torch.randn(16, 8, 3, 3, 3, device=dev()) * 0.1
+
+    def fresh():
+        return ops.Conv3dLayer(w, 3, 1, 1, 1, False)
+
+    plain = fresh()(x)
+    with ops.conv_variant(L_.ALGO_DIRECT):
+        direct = fresh()(x)
+    lay = fresh()
+    for _ in range(2):
+        assert torch.equal(lay(x), plain)
+        with ops.conv_variant(L_.ALGO_DIRECT):
+            assert torch.equal(lay(x), direct)
+        assert torch.equal(lay(x, exact=True), direct)
+    assert torch.equal(lay(x), plain)
