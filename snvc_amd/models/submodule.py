@@ -23,7 +23,7 @@ module tree; their inference forward runs on the depth-1 form of the same HIP co
 (``fused_conv2d`` / ``fused_deconv2d``); under autograd / with train-mode BatchNorm the same kernels sit behind
 ``_Conv2dNormActFn`` (r4: HIP backward -- epilogue reductions, data gradient as a twin layer, deterministic weight gradient).
 """
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -136,38 +136,22 @@ def _folded_bn(bn: nn.BatchNorm3d, plan: _Plan):
 _BatchNormNd = (nn.BatchNorm3d, nn.BatchNorm2d)      # the 2D neck's layers run as depth-1 3D layers (raw is 5-D either way)
 
 
-def _norm_from_raw(raw, norm, plan, residual, flags, out=None):
-    """norm + residual + activation of an already computed conv output `raw` (kept for the backward pass):
-    returns (y, scale, shift, mean, var, per_sample)."""
-    if norm is None:
-        if flags or residual is not None:
-            return ops.affine_act(raw, None, None, residual, flags, out=out), None, None, None, None, False
-        return raw, None, None, None, None, False
-    if isinstance(norm, _BatchNormNd) and not (norm.training or norm.running_mean is None):
-        scale, bias = _folded_bn(norm, plan)
-        return ops.affine_act(raw, scale, bias, residual, flags, out=out), scale, bias, None, None, False
-    c = raw.size(1)
-    if isinstance(norm, nn.GroupNorm):
-        scale, shift, mean, var = ops.norm_stats(raw, norm.weight, norm.bias, norm.num_groups, True, norm.eps)
-        return ops.affine_act(raw, scale, shift, residual, flags, per_sample=True, out=out), scale, shift, mean, var, True
-    if isinstance(norm, _BatchNormNd):
-        scale, shift, mean, var = ops.norm_stats(raw, norm.weight, norm.bias, c, False, norm.eps)
-        _bn_track(norm, mean, var, raw.numel() / c)      # nn.BatchNorm3d bookkeeping: momentum update with the unbiased variance
-        return ops.affine_act(raw, scale, shift, residual, flags, per_sample=False, out=out), scale, shift, mean, var, False
-    raise NotImplementedError(f"norm layer {type(norm).__name__} is not on the path")
+class _Epilogue(NamedTuple):
+    """One layer's epilogue state: ``y`` = act(norm(raw) [+ res]) [+ res] and what the backward pass needs of the way there.  ``raw``
+    is the conv output before the affine / activation (None when the single fused launch was used), ``scale`` / ``shift`` the affine
+    the pass applied ([C], or [N, C] with ``per_sample``: GroupNorm), ``mean`` / ``var`` the statistics taken in this forward (None:
+    no norm or frozen BatchNorm)."""
+    y: Optional[torch.Tensor]
+    raw: Optional[torch.Tensor]
+    scale: Optional[torch.Tensor]
+    shift: Optional[torch.Tensor]
+    mean: Optional[torch.Tensor]
+    var: Optional[torch.Tensor]
+    per_sample: bool
 
-
-def _norm_forward(layer, norm, plan, x, residual, flags, out, keep_raw, exact=False, twin=None):
-    """Shared forward: returns (y, raw, scale, shift, mean, var, per_sample).  `raw` is the conv
-    output before the affine/activation (None when the single fused launch was used).
-    ``keep_raw`` (the autograd functions): the pass that writes y also leaves max|y| in a device word tagged onto y (ops.tag_amax):
-    the next layer's split-operand weight gradient scales its x operand by it (r6).  ``twin`` (r6, see _twin_mul_forward): that pass
-    also writes y's split C8 twin for a consumer that runs on the split kernels."""
-    am = ops.amax_word(x.device) if (keep_raw and x.is_cuda) else None
-    res = _norm_forward_impl(layer, norm, plan, x, residual, flags, out, keep_raw, exact, am, twin)
-    if am is not None and res[1] is not None and res[0] is not res[1]:      # y came out of affine_act (not the raw tensor itself)
-        ops.tag_amax(res[0], am)
-    return res
+    @property
+    def train_stats(self) -> bool:
+        return self.mean is not None
 
 
 def _twin_mul_forward(twin, scale, shift, residual, c, device):
@@ -185,47 +169,56 @@ def _twin_mul_forward(twin, scale, shift, residual, c, device):
     return ops.split_scale_bound(rows, c, device, b=scale, l1=twin[0], amax_x=twin[1], cc=shift, amax_r=ar)
 
 
-def _norm_forward_impl(layer, norm, plan, x, residual, flags, out, keep_raw, exact, am, twin=None):
-    _affine_act = ops.affine_act
-    if twin is not None:
-        def _affine_act(raw, scale, shift, residual=None, flags=0, per_sample=False, out=None, amax=None):
-            ok = ops.twin_ok(raw) and not (flags & EPI_SIGMOID)           # a sigmoid's result is not bounded by its argument's bound
-            tm = _twin_mul_forward(twin, scale, shift, residual, raw.size(1), raw.device) if ok else None
-            return ops.affine_act(raw, scale, shift, residual, flags, per_sample=per_sample, out=out, amax=amax, twin_mul=tm)
+def _norm_over_raw(raw, norm, plan, residual, flags, out=None, amax=None, twin=None, stats=None) -> _Epilogue:
+    """norm (+ residual) (+ activation) of an already computed conv output ``raw``: no norm / frozen BatchNorm / GroupNorm /
+    train-mode BatchNorm.  ``out``: where y goes (None: a new tensor; ``raw`` itself: in place).  ``amax``: zeroed words that receive
+    max|y| (ops.amax_word).  ``twin`` (r6, see _twin_mul_forward): the pass also writes y's split C8 twin for a consumer that runs on
+    the split kernels.  ``stats``: the (scale, shift, mean, var) of a train-mode BatchNorm when the conv kernel's own epilogue took them."""
+    def act(scale, shift, mean=None, var=None, per_sample=False):
+        tm = None
+        if twin is not None and ops.twin_ok(raw) and not (flags & EPI_SIGMOID):      # a sigmoid's result is not bounded by its argument's bound
+            tm = _twin_mul_forward(twin, scale, shift, residual, raw.size(1), raw.device)
+        y = ops.affine_act(raw, scale, shift, residual, flags, per_sample=per_sample, out=out, amax=amax, twin_mul=tm)
+        return _Epilogue(y, raw, scale, shift, mean, var, per_sample)
+
     if norm is None:
-        if keep_raw and (flags or residual is not None):
-            raw = layer(x, None, None, None, 0, None, exact=exact)
-            return _affine_act(raw, None, None, residual, flags, out=out, amax=am), raw, None, None, None, None, False
-        y = layer(x, None, None, residual, flags, out, exact=exact)
-        return y, (y if keep_raw else None), None, None, None, None, False
-    if isinstance(norm, nn.BatchNorm3d) and not (norm.training or norm.running_mean is None):
-        scale, bias = _folded_bn(norm, plan)
-        if keep_raw:
-            raw = layer(x, None, None, None, 0, None, exact=exact)
-            return _affine_act(raw, scale, bias, residual, flags, out=out, amax=am), raw, scale, bias, None, None, False
-        return layer(x, scale, bias, residual, flags, out, exact=exact), None, scale, bias, None, None, False
-    # statistics of the conv output are needed first: conv -> stats -> normalise (+res, +act)
-    if isinstance(norm, nn.BatchNorm3d) and not exact:
+        return act(None, None) if (flags or residual is not None) else _Epilogue(raw, raw, None, None, None, None, False)
+    if isinstance(norm, _BatchNormNd) and not (norm.training or norm.running_mean is None):
+        return act(*_folded_bn(norm, plan))
+    c = raw.size(1)
+    if isinstance(norm, nn.GroupNorm):
+        return act(*ops.norm_stats(raw, norm.weight, norm.bias, norm.num_groups, True, norm.eps), per_sample=True)
+    if isinstance(norm, _BatchNormNd):
+        scale, shift, mean, var = stats if stats is not None else ops.norm_stats(raw, norm.weight, norm.bias, c, False, norm.eps)
+        _bn_track(norm, mean, var, raw.numel() / c)      # nn.BatchNorm3d bookkeeping: momentum update with the unbiased variance
+        return act(scale, shift, mean, var)
+    raise NotImplementedError(f"norm layer {type(norm).__name__} is not on the path")
+
+
+def _norm_forward(layer, norm, plan, x, residual, flags, out, keep_raw, exact=False, twin=None) -> _Epilogue:
+    """The conv-first forward of a layer.  ``keep_raw`` (the autograd functions): the conv output is kept for the backward pass, and
+    the pass that writes y also leaves max|y| in a device word tagged onto y (ops.tag_amax): the next layer's split-operand weight
+    gradient scales its x operand by it (r6).  ``twin``: see _norm_over_raw."""
+    am = ops.amax_word(x.device) if (keep_raw and x.is_cuda) else None
+    frozen = _is_frozen_norm(norm)                       # the conv-first fast paths know BatchNorm3d only; _norm_over_raw takes 2D as well
+    if frozen and not keep_raw:                          # nothing to keep, no statistics to take: the single fused launch
+        scale, bias = _folded_bn(norm, plan) if norm is not None else (None, None)
+        return _Epilogue(layer(x, scale, bias, residual, flags, out, exact=exact), None, scale, bias, None, None, False)
+    raw = stats = None
+    if isinstance(norm, nn.BatchNorm3d) and not frozen and not exact:
         # the 3x3x3 Winograd kernels take the batch statistics in their own epilogue (one read of the tensor less)
         got = layer.forward_stats(x, norm.weight.detach() if norm.weight is not None else None,
                                   norm.bias.detach() if norm.bias is not None else None, norm.eps)
         if got is not None:
-            raw, scale, shift, mean, var = got
+            raw, stats = got[0], got[1:]
             _ROUTES["conv_stats_epilogue"] += 1
-            _bn_track(norm, mean, var, raw.numel() / raw.size(1))
-            dst = out if out is not None else (None if keep_raw else raw)
-            return _affine_act(raw, scale, shift, residual, flags, per_sample=False, out=dst, amax=am), raw, scale, shift, mean, var, False
-    raw = layer(x, None, None, None, 0, None, exact=exact)
-    c = raw.size(1)
-    dst = out if out is not None else (None if keep_raw else raw)
-    if isinstance(norm, nn.GroupNorm):
-        scale, shift, mean, var = ops.norm_stats(raw, norm.weight, norm.bias, norm.num_groups, True, norm.eps)
-        return _affine_act(raw, scale, shift, residual, flags, per_sample=True, out=dst, amax=am), raw, scale, shift, mean, var, True
-    if isinstance(norm, nn.BatchNorm3d):
-        scale, shift, mean, var = ops.norm_stats(raw, norm.weight, norm.bias, c, False, norm.eps)
-        _bn_track(norm, mean, var, raw.numel() / c)      # nn.BatchNorm3d bookkeeping: momentum update with the unbiased variance
-        return _affine_act(raw, scale, shift, residual, flags, per_sample=False, out=dst, amax=am), raw, scale, shift, mean, var, False
-    raise NotImplementedError(f"norm layer {type(norm).__name__} is not on the path")
+    if raw is None:
+        raw = layer(x, None, None, None, 0, None, exact=exact)
+    dst = out if out is not None else (None if keep_raw else raw)      # in place on raw only when nobody needs it afterwards
+    rec = _norm_over_raw(raw, norm, plan, residual, flags, dst, am, twin, stats)
+    if am is not None and rec.y is not raw:              # y came out of affine_act (not the raw tensor itself)
+        ops.tag_amax(rec.y, am)
+    return rec
 
 
 def _dgrad_layer(conv: nn.Module, plan: _Plan) -> ops.Conv3dLayer:
@@ -315,7 +308,7 @@ def _split_operand(t: torch.Tensor, amax: Optional[torch.Tensor]):
 
 
 class _X3TrainLayer:
-    """The plain convolution of a layer on the split kernels behind Conv3dLayer's calling convention (what _norm_forward_impl calls
+    """The plain convolution of a layer on the split kernels behind Conv3dLayer's calling convention (what _norm_forward calls
     with keep_raw): float32 NCDHW in (through its twin), float32 NCDHW out."""
     ksize = 3
 
@@ -395,28 +388,26 @@ class _ConvNormActFn(torch.autograd.Function):
         # comparisons against another implementation see as isolated differences
         ctx.x_amax = ops.amax_of(x)          # max|x| left by the pass that wrote x (None: the weight gradient finds it itself)
         twin = (_l1_out(conv, plan), ctx.x_amax) if (getattr(plan, "want_twin", False) and X3_TRAIN[0] and x.is_cuda) else None
-        y, raw, scale, shift, mean, var, per_sample = _norm_forward(layer, norm, plan, x, residual, flags, None, True,
-                                                                    exact=layer.ksize >= 5 and TRAIN_EXACT_K57[0], twin=twin)
-        if y is not raw:
-            y.snvc_twin_src = plan            # a consumer on the split kernels asks for the twin here (_split_operand)
-        ctx.conv, ctx.norm, ctx.flags, ctx.plan, ctx.per_sample = conv, norm, flags, plan, per_sample
+        rec = _norm_forward(layer, norm, plan, x, residual, flags, None, True, exact=layer.ksize >= 5 and TRAIN_EXACT_K57[0], twin=twin)
+        if rec.y is not rec.raw:
+            rec.y.snvc_twin_src = plan        # a consumer on the split kernels asks for the twin here (_split_operand)
+        ctx.conv, ctx.norm, ctx.flags, ctx.plan = conv, norm, flags, plan
         ctx.has_res = residual is not None
-        ctx.train_stats = mean is not None
         res_saved = residual if (residual is not None and (flags & EPI_ADD_PRE)) else None
-        ctx.save_for_backward(x, raw, scale, shift, mean, var, res_saved)
-        return y
+        _save_epilogue(ctx, rec, x, res_saved)
+        return rec.y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x, raw, scale, shift, mean, var, res = ctx.saved_tensors
+        rec, x, res = _saved_epilogue(ctx)
         conv, norm, flags, plan = ctx.conv, ctx.norm, ctx.flags, ctx.plan
         needs = ctx.needs_input_grad
         x3 = ctx.x3 and needs[0]
-        g_amax = ops.amax_word(raw.device) if ((needs[1] or x3) and raw.is_cuda) else None
+        g_amax = ops.amax_word(rec.raw.device) if ((needs[1] or x3) and rec.raw.is_cuda) else None
         twin = (_l1_out(conv, plan), ctx.x_amax) if (x3 and ctx.x_amax is not None) else None
-        draw, gres, dg, db = _epilogue_backward(raw, gy, res, scale, shift, mean, var, norm, flags, ctx.per_sample, ctx.train_stats,
-                                                ctx.has_res and needs[4], needs[2], needs[3], amax_out=g_amax, twin=twin)
+        draw, gres, dg, db = _epilogue_backward(rec, gy, res, norm, flags, want_res=ctx.has_res and needs[4], want_gamma=needs[2],
+                                                want_beta=needs[3], amax_out=g_amax, twin=twin)
         if draw is gy:                       # no epilogue pass ran: nothing wrote the word
             g_amax = None
         # data and weight gradients
@@ -458,91 +449,96 @@ class _ConvNormActFn(torch.autograd.Function):
         return gx, gw, dg, db, gres, None, None, None, None, None
 
 
-def _epilogue_backward(raw, gy, res, scale, shift, mean, var, norm, flags, per_sample, train_stats, want_res, want_gamma, want_beta,
-                       amax_out=None, twin=None):
-    """Backward of  y = act(norm(raw) [+ res]) [+ res]  given gy: returns (draw, gres, dgamma, dbeta) on the HIP
-    reduction / apply kernels (BatchNorm / GroupNorm backward coefficients in fp64).  ``twin`` (r6) = (L1 norms of the layer's
-    filters per output channel, the words of max|x|): the apply pass also writes draw's split twin, scaled from the bound
-    max_c(|A_c| * max|gy| + |B_c| * L1_c * max|x| + |C_c|) with max|gy| taken by the reduction pass."""
-    gy = gy.contiguous()
-    am_gy = ops.amax_word(raw.device) if (twin is not None and norm is not None and ops.twin_ok(raw) and not (flags & EPI_SIGMOID)) else None
+def _save_epilogue(ctx, rec: _Epilogue, *others) -> None:
+    """An autograd function's saved tensors: the record's (y is the function's output, not needed again), then the function's own."""
+    ctx.per_sample = rec.per_sample
+    ctx.save_for_backward(rec.raw, rec.scale, rec.shift, rec.mean, rec.var, *others)
 
-    def twin_mul(coef_g, coef_raw, coef_const):
-        if am_gy is None:
-            return None
-        if coef_raw is None:               # frozen statistics: draw = A * g
-            return ops.split_scale_bound(coef_g.numel(), raw.size(1), raw.device, a=coef_g, amax_p=am_gy, b=torch.zeros_like(coef_g))
-        return ops.split_scale_bound(coef_g.numel(), raw.size(1), raw.device, a=coef_g, amax_p=am_gy, b=coef_raw, l1=twin[0], amax_x=twin[1],
-                                     cc=coef_const)
 
-    n, c = raw.shape[0], raw.shape[1]
-    s = raw[0, 0].numel()
-    dev = raw.device
-    act_flags = flags & (EPI_RELU | EPI_SIGMOID | EPI_ADD_PRE)
-    dgamma = dbeta = None
-    if norm is None:
-        coef_g = torch.ones(c, device=dev)
-        coef_raw = coef_const = None
-        per_sample = False
+def _saved_epilogue(ctx):
+    """(the record as the forward left it, the function's own saved tensors ...)."""
+    raw, scale, shift, mean, var, *others = ctx.saved_tensors
+    return (_Epilogue(None, raw, scale, shift, mean, var, ctx.per_sample), *others)
+
+
+def _backward_coefs(sums, mean, var, norm, s):
+    """The coefficients of  draw = coef_g * g + coef_raw * raw + coef_const  and (dgamma, dbeta) for the backward of ``norm`` from the
+    reduction pass's ``sums`` [N, C, 2] = [sum g, sum g * raw] per (n, c) over ``s`` elements each (fp64); ``mean`` / ``var`` the
+    forward's statistics (None: frozen BatchNorm, the running ones).  GroupNorm: [N, C] coefficients, statistics [N, groups];
+    BatchNorm: [C].  Float64 throughout, except float32 batch statistics on the GPU, which take ops.bn_backward_coefs' one launch
+    (fp64 inside, float32 results).  coef_raw / coef_const are None for frozen statistics (a plain per-channel affine), dgamma / dbeta
+    for a norm without weight."""
+    n, c = sums.shape[0], sums.shape[1]
+    if not isinstance(norm, nn.GroupNorm) and mean is not None and mean.dtype == torch.float32 and var.dtype == torch.float32:
+        # batch statistics: every coefficient in one launch, instead of ~15 per-channel tensor ops
+        gw = norm.weight.detach().float().contiguous() if norm.weight is not None else None
+        a_, b_, c_, dgamma, dbeta = ops.bn_backward_coefs(sums, mean[0].contiguous(), var[0].contiguous(), gw, float(n * s), float(norm.eps))
     else:
-        sums = ops.act_backward_reduce(raw, gy, res, scale, shift, act_flags, per_sample, amax_gy=am_gy)   # [n, c, 2] fp64
-        gam = norm.weight.detach().double() if norm.weight is not None else torch.ones(c, device=dev, dtype=torch.float64)
+        gam = norm.weight.detach().double() if norm.weight is not None else torch.ones(c, device=sums.device, dtype=torch.float64)
         if isinstance(norm, nn.GroupNorm):
             groups = norm.num_groups
             cpg = c // groups
+            over_group = lambda t: t.view(n, groups, cpg).sum(2).repeat_interleave(cpg, dim=1)      # noqa: E731
             mu = mean.double().repeat_interleave(cpg, dim=1)                       # [n, c]
             rstd = torch.rsqrt(var.double() + norm.eps).repeat_interleave(cpg, dim=1)
             sg, sgr = sums[..., 0], sums[..., 1]
             sgx = rstd * (sgr - mu * sg)                                          # sum g * xhat per (n, c)
-            p1 = (gam * sg).view(n, groups, cpg).sum(2).repeat_interleave(cpg, dim=1)
-            p2 = (gam * sgx).view(n, groups, cpg).sum(2).repeat_interleave(cpg, dim=1)
+            p1, p2 = over_group(gam * sg), over_group(gam * sgx)
             m = float(cpg * s)
             a_ = rstd * gam
             b_ = -rstd * rstd * p2 / m
             c_ = -rstd * p1 / m - b_ * mu
             dgamma, dbeta = sgx.sum(0), sg.sum(0)
         else:
-            if train_stats and mean.dtype == torch.float32 and var.dtype == torch.float32:
-                # batch statistics: every coefficient in one launch (fp64 inside), instead of ~15 per-channel tensor ops
-                gw = norm.weight.detach().float().contiguous() if norm.weight is not None else None
-                coef_g, coef_raw, coef_const, dgamma, dbeta = ops.bn_backward_coefs(
-                    sums, mean[0].contiguous(), var[0].contiguous(), gw, float(n * s), float(norm.eps))
-                if norm.weight is None:
-                    dgamma = dbeta = None
-                # the residual's gradient is g = gy * act'(v): with no activation (conv6: bn(conv) + x) it IS gy -- nothing to write
-                # (r6: the pass wrote a 736 MB copy of gy at cfg4)
-                want_g = want_res and bool(flags & EPI_ADD_PRE) and bool(flags & (EPI_RELU | EPI_SIGMOID))
-                draw, g_out = ops.act_backward_apply(raw, gy, res, scale, shift, coef_g, coef_raw, coef_const, act_flags,
-                                                     per_sample, want_g, amax=amax_out, twin_mul=twin_mul(coef_g, coef_raw, coef_const))
-                gres = (g_out if want_g else gy) if want_res else None
-                return draw, gres, (dgamma if want_gamma else None), (dbeta if want_beta else None)
             sg, sgr = sums[..., 0].sum(0), sums[..., 1].sum(0)                    # [c]
-            if train_stats:
-                mu, rstd = mean[0].double(), torch.rsqrt(var[0].double() + norm.eps)
-                sgx = rstd * (sgr - mu * sg)
+            mu, v = (mean[0], var[0]) if mean is not None else (norm.running_mean, norm.running_var)
+            mu, rstd = mu.double(), torch.rsqrt(v.double() + norm.eps)
+            dgamma, dbeta = rstd * (sgr - mu * sg), sg
+            a_, b_, c_ = gam * rstd, None, None                                   # frozen statistics: a plain per-channel affine
+            if mean is not None:
                 m = float(n * s)
-                a_ = gam * rstd
-                b_ = -gam * rstd * rstd * sgx / m
+                b_ = -gam * rstd * rstd * dgamma / m
                 c_ = -gam * rstd * sg / m - b_ * mu
-            else:   # frozen statistics: a plain per-channel affine
-                mu, rstd = norm.running_mean.double(), torch.rsqrt(norm.running_var.double() + norm.eps)
-                sgx = rstd * (sgr - mu * sg)
-                a_, b_, c_ = gam * rstd, None, None
-            dgamma, dbeta = sgx, sg
-        coef_g = a_.float().contiguous()
-        coef_raw = b_.float().contiguous() if b_ is not None else None
-        coef_const = c_.float().contiguous() if c_ is not None else None
-        if norm.weight is None:
-            dgamma = dbeta = None
+    if norm.weight is None:
+        dgamma = dbeta = None
+    return a_, b_, c_, dgamma, dbeta
+
+
+def _f32_coefs(*coefs):
+    """The coefficient vectors as act_backward_apply takes them: contiguous float32 (the identity on ops.bn_backward_coefs' results)."""
+    return tuple(None if v is None else v.float().contiguous() for v in coefs)
+
+
+def _epilogue_backward(rec: _Epilogue, gy, res, norm, flags, *, want_res, want_gamma, want_beta, amax_out=None, twin=None):
+    """Backward of  y = act(norm(raw) [+ res]) [+ res]  given gy: returns (draw, gres, dgamma, dbeta) on the HIP
+    reduction / apply kernels (BatchNorm / GroupNorm backward coefficients in fp64).  ``twin`` (r6) = (L1 norms of the layer's
+    filters per output channel, the words of max|x|): the apply pass also writes draw's split twin, scaled from the bound
+    max_c(|A_c| * max|gy| + |B_c| * L1_c * max|x| + |C_c|) with max|gy| taken by the reduction pass."""
+    raw, scale, shift, per_sample = rec.raw, rec.scale, rec.shift, rec.per_sample
+    gy = gy.contiguous()
+    c, dev = raw.shape[1], raw.device
+    act_flags = flags & (EPI_RELU | EPI_SIGMOID | EPI_ADD_PRE)
+    dgamma = dbeta = twin_mul = None
+    if norm is None:
+        coef_g, coef_raw, coef_const = torch.ones(c, device=dev), None, None
+    else:
+        am_gy = ops.amax_word(dev) if (twin is not None and ops.twin_ok(raw) and not (flags & EPI_SIGMOID)) else None
+        sums = ops.act_backward_reduce(raw, gy, res, scale, shift, act_flags, per_sample, amax_gy=am_gy)   # [n, c, 2] fp64
+        *coefs, dgamma, dbeta = _backward_coefs(sums, rec.mean, rec.var, norm, raw[0, 0].numel())
+        coef_g, coef_raw, coef_const = _f32_coefs(*coefs)
+        if am_gy is not None and coef_raw is None:          # frozen statistics: draw = A * g
+            twin_mul = ops.split_scale_bound(coef_g.numel(), c, dev, a=coef_g, amax_p=am_gy, b=torch.zeros_like(coef_g))
+        elif am_gy is not None:
+            twin_mul = ops.split_scale_bound(coef_g.numel(), c, dev, a=coef_g, amax_p=am_gy, b=coef_raw, l1=twin[0], amax_x=twin[1], cc=coef_const)
+    # the residual's gradient is g = gy * act'(v): with no activation (conv6: bn(conv) + x) it IS gy -- nothing to write
+    # (r6: the pass wrote a 736 MB copy of gy at cfg4)
     want_g = want_res and bool(flags & EPI_ADD_PRE) and bool(flags & (EPI_RELU | EPI_SIGMOID))
     if norm is None and not act_flags:
         draw, g_out = gy, gy
     else:
-        draw, g_out = ops.act_backward_apply(raw, gy, res, scale, shift, coef_g, coef_raw, coef_const, act_flags,
-                                             per_sample, want_g, amax=amax_out, twin_mul=twin_mul(coef_g, coef_raw, coef_const))
-    gres = None
-    if want_res:
-        gres = g_out if want_g else gy
+        draw, g_out = ops.act_backward_apply(raw, gy, res, scale, shift, coef_g, coef_raw, coef_const, act_flags, per_sample, want_g,
+                                             amax=amax_out, twin_mul=twin_mul)
+    gres = (g_out if want_g else gy) if want_res else None
     dg = dgamma.float() if (dgamma is not None and want_gamma) else None
     db = dbeta.float() if (dbeta is not None and want_beta) else None
     return draw, gres, dg, db
@@ -564,6 +560,12 @@ def _first_conv_train_cache(conv, weight, c):
     return fac
 
 
+def _left_planes(fac, left):
+    """(the left feature stacked 3 deep, the depth-class planes of the left half's convolution over it)."""
+    left3 = left.detach().unsqueeze(2).expand(-1, -1, 3, -1, -1).contiguous()
+    return left3, fac["fl"](left3)
+
+
 class _FactoredFirstConvFn(torch.autograd.Function):
     """Differentiable first layer of the global stack over a CONCAT cost volume that is never built:
         y = act(norm(conv3d(build_cost_volume(left, right, shift, 1), W)))          (k3, stride 1, 2C -> Cout)
@@ -581,8 +583,7 @@ class _FactoredFirstConvFn(torch.autograd.Function):
         if "fr" not in fac:
             wr = weight.detach()[:, c:].contiguous()
             fac.update(fr=ops.Conv3dLayer(wr, 3, 1, 1, 1, False), br=ops.Conv3dLayer(_flip3d(wr), 3, 1, 1, 1, False))
-        left3 = left.detach().unsqueeze(2).expand(-1, -1, 3, -1, -1).contiguous()
-        planes = fac["fl"](left3)
+        left3, planes = _left_planes(fac, left)
         rd = right.detach()
         if commuted and shift.dtype == torch.float32 and rd.size(3) % 4 == 0 and rd.size(3) <= 2048:
             # forward: warp AFTER the convolution (csrc/sheared_conv.hip, any shift array): three depth-1 convolutions of the
@@ -612,20 +613,23 @@ class _FactoredFirstConvFn(torch.autograd.Function):
             raw = fac["fr"](vol_r, None, None, None, 0, None, depth_planes=planes)
             del vol_r
             ctx.commuted_bwd = False
-        y, scale, shf, mean, var, per_sample = _norm_from_raw(raw, norm, plan, None, flags)
-        ctx.conv, ctx.norm, ctx.flags, ctx.per_sample, ctx.train_stats = conv, norm, flags, per_sample, mean is not None
-        ctx.save_for_backward(left3, right.detach(), shift, raw, scale, shf, mean, var)
-        return y
+        if ctx.commuted_bwd and ctx.needs_input_grad[1] and "ba" not in fac:
+            # dRight[c][y][j] = sum Wt[co][c][kd][kh][kw] a[kd][kw][co][y - kh + 1][j]: a depth-1 k3 layer over the backward's nine sums
+            wr = weight.detach()[:, c:]                                           # [Cout, C, kd, kh, kw]
+            wd = torch.zeros((c, 9 * wr.size(0), 3, 3), dtype=wr.dtype, device=wr.device)
+            wd[:, :, :, 1] = wr.permute(1, 2, 4, 0, 3).flip(4).reshape(c, 9 * wr.size(0), 3)
+            fac["ba"] = ops.Conv3dLayer(wd, 3, 1, 1, 1, False, planar=True)
+        rec = _norm_over_raw(raw, norm, plan, None, flags)
+        ctx.fac, ctx.norm, ctx.flags = fac, norm, flags
+        _save_epilogue(ctx, rec, left3, rd, shift)
+        return rec.y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        left3, right, shift, raw, scale, shf, mean, var = ctx.saved_tensors
-        conv, norm, flags = ctx.conv, ctx.norm, ctx.flags
-        needs = ctx.needs_input_grad
-        draw, _, dg, db = _epilogue_backward(raw, gy, None, scale, shf, mean, var, norm, flags, ctx.per_sample, ctx.train_stats,
-                                             False, needs[4], needs[5])
-        fac = conv.__dict__["_snvc_factored_train"]
+        rec, left3, right, shift = _saved_epilogue(ctx)
+        fac, needs = ctx.fac, ctx.needs_input_grad      # the layers this graph's forward ran on, whatever the weights are by now
+        draw, _, dg, db = _epilogue_backward(rec, gy, None, ctx.norm, ctx.flags, want_res=False, want_gamma=needs[4], want_beta=needs[5])
         g_left = g_right = gw = None
         if ctx.commuted_bwd and (needs[1] or needs[3]):
             # one pass over draw: its nine warped-back, tap-shifted sums a[kd][kw] (and the left half's depth-class sums);
@@ -638,11 +642,6 @@ class _FactoredFirstConvFn(torch.autograd.Function):
                 gw_r = g9[:, :, 1, :, 1].reshape(3, 3, cout, c, 3).permute(2, 3, 0, 4, 1)      # [Cout, C, kd, kh, kw]
                 gw = torch.cat([ops.conv3d_wgrad(left3, dplanes, 3, 1, 1, 1), gw_r], dim=1)
             if needs[1]:
-                if "ba" not in fac:     # dRight[c][y][j] = sum Wt[co][c][kd][kh][kw] a[kd][kw][co][y - kh + 1][j]: a depth-1 k3 layer
-                    wr = conv.weight.detach()[:, c:]                              # [Cout, C, kd, kh, kw]
-                    wd = torch.zeros((c, 9 * cout, 3, 3), dtype=wr.dtype, device=wr.device)
-                    wd[:, :, :, 1] = wr.permute(1, 2, 4, 0, 3).flip(4).reshape(c, 9 * cout, 3)
-                    fac["ba"] = ops.Conv3dLayer(wd, 3, 1, 1, 1, False, planar=True)
                 g_right = fac["ba"](a5).squeeze(2)
             if needs[0]:
                 g_left = fac["bl"](dplanes).sum(dim=2)
@@ -727,6 +726,20 @@ def _bn_track(norm, mean, var, cnt):
             norm.running_var.lerp_(var[0] * (cnt / max(cnt - 1, 1)), m)
 
 
+def _sheared_forward_parts(conv, weight, left, right, q, m0, depth):
+    """What both sheared functions' forwards start from: (the layer's training cache, left3, planes, the detached right feature,
+    G, G' = the 3 x 7 layers over the upsampled right feature and over its last-column window, off, off_col)."""
+    c = left.size(1)
+    fac = _first_conv_train_cache(conv, weight, c)
+    fwd = _sheared_train_layers(fac, weight, c, q)[0]
+    off, wu, off_col, wu_col = sheared_geometry(q, m0, depth, left.size(3))
+    left3, planes = _left_planes(fac, left)
+    rd = right.detach()
+    g = fwd[0](ops.sheared_upsample(rd, q, wu, off).unsqueeze(2)).squeeze(2)
+    gcol = fwd[1](ops.sheared_upsample(rd, q, wu_col, off_col).unsqueeze(2)).squeeze(2)
+    return fac, left3, planes, rd, g, gcol, off, off_col
+
+
 class _ShearedFirstConvFn(torch.autograd.Function):
     """``_FactoredFirstConvFn`` for uniformly spaced disparity planes, shift[n][d] = (m0 + d) / q with q in {1, 2}: the warped
     half of the volume is a shear of ONE image Rq and the 3D convolution over it a 2D 3 x 7 convolution G evaluated along the
@@ -740,35 +753,22 @@ class _ShearedFirstConvFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, left, right, weight, gamma, beta, conv, norm, flags, plan, q, m0, depth):
-        c = left.size(1)
-        fac = _first_conv_train_cache(conv, weight, c)
-        fwd = _sheared_train_layers(fac, weight, c, q)[0]
-        n, h, w = left.size(0), left.size(2), left.size(3)
-        off, wu, off_col, wu_col = sheared_geometry(q, m0, depth, w)
-        left3 = left.detach().unsqueeze(2).expand(-1, -1, 3, -1, -1).contiguous()
-        planes = fac["fl"](left3)
-        rd = right.detach()
-        g = fwd[0](ops.sheared_upsample(rd, q, wu, off).unsqueeze(2)).squeeze(2)
-        gcol = fwd[1](ops.sheared_upsample(rd, q, wu_col, off_col).unsqueeze(2)).squeeze(2)
-        raw = torch.empty((n, weight.size(0), depth, h, w), dtype=torch.float32, device=left.device)
+        fac, left3, planes, rd, g, gcol, off, off_col = _sheared_forward_parts(conv, weight, left, right, q, m0, depth)
+        raw = torch.empty((left.size(0), weight.size(0), depth, left.size(2), left.size(3)), dtype=torch.float32, device=left.device)
         ops.sheared_expand(g, gcol, planes, None, None, raw, q, m0, off, off_col, 0)
         del g, gcol
-        y, scale, shf, mean, var, per_sample = _norm_from_raw(raw, norm, plan, None, flags)
-        ctx.conv, ctx.norm, ctx.flags, ctx.per_sample, ctx.train_stats = conv, norm, flags, per_sample, mean is not None
-        ctx.q, ctx.m0 = q, m0
-        ctx.save_for_backward(left3, rd, raw, scale, shf, mean, var)
+        rec = _norm_over_raw(raw, norm, plan, None, flags)
+        ctx.fac, ctx.norm, ctx.flags, ctx.q, ctx.m0 = fac, norm, flags, q, m0
+        _save_epilogue(ctx, rec, left3, rd)
         _ROUTES["sheared_first_conv_train"] += 1
-        return y
+        return rec.y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        left3, right, raw, scale, shf, mean, var = ctx.saved_tensors
-        conv, norm, flags, q, m0 = ctx.conv, ctx.norm, ctx.flags, ctx.q, ctx.m0
-        needs = ctx.needs_input_grad
-        draw, _, dg, db = _epilogue_backward(raw, gy, None, scale, shf, mean, var, norm, flags, ctx.per_sample, ctx.train_stats,
-                                             False, needs[3], needs[4])
-        fac = conv.__dict__["_snvc_factored_train"]
+        rec, left3, right = _saved_epilogue(ctx)
+        fac, q, m0, needs = ctx.fac, ctx.q, ctx.m0, ctx.needs_input_grad      # fac: the layers this graph's forward ran on
+        draw, _, dg, db = _epilogue_backward(rec, gy, None, ctx.norm, ctx.flags, want_res=False, want_gamma=needs[3], want_beta=needs[4])
         depth, w = draw.size(2), draw.size(4)
         off, wu, off_col, wu_col = sheared_geometry(q, m0, depth, w)
         dplanes = ops.depth_class_sums(draw)                                      # [N,Cout,3,H,W]
@@ -837,16 +837,8 @@ class _ShearedFirstConvBNFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, left, right, weight, gamma, beta, conv, norm, plan, q, m0, depth):
-        c = left.size(1)
-        fac = _first_conv_train_cache(conv, weight, c)
-        fwd = _sheared_train_layers(fac, weight, c, q)[0]
+        fac, left3, planes, rd, g, gcol, off, off_col = _sheared_forward_parts(conv, weight, left, right, q, m0, depth)
         n, h, w = left.size(0), left.size(2), left.size(3)
-        off, wu, off_col, wu_col = sheared_geometry(q, m0, depth, w)
-        left3 = left.detach().unsqueeze(2).expand(-1, -1, 3, -1, -1).contiguous()
-        planes = fac["fl"](left3)
-        rd = right.detach()
-        g = fwd[0](ops.sheared_upsample(rd, q, wu, off).unsqueeze(2)).squeeze(2)
-        gcol = fwd[1](ops.sheared_upsample(rd, q, wu_col, off_col).unsqueeze(2)).squeeze(2)
         shape = (n, weight.size(0), depth, h, w)
         gam = gamma.detach() if gamma is not None else None
         bet = beta.detach() if beta is not None else None
@@ -866,7 +858,7 @@ class _ShearedFirstConvBNFn(torch.autograd.Function):
             pair = ops.twin_empty(y)
             ops.sheared_expand_split(g, gcol, planes, (scale * mul).contiguous(), (shift * mul).contiguous(), pair, q, m0, off, off_col, EPI_RELU)
             ops.tag_twin(y, pair, mul)
-        ctx.conv, ctx.norm, ctx.q, ctx.m0 = conv, norm, q, m0
+        ctx.fac, ctx.norm, ctx.q, ctx.m0 = fac, norm, q, m0
         # gamma is saved as the autograd input it is: an in-place update between forward and backward (an interleaved
         # optimizer step, an EMA swap) then trips autograd's version check instead of pairing a new gamma with old scale / shift
         ctx.save_for_backward(left3, rd, g, gcol, planes, scale, shift, mean, var, gamma)
@@ -878,7 +870,7 @@ class _ShearedFirstConvBNFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
         left3, right, g, gcol, planes, scale, shift, mean, var, gamma = ctx.saved_tensors
-        conv, norm, q, m0 = ctx.conv, ctx.norm, ctx.q, ctx.m0
+        norm, q, m0 = ctx.norm, ctx.q, ctx.m0
         needs = ctx.needs_input_grad
         gy = gy.contiguous()
         n, c, depth, h, w = gy.shape
@@ -896,8 +888,7 @@ class _ShearedFirstConvBNFn(torch.autograd.Function):
         d_g, d_gcol = combine(line, cnt_line), combine(lastc, cnt_col)
         pc = lambda t: t.view(1, c, 1, 1, 1)                                       # noqa: E731  [N,C,3,H,W] layout
         dplanes = pc(a_) * colsum[0] + pc(b_) * colsum[1] + pc(c_) * cnt_cls.view(1, 1, 3, 1, 1)
-        fac = conv.__dict__["_snvc_factored_train"]
-        g_left, g_right, gw = _sheared_backward_tail(fac, q, m0, depth, w, left3, right, d_g, d_gcol, dplanes.contiguous(),
+        g_left, g_right, gw = _sheared_backward_tail(ctx.fac, q, m0, depth, w, left3, right, d_g, d_gcol, dplanes.contiguous(),
                                                      needs[0], needs[1], needs[2])
         return g_left, g_right, gw, (dgamma if needs[3] else None), (dbeta if needs[4] else None), None, None, None, None, None, None
 
@@ -993,7 +984,7 @@ def fused_conv3d(conv: nn.Module, norm: Optional[nn.Module], x: torch.Tensor, *,
             y, hy = layer(x, scale, bias, residual, flags, out, side_head=side_head.weight)
             _ROUTES["side_head" if hy is not None else "side_head_separate"] += 1
         else:
-            y, hy = _norm_forward(layer, norm, plan, x, residual, flags, out, False)[0], None
+            y, hy = _norm_forward(layer, norm, plan, x, residual, flags, out, False).y, None
         return y, (hy if hy is not None else side_head(y))
     if head is not None:
         fusable = (out is None and not torch.is_grad_enabled() and _is_channel_head(head, layer.cout) and _is_frozen_norm(norm))
@@ -1009,8 +1000,8 @@ def fused_conv3d(conv: nn.Module, norm: Optional[nn.Module], x: torch.Tensor, *,
             y = ops.conv3d_forward_head(layer, x, scale, bias, residual, flags, head.weight)
             if y is not None:
                 return y
-        return head(_norm_forward(layer, norm, plan, x, residual, flags, out, False)[0])
-    return _norm_forward(layer, norm, plan, x, residual, flags, out, False)[0]
+        return head(_norm_forward(layer, norm, plan, x, residual, flags, out, False).y)
+    return _norm_forward(layer, norm, plan, x, residual, flags, out, False).y
 
 
 def fused_conv3d_avgpool_d4(conv: nn.Module, norm: Optional[nn.Module], x: torch.Tensor, *, relu=False) -> torch.Tensor:
@@ -1350,23 +1341,23 @@ class _Conv2dNormActFn(torch.autograd.Function):
             if norm is not None:
                 raise NotImplementedError("a 2D layer with both a conv bias and a norm is not in the neck")
             scale, shift = torch.ones_like(cbias.detach()), cbias.detach().float().contiguous()
-            y, mean, var, per_sample = ops.affine_act(raw, scale, shift, res5, flags), None, None, False
+            rec = _Epilogue(ops.affine_act(raw, scale, shift, res5, flags), raw, scale, shift, None, None, False)
         else:
-            y, scale, shift, mean, var, per_sample = _norm_from_raw(raw, norm, plan, res5, flags)
-        ctx.conv, ctx.norm, ctx.flags, ctx.plan, ctx.kind, ctx.per_sample = conv, norm, flags, plan, kind, per_sample
-        ctx.has_res, ctx.train_stats, ctx.has_bias = res5 is not None, mean is not None, cbias is not None
-        ctx.save_for_backward(x5, raw, scale, shift, mean, var, res5 if (res5 is not None and (flags & EPI_ADD_PRE)) else None)
+            rec = _norm_over_raw(raw, norm, plan, res5, flags)
+        ctx.conv, ctx.norm, ctx.flags, ctx.plan, ctx.kind = conv, norm, flags, plan, kind
+        ctx.has_res, ctx.has_bias = res5 is not None, cbias is not None
+        _save_epilogue(ctx, rec, x5, res5 if (res5 is not None and (flags & EPI_ADD_PRE)) else None)
         _ROUTES["neck2d_hip_train"] += 1
-        return y
+        return rec.y
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gy):
-        x5, raw, scale, shift, mean, var, res = ctx.saved_tensors
+        rec, x5, res = _saved_epilogue(ctx)
         conv, norm, flags, plan, kind = ctx.conv, ctx.norm, ctx.flags, ctx.plan, ctx.kind
         needs = ctx.needs_input_grad
-        draw, gres, dg, db = _epilogue_backward(raw, gy, res, scale, shift, mean, var, norm, flags, ctx.per_sample, ctx.train_stats,
-                                                ctx.has_res and needs[5], needs[3], needs[4])
+        draw, gres, dg, db = _epilogue_backward(rec, gy, res, norm, flags, want_res=ctx.has_res and needs[5], want_gamma=needs[3],
+                                                want_beta=needs[4])
         gb = draw.sum(dim=(0, 2, 3, 4)) if (ctx.has_bias and needs[2]) else None
         w = conv.weight.detach()
 

@@ -149,7 +149,7 @@ def bn_backward_coefs_ref(sums, mean, var, gamma, count, eps):
 
 
 def gn_backward_coefs_ref(sums, mean, var, gamma, groups, count, eps):
-    """The GroupNorm backward coefficients, the algebra of snvc_amd/models/submodule.py::_epilogue_backward restated: statistics per
+    """The GroupNorm backward coefficients, the algebra of snvc_amd/models/submodule.py::_backward_coefs restated: statistics per
     (n, group) over ``count`` = cpg * S elements, sums per (n, c):
         sgx = rstd * (sgr - mu * sg);  p1 = sum_{c in group} gamma sg;  p2 = sum_{c in group} gamma sgx;
         A = rstd * gamma;  B = -rstd^2 * p2 / count;  Cc = -rstd * p1 / count - B * mu   (all [N, C]);
@@ -173,6 +173,21 @@ def gn_backward_coefs_ref(sums, mean, var, gamma, groups, count, eps):
     cc, cc_m = -rstd * p1 / count - b * mu, rstd * p1_m / count + b_m * np.abs(mu)
     return (dict(coef_g=a, coef_raw=b, coef_const=cc, dgamma=sgx.sum(0), dbeta=sg.sum(0)),
             dict(coef_g=np.abs(a), coef_raw=b_m, coef_const=cc_m, dgamma=sgx_m.sum(0), dbeta=np.abs(sg).sum(0)))
+
+
+def frozen_bn_backward_coefs_ref(sums, running_mean, running_var, gamma, eps):
+    """Eval-mode (frozen) BatchNorm backward: the statistics are constants, so draw = A * g with A = gamma * rstd of the RUNNING
+    statistics and B = Cc = None; dgamma = rstd * (sum g raw - mean * sum g), dbeta = sum g.  Returns (values, magnitudes) as
+    bn_backward_coefs_ref."""
+    sums, mu, var = f64(sums), f64(running_mean).reshape(-1), f64(running_var).reshape(-1)
+    c = mu.shape[0]
+    gam = np.ones(c) if gamma is None else f64(gamma).reshape(c)
+    rstd = 1.0 / np.sqrt(var + float(eps))
+    sg, sgr = sums[..., 0].sum(0), sums[..., 1].sum(0)
+    sg_m, sgr_m = np.abs(sums[..., 0]).sum(0), np.abs(sums[..., 1]).sum(0)
+    a = gam * rstd
+    return (dict(coef_g=a, coef_raw=None, coef_const=None, dgamma=rstd * (sgr - mu * sg), dbeta=sg),
+            dict(coef_g=np.abs(a), coef_raw=None, coef_const=None, dgamma=rstd * (sgr_m + np.abs(mu) * sg_m), dbeta=sg_m))
 
 
 def bn_track_ref(running_mean, running_var, num_batches_tracked, mean, var, count, momentum):

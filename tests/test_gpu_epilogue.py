@@ -434,8 +434,9 @@ def _torch_autograd(x, res, gy, gamma, beta, groups, per_sample, flags):
 @pytest.mark.parametrize("norm", ["batchnorm", "groupnorm"])
 @pytest.mark.parametrize("case", [GROUPS, "slice4_scalar", "slice4_vector"], ids=_id)
 def test_chain_vs_float64_autograd(case, norm, flags):
-    """norm_stats -> affine_act, then act_backward_reduce -> coefficients -> act_backward_apply (BatchNorm: snvc_bn_backward_coefs;
-    GroupNorm: submodule._epilogue_backward, cpg = 3 / 3 / 2), against float64 torch autograd of norm -> [+res] -> relu -> [+res].
+    """norm_stats -> affine_act, then act_backward_reduce -> coefficients -> act_backward_apply (BatchNorm: snvc_bn_backward_coefs by
+    hand, and the same data through submodule._epilogue_backward, bit-equal to the hand chain; GroupNorm: submodule._epilogue_backward,
+    cpg = 3 / 3 / 2), against float64 torch autograd of norm -> [+res] -> relu -> [+res].
       y:     3 u M as _check_affine, plus |x| |scale - scale64| + |shift - shift64| for the float32 scale / shift the pass was handed
              (exact: the epilogue is 1-Lipschitz in v); the statistics themselves are held to _check_norm_stats;
       draw:  3 u M as _check_backward, plus the coefficients' own error: each of A, B, Cc is float64 algebra on float32 mean and var
@@ -471,14 +472,24 @@ def test_chain_vs_float64_autograd(case, norm, flags):
         gn = torch.nn.GroupNorm(groups, c, eps=EPS).to(dev())
         with torch.no_grad():
             gn.weight.copy_(_t(gamma)); gn.bias.copy_(_t(beta))
-        draw, gres, dgamma, dbeta = S._epilogue_backward(x_dev, gy_dev, res_dev, scale, shift, mean, var, gn, flags, True, True,
-                                                          res_dev is not None, True, True)
+        rec = S._Epilogue(y, x_dev, scale, shift, mean, var, True)
+        draw, gres, dgamma, dbeta = S._epilogue_backward(rec, gy_dev, res_dev, gn, flags, want_res=res_dev is not None, want_gamma=True,
+                                                          want_beta=True)
     else:
         act_flags = flags & (RELU | PRE)
         sums = ops.act_backward_reduce(x_dev, gy_dev, res_dev, scale, shift, act_flags, False)
         cg, cr, cc, dgamma, dbeta = ops.bn_backward_coefs(sums, mean[0].contiguous(), var[0].contiguous(), _t(gamma), float(n * int(np.prod(sp))), EPS)
         draw, g_out = ops.act_backward_apply(x_dev, gy_dev, res_dev, scale, shift, cg, cr, cc, act_flags, False, bool(flags & PRE))
         gres = g_out if flags & PRE else (gy_dev if flags & POST else None)
+        # the same three launches through the product's own entry, train-mode BatchNorm3d: the same bits
+        bn = torch.nn.BatchNorm3d(c, eps=EPS).to(dev()).train()
+        with torch.no_grad():
+            bn.weight.copy_(_t(gamma)); bn.bias.copy_(_t(beta))
+        rec = S._Epilogue(y, x_dev, scale, shift, mean, var, False)
+        got = S._epilogue_backward(rec, gy_dev, res_dev, bn, flags, want_res=res_dev is not None, want_gamma=True, want_beta=True)
+        for name, a, b in zip(("draw", "residual gradient", "dgamma", "dbeta"), got, (draw, gres, dgamma, dbeta)):
+            assert (a is None) == (b is None), what + " " + name
+            assert a is None or (a.dtype == b.dtype and np.array_equal(_np(a), _np(b))), what + " _epilogue_backward " + name
     bc = (lambda a: a[:, :, None, None, None]) if per_sample else (lambda a: a[None, :, None, None, None])
     coef_err = 2.0 ** -21 * (bc(mags["coef_g"]) * np.abs(ref["g"]) + bc(mags["coef_raw"]) * np.abs(ER.f64(x)) + bc(mags["coef_const"]))
     _within(_np(draw), dx64, 3 * U * ref["m_draw"] + coef_err, what + " draw")

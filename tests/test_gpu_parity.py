@@ -1649,6 +1649,38 @@ def test_training_step_sheared_first_conv_vs_torch_autograd(q, m0, fused_bn):
         check(gp_o[k].numpy(), gp_g[k].numpy(), 1e-3, f"d {k} (vs general)")
 
 
+@pytest.mark.parametrize("fused_bn", [True, False])
+def test_first_layer_backward_runs_on_the_layers_of_its_own_forward(fused_bn):
+    """Another forward with updated first-layer weights (and another plane spacing) between a graph's forward and its backward replaces
+    the layer's training cache (_first_conv_train_cache).  The first graph's backward still runs on the layers its own forward built:
+    the gradients of the undisturbed step, bit for bit (the same launches on the same tensors; the weight is no saved tensor, so
+    autograd's version check does not see the update)."""
+    from snvc_amd.models.stereo_volume import GlobalStack
+    r = np.random.default_rng(191)
+    C, H, W, D = 32, 8, 40, 12
+    model = seeded(GlobalStack(C), 182).to(dev()).train()
+    L, R = (torch.from_numpy(r.standard_normal((2, C, H, W)).astype(np.float32)).to(dev()).requires_grad_() for _ in range(2))
+    half = torch.from_numpy(np.tile((np.arange(D) / 2).astype(np.float32)[None], (2, 1))).to(dev())
+    whole = torch.from_numpy(np.tile(np.arange(D).astype(np.float32)[None], (2, 1))).to(dev())
+    w1 = model.conv1[0][0].weight
+
+    def step(disturb):
+        for t in list(model.parameters()) + [L, R]:
+            t.grad = None
+        loss = model.forward_pair(L, R, half, 1, fused_bn=fused_bn).pow(2).mean()
+        if disturb:
+            with torch.no_grad():
+                w1.mul_(1.25)
+            model.forward_pair(L, R, whole, 1, fused_bn=fused_bn)            # under autograd: rebuilds the cache for the new weight, q = 1
+        loss.backward()
+        return [L.grad.clone(), R.grad.clone()] + [p.grad.clone() for p in model.conv1.parameters()]
+    step(False)                                                                 # from the second step on the layers' operands come as twins
+    want, got = step(False), step(True)
+    assert len(want) == len(got) == 5
+    for a, b in zip(got, want):
+        assert torch.equal(a, b)
+
+
 @pytest.mark.parametrize("q,m0", [(2, 0), (2, 5), (1, 1)])
 def test_sheared_fused_batchnorm_entry_points_vs_numpy(q, m0):
     """snvc_sheared_expand_stats against the statistics of the expanded tensor, and snvc_sheared_backward_reduce against the
