@@ -6,6 +6,7 @@
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
+#include <mutex>
 
 #include "snvc_hip.h"
 
@@ -18,8 +19,8 @@ inline int fail(int code, const char *msg) {
     return code;
 }
 
-// Set by allow_large_lds when the attribute call failed (the launch that follows is skipped by its caller and
-// check_launch reports the failure, message already recorded by set_error).
+// Set by launch_lds when the attribute call failed (the launch is skipped and the caller's check_launch reports the
+// failure, message already recorded by set_error).
 inline thread_local bool g_launch_aborted = false;
 
 // Called after every launch: hipGetLastError is a host-side query (no device sync).
@@ -39,22 +40,42 @@ inline int check_launch(const char *what) {
 
 inline hipStream_t as_stream(void *s) { return reinterpret_cast<hipStream_t>(s); }
 
-// Kernels that need more than 48 KB of dynamic LDS must say so once per device (one process may drive several,
-// from several host threads: nn.DataParallel replicas).  `done_mask` has one bit per device; the bit is set only
-// after the attribute call succeeded, so a racing thread at worst repeats the (idempotent) call.
-inline bool allow_large_lds(const void *func, int bytes, std::atomic<unsigned> &done_mask) {
-    if (bytes <= 48 * 1024) return true;
+namespace detail {
+inline std::mutex g_lds_raise_mutex;
+
+// Kernels that need more than 48 KB of dynamic LDS must say so per device (one process may drive several, from several
+// host threads: nn.DataParallel replicas).  `granted` holds the bytes last granted on each device, written only after the
+// attribute call succeeded; a call that needs more raises the grant under the mutex, so that two threads raising at once
+// cannot leave the attribute at the smaller size while the record holds the larger.
+inline bool grant_lds(const void *func, int bytes, std::atomic<int> (&granted)[32]) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 32) dev = 0;
-    if (done_mask.load(std::memory_order_acquire) & (1u << dev)) return true;
+    if (granted[dev].load(std::memory_order_acquire) >= bytes) return true;
+    std::lock_guard<std::mutex> lock(g_lds_raise_mutex);
+    if (granted[dev].load(std::memory_order_relaxed) >= bytes) return true;
     const hipError_t e = hipFuncSetAttribute(func, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
     if (e != hipSuccess) {
         set_error("hipFuncSetAttribute(MaxDynamicSharedMemorySize, %d): %s", bytes, hipGetErrorString(e));
         g_launch_aborted = true;
         return false;
     }
-    done_mask.fetch_or(1u << dev, std::memory_order_release);
+    granted[dev].store(bytes, std::memory_order_release);
     return true;
+}
+}  // namespace detail
+
+// Launches Kernel with `bytes` of dynamic LDS.  The grant record is per kernel (one instantiation each) and per device.
+template <auto Kernel, class... Args>
+void launch_lds(dim3 grid, dim3 block, size_t bytes, hipStream_t st, const Args &...args) {
+    static std::atomic<int> granted[32] = {};
+    if (bytes > 48 * 1024 && !detail::grant_lds(reinterpret_cast<const void *>(Kernel), (int)bytes, granted)) return;
+    Kernel<<<grid, block, bytes, st>>>(args...);
+}
+
+// True when every pointer is a multiple of n bytes (n a power of two; NULL counts as aligned).
+template <class... T>
+inline bool aligned(uintptr_t n, const T *...ptrs) {
+    return ((reinterpret_cast<uintptr_t>(ptrs) | ...) & (n - 1)) == 0;
 }
 
 // Compute units of the current device, rounded down to whole XCD octets (persistent-grid sizing).

@@ -2209,19 +2209,10 @@ struct Plan {
     int MI, KC, TD, TH;  // tile choice
     int groups, nchunks;
     int tiles_d, tiles_h, tiles_w;
-    int kind;  // index into the instantiation table
-};
-
-enum Kind {
-    K1_M1, K1_M2,
-    K3_M1, K3_M2,
-    K3S2_M1, K3S2_M2,
-    K5_M1, K5_M2,
-    K5D2_M1, K5D2_M2,
-    K7_M1, K7_M2,
-    DC_M1, DC_M2, DCP_M1,
-    P1_M1S, P1S2_M1S, P3_M1S, P3S2_M1S, P7_M1S, P3D2_M1S,                // depth-1 (2D) layers, 1 x 4 x 32 tiles
-    KIND_NONE
+    // the direct / transposed MFMA kernel of the configuration; vec8: the rows are 8-byte aligned (the transposed forms have a
+    // configuration for them)
+    void (*launch)(ConvArgs &a, bool vec8, dim3 grid, hipStream_t st);
+    bool dc_m1;  // the single-group ConvTranspose3d form (CfgDCM1): the one that carries the fused head and the statistics epilogue
 };
 
 //                       KS S  D  MI TD TH KC  DB   OCC KDG
@@ -2277,8 +2268,51 @@ using CfgDCM2v8 = DeconvCfg<2, 2, 4, 4, 2>;
 using CfgDCP    = DeconvCfg<1, 1, 8, 4>;
 using CfgDCPv8  = DeconvCfg<1, 1, 8, 4, 2>;
 
+// FAST: also build the fast-epilogue variants of this configuration (the ones on a measured path)
+template <class Cfg, bool FAST>
+void launch_conv(ConvArgs &a, bool, dim3 grid, hipStream_t st) {
+    if constexpr (FAST) {
+        if (a.fast_epi && !a.plane) {
+            if (a.res) launch_lds<conv3d_mfma_kernel<Cfg, 2>>(grid, 256, Cfg::LDS_BYTES, st, a);
+            else launch_lds<conv3d_mfma_kernel<Cfg, 1>>(grid, 256, Cfg::LDS_BYTES, st, a);
+            return;
+        }
+    }
+    launch_lds<conv3d_mfma_kernel<Cfg, 0>>(grid, 256, Cfg::LDS_BYTES, st, a);
+}
+
 template <class Cfg>
-constexpr Plan plan_of(int kind) { return Plan{Cfg::MI, Cfg::KC, Cfg::TD, Cfg::TH, 0, 0, 0, 0, 0, kind}; }
+void launch_deconv(const ConvArgs &a, dim3 grid, hipStream_t st) {
+    constexpr int BYTES = Cfg::LDS_BYTES;
+    // the pair exchange of the fast epilogue needs an even input width (both lanes of a pair in range)
+    if (a.stats) {    // validated by conv3d_forward_impl: fast epilogue conditions, one channel group per workgroup, no addends
+        if constexpr (Cfg::MI == 1) launch_lds<deconv3d_mfma_kernel<Cfg, 5>>(grid, 256, BYTES, st, a);
+    } else if (a.head_w) {   // validated by snvc_conv3d_forward_head: fast epilogue conditions hold, one channel group
+        if constexpr (Cfg::MI == 1) {
+            if (a.res) launch_lds<deconv3d_mfma_kernel<Cfg, 4>>(grid, 256, BYTES, st, a);
+            else launch_lds<deconv3d_mfma_kernel<Cfg, 3>>(grid, 256, BYTES, st, a);
+        }
+    } else if (a.fast_epi && a.Win % 2 == 0) {
+        if (a.res) launch_lds<deconv3d_mfma_kernel<Cfg, 2>>(grid, 256, BYTES, st, a);
+        else launch_lds<deconv3d_mfma_kernel<Cfg, 1>>(grid, 256, BYTES, st, a);
+    } else {
+        launch_lds<deconv3d_mfma_kernel<Cfg, 0>>(grid, 256, BYTES, st, a);
+    }
+}
+
+// Cfg on 16-byte rows (or unaligned ones), CfgV8 on rows that are only 8-byte aligned
+template <class Cfg, class CfgV8>
+void launch_deconv_rows(ConvArgs &a, bool vec8, dim3 grid, hipStream_t st) {
+    if (!a.vec && vec8) { a.vec = 1; launch_deconv<CfgV8>(a, grid, st); }
+    else launch_deconv<Cfg>(a, grid, st);
+}
+
+template <class Cfg, bool FAST = false>
+constexpr Plan plan_of() { return Plan{Cfg::MI, Cfg::KC, Cfg::TD, Cfg::TH, 0, 0, 0, 0, 0, &launch_conv<Cfg, FAST>, false}; }
+template <class Cfg, class CfgV8>
+constexpr Plan deconv_plan_of(bool dc_m1 = false) {
+    return Plan{Cfg::MI, Cfg::KC, Cfg::TD, Cfg::TH, 0, 0, 0, 0, 0, &launch_deconv_rows<Cfg, CfgV8>, dc_m1};
+}
 
 int make_plan(const snvc_conv3d_desc &d, Plan &p) {
     if (d.N < 0 || d.Cin <= 0 || d.Cout <= 0 || d.Din <= 0 || d.Hin <= 0 || d.Win <= 0)
@@ -2290,14 +2324,14 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
         if (d.ksize_d == 1) {   // depth-1 form: [N,C,1,H,W] -> [N,C,1,2H,2W]; the weight is the 2D kernel on the kd = 1 plane of a 3x3x3 one
             if (d.Din != 1 || d.Dout != 1 || d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win || (d.ksize_h != 0 && d.ksize_h != 3))
                 return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d: a depth-1 transposed layer maps [1,H,W] to [1,2H,2W]");
-            p = plan_of<CfgDCP>(DCP_M1);
+            p = deconv_plan_of<CfgDCP, CfgDCPv8>();
             p.tiles_d = 1; p.tiles_h = ceil_div(d.Hin, p.TH); p.tiles_w = ceil_div(d.Win, 32);
         } else {
         if (d.Dout != 2 * d.Din || d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win)
             return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d: transposed output must be 2x the input");
         // whole 32-channel groups run the single-group form (128 VGPRs: four workgroups per CU); the 64-channel
         // form only remains for channel counts that are not multiples of 32
-        p = (wide && d.Cout % 32 != 0) ? plan_of<CfgDCM2>(DC_M2) : plan_of<CfgDCM1>(DC_M1);
+        p = (wide && d.Cout % 32 != 0) ? deconv_plan_of<CfgDCM2, CfgDCM2v8>() : deconv_plan_of<CfgDCM1, CfgDCM1v8>(true);
         p.tiles_d = ceil_div(d.Din, p.TD); p.tiles_h = ceil_div(d.Hin, p.TH); p.tiles_w = ceil_div(d.Win, 32);
         }
     } else if (d.ksize_d == 1) {
@@ -2321,12 +2355,12 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
         // one 32-channel group per workgroup on 1 x 4 x 32 tiles whatever the layer (see CfgP*s above)
         (void)wide;
         switch (key) {
-            case 11: p = plan_of<CfgP1M1s>(P1_M1S); break;
-            case 12: p = plan_of<CfgP1S2M1s>(P1S2_M1S); break;
-            case 31: p = plan_of<CfgP3M1s>(P3_M1S); break;
-            case 32: p = plan_of<CfgP3S2M1s>(P3S2_M1S); break;
-            case 71: p = plan_of<CfgP7M1s>(P7_M1S); break;
-            case 312: p = plan_of<CfgP3D2M1s>(P3D2_M1S); break;
+            case 11: p = plan_of<CfgP1M1s>(); break;
+            case 12: p = plan_of<CfgP1S2M1s>(); break;
+            case 31: p = plan_of<CfgP3M1s, true>(); break;
+            case 32: p = plan_of<CfgP3S2M1s, true>(); break;
+            case 71: p = plan_of<CfgP7M1s>(); break;
+            case 312: p = plan_of<CfgP3D2M1s, true>(); break;
             default: return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: depth-1 layers are built for ksize 1 and 3 (stride 1 and 2) and 3 x 7 (stride 1)");
         }
         p.tiles_d = 1; p.tiles_h = ceil_div(d.Hout, p.TH); p.tiles_w = ceil_div(d.Wout, 32);
@@ -2344,12 +2378,12 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
             return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d: output size does not match the convolution arithmetic");
         const int key = d.ksize * 100 + d.stride * 10 + d.dilation;
         switch (key) {
-            case 111: p = wide ? plan_of<CfgK1M2>(K1_M2) : plan_of<CfgK1M1>(K1_M1); break;
-            case 311: p = wide ? plan_of<CfgK3M2>(K3_M2) : plan_of<CfgK3M1>(K3_M1); break;
-            case 321: p = wide ? plan_of<CfgK3S2M2>(K3S2_M2) : plan_of<CfgK3S2M1>(K3S2_M1); break;
-            case 511: p = wide ? plan_of<CfgK5M2>(K5_M2) : plan_of<CfgK5M1>(K5_M1); break;
-            case 512: p = wide ? plan_of<CfgK5D2M2>(K5D2_M2) : plan_of<CfgK5D2M1>(K5D2_M1); break;
-            case 711: p = wide ? plan_of<CfgK7M2>(K7_M2) : plan_of<CfgK7M1>(K7_M1); break;
+            case 111: p = wide ? plan_of<CfgK1M2>() : plan_of<CfgK1M1>(); break;
+            case 311: p = wide ? plan_of<CfgK3M2>() : plan_of<CfgK3M1>(); break;
+            case 321: p = wide ? plan_of<CfgK3S2M2, true>() : plan_of<CfgK3S2M1, true>(); break;
+            case 511: p = wide ? plan_of<CfgK5M2>() : plan_of<CfgK5M1, true>(); break;
+            case 512: p = wide ? plan_of<CfgK5D2M2>() : plan_of<CfgK5D2M1>(); break;
+            case 711: p = wide ? plan_of<CfgK7M2>() : plan_of<CfgK7M1, true>(); break;
             default:
                 return fail(SNVC_ERR_UNSUPPORTED,
                             "snvc_conv3d: (ksize,stride,dilation) not in {(1,1,1),(3,1,1),(3,2,1),(5,1,1),(5,1,2),(7,1,1)}");
@@ -2360,26 +2394,6 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
     p.nchunks = ceil_div(d.Cin, p.KC);
     if (p.groups > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: too many channel groups or samples");
     return SNVC_OK;
-}
-
-template <class Cfg, int EPI>
-void launch_conv_variant(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};   // one bit per device: the attribute is per device
-    if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_mfma_kernel<Cfg, EPI>), Cfg::LDS_BYTES, attr_done)) return;
-    conv3d_mfma_kernel<Cfg, EPI><<<grid, 256, Cfg::LDS_BYTES, st>>>(a);
-}
-
-// FAST: also build the fast-epilogue variants of this configuration (the ones on a measured path)
-template <class Cfg, bool FAST = false>
-void launch_conv(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    if constexpr (FAST) {
-        if (a.fast_epi && !a.plane) {
-            if (a.res) launch_conv_variant<Cfg, 2>(a, grid, st);
-            else launch_conv_variant<Cfg, 1>(a, grid, st);
-            return;
-        }
-    }
-    launch_conv_variant<Cfg, 0>(a, grid, st);
 }
 
 // depth-1 k3 / stride-1 layers big enough for the 1 x 16 x 32 Winograd tile (the small levels of the neck stay on the direct
@@ -2404,97 +2418,64 @@ inline int64_t wino_packed_count(const snvc_conv3d_desc &d) {
     return 0;
 }
 
-template <class Cfg, bool RES>
-void launch_winok_variant(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    constexpr int BYTES = Cfg::LDS_BYTES + 256;   // + (scale | bias) of 32 channels
-    static std::atomic<unsigned> attr_done{0};   // one bit per device: the attribute is per device
-    if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_winok_kernel<Cfg, RES>), BYTES, attr_done)) return;
-    conv3d_winok_kernel<Cfg, RES><<<grid, 256, BYTES, st>>>(a);
+// The packed fp32 weight buffer of a layer: [direct MFMA packing][Winograd packing][raw tail], in floats.
+struct PackedLayout {
+    int taps;                  // taps of the direct section
+    int64_t direct, wino, raw;
+    int64_t total() const { return direct + wino + raw; }
+    const float *wino_at(const float *packed) const { return packed + direct; }
+    const float *raw_at(const float *packed) const { return packed + direct + wino; }
+};
+
+PackedLayout packed_layout(const snvc_conv3d_desc &d, const Plan &p) {
+    const bool planar = d.ksize_d == 1;      // depth-1 layer: 1 x kh x k taps, never a raw tail
+    PackedLayout w;
+    w.taps = d.transposed ? 27 : planar ? (d.ksize_h ? d.ksize_h : d.ksize) * d.ksize : d.ksize * d.ksize * d.ksize;
+    w.direct = (int64_t)p.groups * p.nchunks * w.taps * (p.KC / 2) * 64 * p.MI;
+    w.wino = wino_packed_count(d);           // k3/s1 layers (and their kin) also carry the Winograd-transformed weights
+    w.raw = 0;
+    if (planar) return w;
+    // 1x1x1 layers to or (r6) from <= 2 channels also keep their raw [Cout][Cin] weights (streaming kernels)
+    if (!d.transposed && d.ksize == 1 && (d.Cout <= 2 || d.Cin <= 2)) w.raw = (int64_t)d.Cout * d.Cin;
+    // 3x3x3 / stride-1 layers with ONE output channel too ([Cin][27], VALU kernel)
+    if (!d.transposed && d.ksize == 3 && d.stride == 1 && d.dilation == 1 && d.Cout == 1) w.raw = (int64_t)d.Cin * 27;
+    // transposed layers to ONE channel as well ([Cin][1][27], VALU kernel of conv3d_small.hip)
+    if (d.transposed && d.Cout == 1) w.raw = (int64_t)d.Cin * 27;
+    return w;
+}
+
+static_assert(CfgWino::KC == 2 && CfgWinoP::KC == 2 && CfgWinoS2::KC == 2 && CfgWinoK5::KC == 2, "the Winograd packings hold two input channels per chunk");
+
+// dynamic LDS of the Winograd kernels: the tile + (scale | bias [| head weights]) of 32 channels
+template <class Cfg, int XMODE = 0>
+constexpr int wino_lds_bytes = Cfg::LDS_BYTES + (XMODE == 1 ? 384 : 256);
+
+template <class Cfg>
+void launch_winok(const ConvArgs &a, dim3 grid, hipStream_t st) {
+    if (a.res) launch_lds<conv3d_winok_kernel<Cfg, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else launch_lds<conv3d_winok_kernel<Cfg, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
 }
 
 template <class Cfg>
 void launch_winos2_pipe(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    constexpr int BYTES = Cfg::LDS_BYTES + 256;   // + (scale | bias) of 32 channels
-    if (a.res) {
-        static std::atomic<unsigned> attr_done{0};
-        if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_winos2_pipe_kernel<Cfg, true>), BYTES, attr_done)) return;
-        conv3d_winos2_pipe_kernel<Cfg, true><<<grid, 256, BYTES, st>>>(a);
-    } else {
-        static std::atomic<unsigned> attr_done{0};
-        if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_winos2_pipe_kernel<Cfg, false>), BYTES, attr_done)) return;
-        conv3d_winos2_pipe_kernel<Cfg, false><<<grid, 256, BYTES, st>>>(a);
-    }
-}
-
-template <class Cfg>
-void launch_winok(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    if (a.res) launch_winok_variant<Cfg, true>(a, grid, st);
-    else launch_winok_variant<Cfg, false>(a, grid, st);
-}
-
-template <class Cfg>
-void launch_winos2_pipe_stats(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    constexpr int BYTES = Cfg::LDS_BYTES + 256;
-    static std::atomic<unsigned> attr_done{0};
-    if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_winos2_pipe_kernel<Cfg, false, 3>), BYTES, attr_done)) return;
-    conv3d_winos2_pipe_kernel<Cfg, false, 3><<<grid, 256, BYTES, st>>>(a);
-}
-
-template <class Cfg, bool RES, bool PLANE>
-void launch_wino_variant(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    constexpr int BYTES = Cfg::LDS_BYTES + 256;   // + (scale | bias) of 32 channels
-    static std::atomic<unsigned> attr_done{0};   // one bit per device: the attribute is per device
-    if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_wino_kernel<Cfg, RES, PLANE>), BYTES, attr_done)) return;
-    conv3d_wino_kernel<Cfg, RES, PLANE><<<grid, 256, BYTES, st>>>(a);
-}
-
-template <class Cfg, bool RES, bool PLANE, int XMODE = 0>
-void launch_wino_dma_variant(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    constexpr int BYTES = Cfg::LDS_BYTES + (XMODE == 1 ? 384 : 256);   // + (scale | bias [| head weights]) of 32 channels
-    static std::atomic<unsigned> attr_done{0};   // one bit per device: the attribute is per device
-    if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_wino_dma_kernel<Cfg, RES, PLANE, XMODE>), BYTES, attr_done)) return;
-    conv3d_wino_dma_kernel<Cfg, RES, PLANE, XMODE><<<grid, 256, BYTES, st>>>(a);
+    if (a.res) launch_lds<conv3d_winos2_pipe_kernel<Cfg, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else launch_lds<conv3d_winos2_pipe_kernel<Cfg, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
 }
 
 template <class Cfg>
 void launch_wino_dma(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    if (a.res && a.plane) launch_wino_dma_variant<Cfg, true, true>(a, grid, st);
-    else if (a.res) launch_wino_dma_variant<Cfg, true, false>(a, grid, st);
-    else if (a.plane) launch_wino_dma_variant<Cfg, false, true>(a, grid, st);
-    else launch_wino_dma_variant<Cfg, false, false>(a, grid, st);
+    if (a.res && a.plane) launch_lds<conv3d_wino_dma_kernel<Cfg, true, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else if (a.res) launch_lds<conv3d_wino_dma_kernel<Cfg, true, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else if (a.plane) launch_lds<conv3d_wino_dma_kernel<Cfg, false, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else launch_lds<conv3d_wino_dma_kernel<Cfg, false, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
 }
 
 template <class Cfg>
 void launch_wino(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    if (a.res && a.plane) launch_wino_variant<Cfg, true, true>(a, grid, st);
-    else if (a.res) launch_wino_variant<Cfg, true, false>(a, grid, st);
-    else if (a.plane) launch_wino_variant<Cfg, false, true>(a, grid, st);
-    else launch_wino_variant<Cfg, false, false>(a, grid, st);
-}
-
-template <class Cfg, int EPI>
-void launch_deconv_variant(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};   // one bit per device: the attribute is per device
-    if (!allow_large_lds(reinterpret_cast<const void *>(&deconv3d_mfma_kernel<Cfg, EPI>), Cfg::LDS_BYTES, attr_done)) return;
-    deconv3d_mfma_kernel<Cfg, EPI><<<grid, 256, Cfg::LDS_BYTES, st>>>(a);
-}
-
-template <class Cfg>
-void launch_deconv(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    // the pair exchange of the fast epilogue needs an even input width (both lanes of a pair in range)
-    if (a.stats) {    // validated by conv3d_forward_impl: fast epilogue conditions, one channel group per workgroup, no addends
-        if constexpr (Cfg::MI == 1) launch_deconv_variant<Cfg, 5>(a, grid, st);
-    } else if (a.head_w) {   // validated by snvc_conv3d_forward_head: fast epilogue conditions hold, one channel group
-        if constexpr (Cfg::MI == 1) {
-            if (a.res) launch_deconv_variant<Cfg, 4>(a, grid, st);
-            else launch_deconv_variant<Cfg, 3>(a, grid, st);
-        }
-    } else if (a.fast_epi && a.Win % 2 == 0) {
-        if (a.res) launch_deconv_variant<Cfg, 2>(a, grid, st);
-        else launch_deconv_variant<Cfg, 1>(a, grid, st);
-    } else {
-        launch_deconv_variant<Cfg, 0>(a, grid, st);
-    }
+    if (a.res && a.plane) launch_lds<conv3d_wino_kernel<Cfg, true, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else if (a.res) launch_lds<conv3d_wino_kernel<Cfg, true, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else if (a.plane) launch_lds<conv3d_wino_kernel<Cfg, false, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+    else launch_lds<conv3d_wino_kernel<Cfg, false, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
 }
 
 }  // namespace
@@ -2581,18 +2562,7 @@ int64_t snvc_conv3d_packed_weight_count(const snvc_conv3d_desc *d) {
     using namespace snvc;
     Plan p;
     if (!d || make_plan(*d, p) != SNVC_OK) return -1;
-    const bool planar = d->ksize_d == 1;      // depth-1 layer: only the direct packing, no special forms
-    const int64_t taps = d->transposed ? 27 : (int64_t)(planar ? 1 : d->ksize) * (planar && d->ksize_h ? d->ksize_h : d->ksize) * d->ksize;
-    int64_t count = (int64_t)p.groups * p.nchunks * taps * (p.KC / 2) * 64 * p.MI;
-    if (planar) return count + wino_packed_count(*d);
-    count += wino_packed_count(*d);   // k3/s1 layers also carry the Winograd-transformed weights
-    // 1x1x1 layers with <= 2 output channels also keep their raw [Cout][Cin] weights (streaming kernel)
-    if (!d->transposed && d->ksize == 1 && (d->Cout <= 2 || d->Cin <= 2)) count += (int64_t)d->Cout * d->Cin;      // r6: or FROM <= 2 channels
-    // 3x3x3 / stride-1 layers with ONE output channel too ([Cin][27], VALU kernel)
-    if (!d->transposed && d->ksize == 3 && d->stride == 1 && d->dilation == 1 && d->Cout == 1) count += (int64_t)d->Cin * 27;
-    // transposed layers to ONE channel as well ([Cin][1][27], VALU kernel of conv3d_small.hip)
-    if (d->transposed && d->Cout == 1) count += (int64_t)d->Cin * 27;
-    return count;
+    return packed_layout(*d, p).total();
 }
 
 int snvc_conv3d_pack_weights(const snvc_conv3d_desc *d, const float *weight, float *packed, void *stream) {
@@ -2602,43 +2572,33 @@ int snvc_conv3d_pack_weights(const snvc_conv3d_desc *d, const float *weight, flo
     int rc = make_plan(*d, p);
     if (rc) return rc;
     if (!weight || !packed) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_pack_weights: null pointer");
-    int64_t total = snvc_conv3d_packed_weight_count(d);
-    const bool planar = d->ksize_d == 1;
-    const bool k3c1 = !planar && ((!d->transposed && d->ksize == 3 && d->stride == 1 && d->dilation == 1 && d->Cout == 1) ||
-                                  (d->transposed && d->Cout == 1));
-    if (!planar && ((!d->transposed && d->ksize == 1 && (d->Cout <= 2 || d->Cin <= 2)) || k3c1)) {   // raw copy behind the MFMA packing
-        const int64_t nraw = k3c1 ? (int64_t)d->Cin * 27 : (int64_t)d->Cout * d->Cin;
-        total -= nraw;
-        if (hipMemcpyAsync(packed + total, weight, sizeof(float) * nraw, hipMemcpyDeviceToDevice,
-                           as_stream(stream)) != hipSuccess)
-            return fail(SNVC_ERR_HIP, "snvc_conv3d_pack_weights: hipMemcpyAsync failed");
-    }
-    const int64_t wino = wino_packed_count(*d);
-    if (wino) {
-        total -= wino;
-        const unsigned wb = (unsigned)ceil_div<int64_t>(wino, 256);
+    const PackedLayout w = packed_layout(*d, p);
+    if (w.raw && hipMemcpyAsync(packed + w.direct + w.wino, weight, sizeof(float) * w.raw, hipMemcpyDeviceToDevice,
+                                as_stream(stream)) != hipSuccess)      // raw copy behind the packings
+        return fail(SNVC_ERR_HIP, "snvc_conv3d_pack_weights: hipMemcpyAsync failed");
+    if (w.wino) {
+        float *pw = packed + w.direct;
+        const unsigned wb = (unsigned)ceil_div<int64_t>(w.wino, 256);
         const int nck = ceil_div(d->Cin, 2);
-        if (planar)
-            pack_wino_weights_kernel<<<wb, 256, 0, as_stream(stream)>>>(weight, packed + total, d->Cout, d->Cin, 2, nck, wino, 3);
+        if (d->ksize_d == 1)
+            pack_wino_weights_kernel<<<wb, 256, 0, as_stream(stream)>>>(weight, pw, d->Cout, d->Cin, 2, nck, w.wino, 3);
         else if (d->ksize == 3 && d->stride == 2)
-            pack_winos2_weights_kernel<<<wb, 256, 0, as_stream(stream)>>>(weight, packed + total, d->Cout, d->Cin, 2, nck, wino);
+            pack_winos2_weights_kernel<<<wb, 256, 0, as_stream(stream)>>>(weight, pw, d->Cout, d->Cin, 2, nck, w.wino);
         else if (d->ksize == 3)
-            pack_wino_weights_kernel<<<wb, 256, 0, as_stream(stream)>>>(weight, packed + total, d->Cout, d->Cin, 2, nck, wino);
+            pack_wino_weights_kernel<<<wb, 256, 0, as_stream(stream)>>>(weight, pw, d->Cout, d->Cin, 2, nck, w.wino);
         else if (d->ksize == 5)
-            pack_winok_weights_kernel<5><<<wb, 256, 0, as_stream(stream)>>>(weight, packed + total, d->Cout, d->Cin, 2, nck, wino);
+            pack_winok_weights_kernel<5><<<wb, 256, 0, as_stream(stream)>>>(weight, pw, d->Cout, d->Cin, 2, nck, w.wino);
         else
-            pack_winok_weights_kernel<7><<<wb, 256, 0, as_stream(stream)>>>(weight, packed + total, d->Cout, d->Cin, 2, nck, wino);
+            pack_winok_weights_kernel<7><<<wb, 256, 0, as_stream(stream)>>>(weight, pw, d->Cout, d->Cin, 2, nck, w.wino);
         int rcw = check_launch("snvc_conv3d_pack_weights(winograd)");
         if (rcw) return rcw;
     }
-    const unsigned blocks = (unsigned)ceil_div<int64_t>(total, 256);
+    const unsigned blocks = (unsigned)ceil_div<int64_t>(w.direct, 256);
     if (d->transposed)
-        pack_deconv_weights_kernel<<<blocks, 256, 0, as_stream(stream)>>>(weight, packed, d->Cout, d->Cin, p.MI, p.KC,
-                                                                           p.nchunks, total);
+        pack_deconv_weights_kernel<<<blocks, 256, 0, as_stream(stream)>>>(weight, packed, d->Cout, d->Cin, p.MI, p.KC, p.nchunks, w.direct);
     else
-        pack_conv_weights_kernel<<<blocks, 256, 0, as_stream(stream)>>>(weight, packed, d->Cout, d->Cin,
-                                                                         (planar ? 1 : d->ksize) * (planar && d->ksize_h ? d->ksize_h : d->ksize) * d->ksize, p.MI, p.KC,
-                                                                         p.nchunks, total);
+        pack_conv_weights_kernel<<<blocks, 256, 0, as_stream(stream)>>>(weight, packed, d->Cout, d->Cin, w.taps, p.MI, p.KC, p.nchunks,
+                                                                         w.direct);
     return check_launch("snvc_conv3d_pack_weights");
 }
 
@@ -2660,8 +2620,8 @@ int snvc_conv3d_forward_head(const snvc_conv3d_desc *d, const float *x, const fl
     using namespace snvc;
     if (!d || !head_weight || !y_head) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_head: null pointer");
     if (!d->transposed || d->Cout != 32 || d->Win % 2 != 0 || (d->flags & SNVC_EPI_SIGMOID) ||
-        (int64_t)d->Dout * d->Hout * d->Wout >= ((int64_t)1 << 27) || (reinterpret_cast<uintptr_t>(y_head) & 7) ||
-        (reinterpret_cast<uintptr_t>(residual) & 15) || (d->res_batch_stride % 4) != 0)
+        (int64_t)d->Dout * d->Hout * d->Wout >= ((int64_t)1 << 27) || !aligned(8, y_head) || !aligned(16, residual) ||
+        (d->res_batch_stride % 4) != 0)
         return fail(SNVC_ERR_UNSUPPORTED,
                     "snvc_conv3d_forward_head: needs a transposed layer with 32 output channels, an even input width, "
                     "no Sigmoid, a 16-byte aligned residual and an 8-byte aligned head output");
@@ -2710,6 +2670,224 @@ int snvc_conv3d_forward_stats(const snvc_conv3d_desc *d, const float *x, const f
 }  // extern "C"
 
 namespace snvc {
+namespace {
+
+// What the kernel families ask about a call beyond its ConvArgs.  A family is `bool f(const Route &, ConvArgs &, int &rc)`: false
+// when it does not take the layer (the next one is tried), true with the call's status in rc when it does.
+struct Route {
+    const snvc_conv3d_desc &d;
+    const Plan &p;
+    PackedLayout w;
+    const float *packed_weight;
+    hipStream_t st;
+    bool planar, side_head, pooled, direct_only;
+    bool vec8;          // input rows 8-byte aligned (a.vec: 16-byte)
+    bool fast_common;   // fast epilogues: (wave-uniform channel base) + 32-bit lane byte offsets, whole 32-channel groups, no Sigmoid
+    bool epi16;         // 16-byte stores: output rows, y, residual and depth planes allow them
+    bool stream16;      // x, y and the residual allow the streaming kernels' 16-byte accesses
+    int64_t S;          // output voxels per channel
+};
+
+inline dim3 stream_grid(const Route &r) {
+    int64_t blocks = ceil_div<int64_t>(r.S / 4, 256);
+    if (blocks > 4096) blocks = 4096;
+    return dim3((unsigned)blocks, (unsigned)r.d.N);
+}
+
+// 1x1x1 convolution to <= 2 channels: HBM-bound streaming kernel (raw weights ride at the end of the packed buffer)
+bool pointwise_to_few(const Route &r, ConvArgs &a, int &rc) {
+    const snvc_conv3d_desc &d = r.d;
+    if (r.planar || d.transposed || d.ksize != 1 || d.stride != 1 || d.Cout > 2 || (r.S % 4) != 0 || !r.stream16) return false;
+    const float *wraw = r.w.raw_at(r.packed_weight);
+    if (d.Cout == 1)
+        pointwise_small_kernel<1><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cin, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+    else
+        pointwise_small_kernel<2><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cin, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+    rc = check_launch("snvc_conv3d_forward(pointwise)");
+    return true;
+}
+
+// 1x1x1 from <= 2 channels (the classifier's data gradient): streamed as well
+bool pointwise_from_few(const Route &r, ConvArgs &a, int &rc) {
+    const snvc_conv3d_desc &d = r.d;
+    if (r.planar || d.transposed || d.ksize != 1 || d.stride != 1 || d.Cin > 2 || d.Cout <= 2 || (r.S % 4) != 0 || a.plane || a.head_w ||
+        a.stats || (d.algo & SNVC_ALGO_ARITH_MASK) != 0 || !r.stream16)
+        return false;
+    const float *wraw = r.w.raw_at(r.packed_weight);
+    if (d.Cin == 1)
+        pointwise_expand_kernel<1><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cout, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+    else
+        pointwise_expand_kernel<2><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cout, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+    rc = check_launch("snvc_conv3d_forward(pointwise expand)");
+    return true;
+}
+
+// 3x3x3 / stride 1 to ONE channel: VALU kernel (raw weights as above)
+bool k3_to_one(const Route &r, ConvArgs &a, int &rc) {
+    const snvc_conv3d_desc &d = r.d;
+    if (r.planar || d.transposed || d.ksize != 3 || d.stride != 1 || d.dilation != 1 || d.Cout != 1 || a.plane) return false;
+    const int th_ = ceil_div(d.Hout, K3C1_TH), tw_ = ceil_div(d.Wout, 32);
+    const int64_t nt = (int64_t)ceil_div(d.Dout, K3C1_TD) * th_ * tw_;
+    if (nt >= ((int64_t)1 << 31) || d.N > 65535) return false;
+    conv3d_k3_cout1_kernel<<<dim3((unsigned)nt, (unsigned)d.N), 256, 0, r.st>>>(a.x, r.w.raw_at(r.packed_weight), a.scale, a.bias, a.res, a.y, d.Cin, d.Dout,
+                                                                                d.Hout, d.Wout, th_, tw_, a.x_bs, a.y_bs, a.r_bs, d.flags);
+    rc = check_launch("snvc_conv3d_forward(k3 to one channel)");
+    return true;
+}
+
+// transposed layer to ONE channel (the folded hourglass tail + classifier): VALU kernel, raw weights as above
+bool transposed_to_one(const Route &r, ConvArgs &a, int &rc) {
+    if (r.planar || a.head_w || !deconv3d_cout1_qualifies(r.d, a.x, a.y, a.res, a.x_bs, a.y_bs, a.r_bs)) return false;
+    deconv3d_cout1_launch(r.d, a.x, r.w.raw_at(r.packed_weight), a.scale, a.bias, a.res, a.y, a.x_bs, a.y_bs, a.r_bs, r.st);
+    rc = check_launch("snvc_conv3d_forward(transposed to one channel)");
+    return true;
+}
+
+// Job grid of the Winograd forms: one job per (sample, 32-channel group, TD x TH x TW output tile), two input channels per chunk
+inline int64_t wino_job_count(const snvc_conv3d_desc &d, int TD, int TH, int TW) {
+    return (int64_t)ceil_div(d.Dout, TD) * ceil_div(d.Hout, TH) * ceil_div(d.Wout, TW) * ceil_div(d.Cout, 32) * d.N;
+}
+// Fills the Winograd half of `a` for that grid; false, with `a` untouched, when the jobs do not fit a 32-bit grid.
+bool wino_job_grid(const Route &r, ConvArgs &a, int TD, int TH, int TW) {
+    const int64_t nj = wino_job_count(r.d, TD, TH, TW);
+    if (nj >= ((int64_t)1 << 31)) return false;
+    a.wp_wino = r.w.wino_at(r.packed_weight);
+    a.nchunks_wino = ceil_div(r.d.Cin, 2);
+    a.groups = ceil_div(r.d.Cout, 32);
+    a.tiles_d = ceil_div(r.d.Dout, TD); a.tiles_h = ceil_div(r.d.Hout, TH); a.tiles_w = ceil_div(r.d.Wout, TW);
+    a.njobs = (int)nj;
+    return true;
+}
+
+// k3 / stride 2: polyphase + F(4,2) along W (LDS-DMA staged: 16-byte INPUT rows; output rows may be 8-byte ones)
+bool winograd_stride2(const Route &r, ConvArgs &a, int &rc) {
+    const snvc_conv3d_desc &d = r.d;
+    const bool out8 = r.fast_common && (d.Wout % 2 == 0) && a.y_bs % 2 == 0 && a.r_bs % 2 == 0 && aligned(8, a.y, a.res);
+    if (r.planar || d.transposed || d.ksize != 3 || d.stride != 2 || d.dilation != 1 || !a.vec || !(a.fast_epi || out8) || a.plane ||
+        r.direct_only || !wino_job_grid(r, a, 4, 4, 32))
+        return false;
+    const dim3 g((unsigned)a.njobs, 1, 1);
+    // default: the slice-pipelined refill; SNVC_ALGO_WINO_TILE_STD selects the per-chunk refill form
+    const bool per_chunk = (d.algo & SNVC_ALGO_WINO_TILE_MASK) == SNVC_ALGO_WINO_TILE_STD;
+    if (a.stats) {        // the default form with 16-byte output rows carries the statistics epilogue
+        using Cfg = WinoS2PipeCfg<4>;
+        if (per_chunk || !a.fast_epi || a.res)
+            rc = fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: this stride-2 layer does not take the default kernel form");
+        else {
+            launch_lds<conv3d_winos2_pipe_kernel<Cfg, false, 3>>(g, 256, wino_lds_bytes<Cfg>, r.st, a);
+            rc = check_launch("snvc_conv3d_forward_stats(winograd stride 2)");
+        }
+        return true;
+    }
+    if (per_chunk && a.fast_epi) launch_winok<CfgWinoS2>(a, g, r.st);
+    else if (per_chunk) launch_winok<CfgWinoS2v8>(a, g, r.st);
+    else if (a.fast_epi) launch_winos2_pipe<WinoS2PipeCfg<4>>(a, g, r.st);
+    else launch_winos2_pipe<WinoS2PipeCfg<2>>(a, g, r.st);
+    rc = check_launch("snvc_conv3d_forward(winograd stride 2)");
+    return true;
+}
+
+// k5 / k7, stride 1 (k5 also at dilation 2): Winograd F(4,KS) along W (LDS-DMA staged: 16-byte rows only)
+bool winograd_k5k7(const Route &r, ConvArgs &a, int &rc) {
+    const snvc_conv3d_desc &d = r.d;
+    if (r.planar || d.transposed || !(d.ksize == 5 || d.ksize == 7) || d.stride != 1 || !(d.dilation == 1 || (d.dilation == 2 && d.ksize == 5)) ||
+        !a.vec || !a.fast_epi || a.plane || r.direct_only || !wino_job_grid(r, a, 4, 4, 32))
+        return false;
+    const dim3 g((unsigned)a.njobs, 1, 1);
+    if (d.ksize == 5 && d.dilation == 2) launch_winok<CfgWinoK5D2>(a, g, r.st);
+    else if (d.ksize == 5) launch_winok<CfgWinoK5>(a, g, r.st);
+    else launch_winok<CfgWinoK7>(a, g, r.st);
+    rc = check_launch("snvc_conv3d_forward(winograd k5/k7)");
+    return true;
+}
+
+// depth-1 k3 / stride 1 (the 2D neck's larger levels) on 16-byte rows: the same Winograd kernel on 1 x 16 x 32 tiles with
+// 3 taps per chunk instead of 9 (half the MFMAs of the direct depth-1 form)
+bool winograd_depth1(const Route &r, ConvArgs &a, int &rc) {
+    const snvc_conv3d_desc &d = r.d;
+    if (!r.planar || !planar_wino_layer(d) || !a.vec || !r.epi16 || !r.fast_common || r.direct_only || a.plane || a.head_w || r.pooled || a.stats)
+        return false;
+    // a job is a serial chain of Cin / 2 chunks: below two jobs per CU the direct form's 4x smaller tiles (4x the
+    // workgroups) finish sooner (2 crops of the released shape: heads 0.46 vs 0.44 ms/crop; 8 crops: 0.164 vs 0.196)
+    const bool forced = (d.algo & SNVC_ALGO_WINO_TILE_MASK) == SNVC_ALGO_WINO_TILE_BIG;     // tests reach the form on small inputs
+    if (!(forced || wino_job_count(d, 1, CfgWinoP::TH, CfgWinoP::TW) >= 2 * device_cu_count()) ||
+        !wino_job_grid(r, a, 1, CfgWinoP::TH, CfgWinoP::TW))
+        return false;
+    launch_wino_dma<CfgWinoP>(a, dim3((unsigned)a.njobs, 1, 1), r.st);
+    rc = check_launch("snvc_conv3d_forward(depth-1 winograd)");
+    return true;
+}
+
+// k3 / stride 1: Winograd F(4,3) along W when the rows allow 8-byte pair stores and 16-byte staging
+bool winograd_k3(const Route &r, ConvArgs &a, int &rc) {
+    const snvc_conv3d_desc &d = r.d;
+    const bool pair_ok = (d.Wout % 2 == 0) && a.y_bs % 2 == 0 && a.r_bs % 2 == 0 && aligned(8, a.y, a.res, a.plane);
+    const bool wide = a.vec && r.epi16;   // 16-byte staging and stores; else 8-byte ones (pair_ok)
+    if (r.planar || d.ksize != 3 || d.stride != 1 || d.transposed || !r.w.wino || !pair_ok || !r.fast_common || !(wide || r.vec8) || r.direct_only)
+        return false;
+    // tile choice.  Default: the 4x4x32 tile, LDS-DMA staged (137 VGPRs, 51 KB LDS: three workgroups per
+    // CU), or its register-staged 8-byte-row form when the rows are not 16-byte aligned.  Measured on cfg2:
+    // conv1 2.70 ms / conv2 1.40 ms / hg conv2 0.73 ms, against 2.82 / 1.45 / 0.89 for the 4x4x64 LDS-DMA
+    // tile (BIG) and 2.93 / 1.52 / 0.91 for the 2x4x64 register-staged one (STD).  desc.algo's
+    // SNVC_ALGO_WINO_TILE_* bits select the other forms (the parity tests run all of them).
+    const int tsel = d.algo & SNVC_ALGO_WINO_TILE_MASK;
+    const bool big = tsel == SNVC_ALGO_WINO_TILE_BIG && wide, stdt = tsel == SNVC_ALGO_WINO_TILE_STD, nreg = tsel == SNVC_ALGO_WINO_TILE_NARROW_REG;
+    const bool narrow = !big && !stdt;
+    if (!wino_job_grid(r, a, (big || narrow) ? 4 : 2, 4, narrow ? 32 : 64)) return false;
+    const dim3 g((unsigned)a.njobs, 1, 1);
+    const bool dflt = narrow && wide && !nreg;      // the default kernel form: the one that carries the side head, statistics and pooling
+    if (r.side_head) {   // built for the default kernel form without addends (the global model's conv2)
+        if (!dflt || a.res || a.plane || d.Cout != 32 || !aligned(16, a.y_head)) {
+            rc = fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_side_head: needs the default Winograd form, 32 output "
+                                            "channels, no residual / depth planes and a 16-byte aligned y_head");
+            return true;
+        }
+        launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 1>>(g, 256, wino_lds_bytes<CfgWinoN3, 1>, r.st, a);
+        rc = check_launch("snvc_conv3d_forward_side_head");
+    } else if (a.stats) {       // the default kernel form without addends carries the statistics epilogue
+        if (!dflt || a.res || a.plane) {
+            rc = fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: this layer does not take the default Winograd form");
+            return true;
+        }
+        launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 3>>(g, 256, wino_lds_bytes<CfgWinoN3, 3>, r.st, a);
+        rc = check_launch("snvc_conv3d_forward_stats(winograd)");
+    } else if (r.pooled) {      // built for the default kernel form without addends (the local trunk's conv4)
+        if (!dflt || a.res || a.plane) {
+            rc = fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: SNVC_EPI_AVGPOOL_D4 needs the default Winograd "
+                                            "form and no residual / depth planes");
+            return true;
+        }
+        launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 2>>(g, 256, wino_lds_bytes<CfgWinoN3, 2>, r.st, a);
+        rc = check_launch("snvc_conv3d_forward(pooled)");
+    } else {
+        if (big) launch_wino_dma<CfgWinoBig>(a, g, r.st);
+        else if (dflt) launch_wino_dma<CfgWinoN3>(a, g, r.st);
+        else if (narrow && wide) launch_wino<CfgWinoN>(a, g, r.st);
+        else if (narrow) launch_wino<CfgWinoN8>(a, g, r.st);
+        else if (wide) launch_wino<CfgWino>(a, g, r.st);
+        else launch_wino<CfgWino8>(a, g, r.st);
+        rc = check_launch("snvc_conv3d_forward(winograd)");
+    }
+    return true;
+}
+
+// direct and transposed MFMA kernels: every layer make_plan accepts, whatever its rows
+int direct_mfma(const Route &r, ConvArgs &a) {
+    const snvc_conv3d_desc &d = r.d;
+    if (a.stats && !(r.p.dc_m1 && a.vec && a.fast_epi && d.Win % 2 == 0 && !a.res && !a.head_w))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: the layer's rows do not allow the kernel forms that carry the statistics epilogue");
+    if (r.side_head)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_side_head: built for 3x3x3 / stride-1 layers on the Winograd path");
+    if (r.pooled)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: SNVC_EPI_AVGPOOL_D4 needs 16-byte aligned rows (the Winograd path)");
+    const int64_t ntiles = (int64_t)r.p.tiles_d * r.p.tiles_h * r.p.tiles_w;
+    const int64_t gx = d.transposed ? ntiles * (a.dc_planar ? 2 : 4) : ntiles;
+    if (gx >= ((int64_t)1 << 31)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: too many tiles");
+    r.p.launch(a, r.vec8, dim3((unsigned)gx, (unsigned)r.p.groups, (unsigned)d.N), r.st);
+    return check_launch("snvc_conv3d_forward");
+}
+
+}  // namespace
 
 int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *packed_weight, const float *scale,
                         const float *bias, const float *residual, const float *depth_planes, float *y,
@@ -2728,11 +2906,23 @@ int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward: ADD_PRE and ADD_POST are exclusive");
     if (depth_planes && (d->transposed || d->stride != 1 || d->Dout < 2 || d->ksize_d == 1 || (d->ksize == 1 && d->Cout <= 2)))
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_ex: depth planes need a stride-1 Conv3d with Dout >= 2");
-    if (d->transposed && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual)) & 7))
+    if (d->transposed && !aligned(8, y, residual))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward: transposed y / residual must be 8-byte aligned");
     const int64_t in_sz = (int64_t)d->Cin * d->Din * d->Hin * d->Win, out_sz = (int64_t)d->Cout * d->Dout * d->Hout * d->Wout;
     if (in_sz + (int64_t)8 * d->Din * d->Hin * d->Win >= ((int64_t)1 << 31))  // 32-bit in-sample offsets
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: one sample must stay below 2^31 elements");
+    const bool side_head = head_w && y;   // snvc_conv3d_forward_side_head: y AND its one-channel projection
+    const bool pooled = (d->flags & SNVC_EPI_AVGPOOL_D4) != 0;   // y is [N,Cout,Dout/4,Hout,Wout]
+    const bool direct_only = (d->algo & SNVC_ALGO_ARITH_MASK) == SNVC_ALGO_DIRECT;
+    if (pooled && (side_head || head_w || d->transposed || d->ksize_d == 1 || d->ksize != 3 || d->stride != 1 || d->dilation != 1 ||
+                   depth_planes || d->Dout % 4 != 0 || d->Cout % 32 != 0 || (d->flags & (SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST | SNVC_EPI_SIGMOID)) ||
+                   direct_only))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: SNVC_EPI_AVGPOOL_D4 is built for 3x3x3 / stride-1 Conv3d layers "
+                                          "with Dout % 4 == 0, whole 32-channel groups and no residual");
+    if (side_head && (d->transposed || d->ksize_d == 1 || d->ksize != 3 || d->stride != 1 || d->dilation != 1 || depth_planes))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_side_head: built for 3x3x3 / stride-1 Conv3d layers");
+    if (head_w && !side_head && !p.dc_m1)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_head: layer is not a single-group transposed convolution");
 
     ConvArgs a;
     a.x = x; a.wp = packed_weight; a.scale = scale; a.bias = bias;
@@ -2741,17 +2931,6 @@ int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *
     a.head_w = head_w; a.y_head = y_head;
     a.stats = stats;
     a.dc_planar = (d->transposed && d->ksize_d == 1) ? 1 : 0;
-    const bool side_head = head_w && y;   // snvc_conv3d_forward_side_head: y AND its one-channel projection
-    const bool pooled = (d->flags & SNVC_EPI_AVGPOOL_D4) != 0;   // y is [N,Cout,Dout/4,Hout,Wout]
-    if (pooled && (side_head || head_w || d->transposed || d->ksize_d == 1 || d->ksize != 3 || d->stride != 1 || d->dilation != 1 ||
-                   depth_planes || d->Dout % 4 != 0 || d->Cout % 32 != 0 || (d->flags & (SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST | SNVC_EPI_SIGMOID)) ||
-                   (d->algo & SNVC_ALGO_ARITH_MASK) == SNVC_ALGO_DIRECT))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: SNVC_EPI_AVGPOOL_D4 is built for 3x3x3 / stride-1 Conv3d layers "
-                                          "with Dout % 4 == 0, whole 32-channel groups and no residual");
-    if (side_head && (d->transposed || d->ksize_d == 1 || d->ksize != 3 || d->stride != 1 || d->dilation != 1 || depth_planes))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_side_head: built for 3x3x3 / stride-1 Conv3d layers");
-    if (head_w && !side_head && p.kind != DC_M1)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_head: layer is not a single-group transposed convolution");
     a.wp_wino = nullptr; a.nchunks_wino = 0;
     a.y = y;
     a.Cin = d->Cin; a.Din = d->Din; a.Hin = d->Hin; a.Win = d->Win;
@@ -2761,236 +2940,22 @@ int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *
     a.x_bs = d->x_batch_stride ? d->x_batch_stride : in_sz;
     a.y_bs = d->y_batch_stride ? d->y_batch_stride : (pooled ? out_sz / 4 : out_sz);
     a.r_bs = d->res_batch_stride ? d->res_batch_stride : out_sz;
-    a.vec = (d->Win % 4 == 0) && (reinterpret_cast<uintptr_t>(x) % 16 == 0) && (a.x_bs % 4 == 0);
-    const bool vec8 = (d->Win % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0) && (a.x_bs % 2 == 0);
-    // fast epilogues: (wave-uniform channel base) + 32-bit lane byte offsets, whole 32-channel groups, no
-    // Sigmoid; 16-byte stores when the output rows allow them
-    const bool direct_only = (d->algo & SNVC_ALGO_ARITH_MASK) == SNVC_ALGO_DIRECT;
-    const bool fast_common = (int64_t)d->Dout * d->Hout * d->Wout < ((int64_t)1 << 27) && d->Cout % 32 == 0 &&
-                             !(d->flags & SNVC_EPI_SIGMOID) && !(d->algo & SNVC_ALGO_GENERIC_EPILOGUE);
-    const bool epi16 = d->Wout % 4 == 0 && a.y_bs % 4 == 0 && a.r_bs % 4 == 0 &&
-                       ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(a.res) |
-                         reinterpret_cast<uintptr_t>(depth_planes)) & 15) == 0;
-    a.fast_epi = fast_common && epi16;
+    a.vec = (d->Win % 4 == 0) && aligned(16, x) && (a.x_bs % 4 == 0);
 
-    // 1x1x1 convolution to <= 2 channels: HBM-bound streaming kernel (raw weights ride at the end of
-    // the packed buffer, see snvc_conv3d_pack_weights)
-    const bool planar = d->ksize_d == 1;
-    const int64_t S = (int64_t)d->Dout * d->Hout * d->Wout;
-    if (!planar && !d->transposed && d->ksize == 1 && d->stride == 1 && d->Cout <= 2 && (S % 4) == 0 &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(a.res)) & 15) == 0 &&
-        a.x_bs % 4 == 0 && a.y_bs % 4 == 0 && a.r_bs % 4 == 0) {
-        const float *wraw = packed_weight + snvc_conv3d_packed_weight_count(d) - (int64_t)d->Cout * d->Cin;
-        int64_t blocks = ceil_div<int64_t>(S / 4, 256);
-        if (blocks > 4096) blocks = 4096;
-        dim3 g((unsigned)blocks, (unsigned)d->N);
-        if (d->Cout == 1)
-            pointwise_small_kernel<1><<<g, 256, 0, as_stream(stream)>>>(x, wraw, scale, bias, a.res, y, d->Cin, S, a.x_bs, a.y_bs, a.r_bs, d->flags);
-        else
-            pointwise_small_kernel<2><<<g, 256, 0, as_stream(stream)>>>(x, wraw, scale, bias, a.res, y, d->Cin, S, a.x_bs, a.y_bs, a.r_bs, d->flags);
-        return check_launch("snvc_conv3d_forward(pointwise)");
-    }
-    // 1x1x1 from <= 2 channels (the classifier's data gradient): streamed as well
-    if (!planar && !d->transposed && d->ksize == 1 && d->stride == 1 && d->Cin <= 2 && d->Cout > 2 && (S % 4) == 0 && !depth_planes &&
-        !head_w && !stats && (d->algo & SNVC_ALGO_ARITH_MASK) == 0 &&
-        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(a.res)) & 15) == 0 &&
-        a.x_bs % 4 == 0 && a.y_bs % 4 == 0 && a.r_bs % 4 == 0) {
-        const float *wraw = packed_weight + snvc_conv3d_packed_weight_count(d) - (int64_t)d->Cout * d->Cin;
-        int64_t blocks = ceil_div<int64_t>(S / 4, 256);
-        if (blocks > 4096) blocks = 4096;
-        dim3 g((unsigned)blocks, (unsigned)d->N);
-        if (d->Cin == 1)
-            pointwise_expand_kernel<1><<<g, 256, 0, as_stream(stream)>>>(x, wraw, scale, bias, a.res, y, d->Cout, S, a.x_bs, a.y_bs, a.r_bs, d->flags);
-        else
-            pointwise_expand_kernel<2><<<g, 256, 0, as_stream(stream)>>>(x, wraw, scale, bias, a.res, y, d->Cout, S, a.x_bs, a.y_bs, a.r_bs, d->flags);
-        return check_launch("snvc_conv3d_forward(pointwise expand)");
-    }
-    // 3x3x3 / stride 1 to ONE channel: VALU kernel (raw weights ride at the end of the packed buffer)
-    if (!planar && !d->transposed && d->ksize == 3 && d->stride == 1 && d->dilation == 1 && d->Cout == 1 && !depth_planes) {
-        const float *wraw = packed_weight + snvc_conv3d_packed_weight_count(d) - (int64_t)d->Cin * 27;
-        const int th_ = ceil_div(d->Hout, K3C1_TH), tw_ = ceil_div(d->Wout, 32);
-        const int64_t nt = (int64_t)ceil_div(d->Dout, K3C1_TD) * th_ * tw_;
-        if (nt < ((int64_t)1 << 31) && d->N <= 65535) {
-            conv3d_k3_cout1_kernel<<<dim3((unsigned)nt, (unsigned)d->N), 256, 0, as_stream(stream)>>>(
-                x, wraw, scale, bias, a.res, y, d->Cin, d->Dout, d->Hout, d->Wout, th_, tw_, a.x_bs, a.y_bs, a.r_bs, d->flags);
-            return check_launch("snvc_conv3d_forward(k3 to one channel)");
-        }
-    }
-    // transposed layer to ONE channel (the folded hourglass tail + classifier): VALU kernel, raw weights as above
-    if (!planar && !head_w && deconv3d_cout1_qualifies(*d, x, y, a.res, a.x_bs, a.y_bs, a.r_bs)) {
-        const float *wraw = packed_weight + snvc_conv3d_packed_weight_count(d) - (int64_t)d->Cin * 27;
-        deconv3d_cout1_launch(*d, x, wraw, scale, bias, a.res, y, a.x_bs, a.y_bs, a.r_bs, as_stream(stream));
-        return check_launch("snvc_conv3d_forward(transposed to one channel)");
-    }
-    // k3 / stride 2: polyphase + F(4,2) along W (LDS-DMA staged: 16-byte INPUT rows; output rows may be 8-byte ones)
-    {
-        const bool out8 = fast_common && (d->Wout % 2 == 0) && a.y_bs % 2 == 0 && a.r_bs % 2 == 0 &&
-                          ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(a.res)) & 7) == 0;
-        if (!planar && !d->transposed && d->ksize == 3 && d->stride == 2 && d->dilation == 1 && a.vec && (a.fast_epi || out8) &&
-            !depth_planes && !direct_only) {
-            a.wp_wino = packed_weight + (int64_t)p.groups * p.nchunks * 27 * (p.KC / 2) * 64 * p.MI;
-            a.nchunks_wino = ceil_div(d->Cin, 2);
-            a.groups = ceil_div(d->Cout, 32);
-            a.tiles_d = ceil_div(d->Dout, 4); a.tiles_h = ceil_div(d->Hout, 4); a.tiles_w = ceil_div(d->Wout, 32);
-            const int64_t nj = (int64_t)a.tiles_d * a.tiles_h * a.tiles_w * a.groups * d->N;
-            if (nj < ((int64_t)1 << 31)) {
-                a.njobs = (int)nj;
-                // default: the slice-pipelined refill; SNVC_ALGO_WINO_TILE_STD selects the per-chunk refill form
-                const bool per_chunk = (d->algo & SNVC_ALGO_WINO_TILE_MASK) == SNVC_ALGO_WINO_TILE_STD;
-                if (stats) {        // the default form with 16-byte output rows carries the statistics epilogue
-                    if (per_chunk || !a.fast_epi || a.res)
-                        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: this stride-2 layer does not take the default kernel form");
-                    launch_winos2_pipe_stats<WinoS2PipeCfg<4>>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                    return check_launch("snvc_conv3d_forward_stats(winograd stride 2)");
-                }
-                if (per_chunk && a.fast_epi) launch_winok<CfgWinoS2>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                else if (per_chunk) launch_winok<CfgWinoS2v8>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                else if (a.fast_epi) launch_winos2_pipe<WinoS2PipeCfg<4>>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                else launch_winos2_pipe<WinoS2PipeCfg<2>>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                return check_launch("snvc_conv3d_forward(winograd stride 2)");
-            }
-        }
-    }
-    // k5 / k7, stride 1, no dilation: Winograd F(4,KS) along W (LDS-DMA staged: 16-byte rows only)
-    if (!planar && !d->transposed && (d->ksize == 5 || d->ksize == 7) && d->stride == 1 &&
-        (d->dilation == 1 || (d->dilation == 2 && d->ksize == 5)) && a.vec && a.fast_epi && !depth_planes) {
-        if (!direct_only) {
-            const int64_t taps = (int64_t)d->ksize * d->ksize * d->ksize;
-            a.wp_wino = packed_weight + (int64_t)p.groups * p.nchunks * taps * (p.KC / 2) * 64 * p.MI;
-            a.nchunks_wino = ceil_div(d->Cin, 2);
-            a.groups = ceil_div(d->Cout, 32);
-            a.tiles_d = ceil_div(d->Dout, 4); a.tiles_h = ceil_div(d->Hout, 4); a.tiles_w = ceil_div(d->Wout, 32);
-            const int64_t nj = (int64_t)a.tiles_d * a.tiles_h * a.tiles_w * a.groups * d->N;
-            if (nj < ((int64_t)1 << 31)) {
-                a.njobs = (int)nj;
-                if (d->ksize == 5 && d->dilation == 2) launch_winok<CfgWinoK5D2>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                else if (d->ksize == 5) launch_winok<CfgWinoK5>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                else launch_winok<CfgWinoK7>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-                return check_launch("snvc_conv3d_forward(winograd k5/k7)");
-            }
-        }
-    }
-    // depth-1 k3 / stride 1 (the 2D neck's larger levels) on 16-byte rows: the same Winograd kernel on 1 x 16 x 32 tiles with
-    // 3 taps per chunk instead of 9 (half the MFMAs of the direct depth-1 form)
-    if (planar && planar_wino_layer(*d) && a.vec && epi16 && fast_common && !direct_only && !depth_planes && !head_w && !pooled && !stats) {
-        const int th_ = ceil_div(d->Hout, CfgWinoP::TH), tw_ = ceil_div(d->Wout, CfgWinoP::TW), groups_ = ceil_div(d->Cout, 32);
-        const int64_t nj = (int64_t)th_ * tw_ * groups_ * d->N;
-        // a job is a serial chain of Cin / 2 chunks: below two jobs per CU the direct form's 4x smaller tiles (4x the
-        // workgroups) finish sooner (2 crops of the released shape: heads 0.46 vs 0.44 ms/crop; 8 crops: 0.164 vs 0.196)
-        const bool forced = (d->algo & SNVC_ALGO_WINO_TILE_MASK) == SNVC_ALGO_WINO_TILE_BIG;     // tests reach the form on small inputs
-        if ((forced || nj >= 2 * device_cu_count()) && nj < ((int64_t)1 << 31)) {
-            a.wp_wino = packed_weight + (int64_t)p.groups * p.nchunks * 9 * (p.KC / 2) * 64 * p.MI;
-            a.nchunks_wino = ceil_div(d->Cin, CfgWinoP::KC);
-            a.groups = groups_;
-            a.tiles_d = 1; a.tiles_h = th_; a.tiles_w = tw_;
-            a.njobs = (int)nj;
-            launch_wino_dma<CfgWinoP>(a, dim3((unsigned)nj, 1, 1), as_stream(stream));
-            return check_launch("snvc_conv3d_forward(depth-1 winograd)");
-        }
-    }
-    // k3 / stride 1: Winograd F(4,3) along W when the rows allow 8-byte pair stores and 16-byte staging
-    {
-        const int64_t wino = (!planar && d->ksize == 3 && d->stride == 1 && !d->transposed) ? wino_packed_count(*d) : 0;
-        const bool pair_ok = (d->Wout % 2 == 0) && a.y_bs % 2 == 0 && a.r_bs % 2 == 0 &&
-                             ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(a.res) |
-                               reinterpret_cast<uintptr_t>(depth_planes)) & 7) == 0;
-        const bool wide = a.vec && epi16;   // 16-byte staging and stores; else 8-byte ones (pair_ok)
-        if (wino && pair_ok && fast_common && (wide || vec8) && !direct_only) {
-            a.wp_wino = packed_weight + (int64_t)p.groups * p.nchunks * 27 * (p.KC / 2) * 64 * p.MI;
-            a.nchunks_wino = ceil_div(d->Cin, CfgWino::KC);
-            a.groups = ceil_div(d->Cout, 32);
-            // tile choice.  Default: the 4x4x32 tile, LDS-DMA staged (137 VGPRs, 51 KB LDS: three workgroups per
-            // CU), or its register-staged 8-byte-row form when the rows are not 16-byte aligned.  Measured on cfg2:
-            // conv1 2.70 ms / conv2 1.40 ms / hg conv2 0.73 ms, against 2.82 / 1.45 / 0.89 for the 4x4x64 LDS-DMA
-            // tile (BIG) and 2.93 / 1.52 / 0.91 for the 2x4x64 register-staged one (STD).  desc.algo's
-            // SNVC_ALGO_WINO_TILE_* bits select the other forms (the parity tests run all of them).
-            const int tsel = d->algo & SNVC_ALGO_WINO_TILE_MASK;
-            const bool big = tsel == SNVC_ALGO_WINO_TILE_BIG && wide, stdt = tsel == SNVC_ALGO_WINO_TILE_STD,
-                       nreg = tsel == SNVC_ALGO_WINO_TILE_NARROW_REG;
-            const bool narrow = !big && !stdt;
-            const int TDc = (big || narrow) ? 4 : 2, THc = 4, TWc = narrow ? 32 : 64;
-            a.tiles_d = ceil_div(d->Dout, TDc);
-            a.tiles_h = ceil_div(d->Hout, THc);
-            a.tiles_w = ceil_div(d->Wout, TWc);
-            const int64_t nj = (int64_t)a.tiles_d * a.tiles_h * a.tiles_w * a.groups * d->N;
-            if (nj < ((int64_t)1 << 31)) {
-                a.njobs = (int)nj;
-                const dim3 g((unsigned)nj, 1, 1);
-                if (side_head) {   // built for the default kernel form without addends (the global model's conv2)
-                    if (!(narrow && wide && !nreg) || a.res || a.plane || d->Cout != 32 || (reinterpret_cast<uintptr_t>(y_head) & 15))
-                        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_side_head: needs the default Winograd form, 32 output "
-                                                          "channels, no residual / depth planes and a 16-byte aligned y_head");
-                    launch_wino_dma_variant<CfgWinoN3, false, false, 1>(a, g, as_stream(stream));
-                    return check_launch("snvc_conv3d_forward_side_head");
-                }
-                if (stats) {       // the default kernel form without addends carries the statistics epilogue
-                    if (!(narrow && wide && !nreg) || a.res || a.plane)
-                        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: this layer does not take the default Winograd form");
-                    launch_wino_dma_variant<CfgWinoN3, false, false, 3>(a, g, as_stream(stream));
-                    return check_launch("snvc_conv3d_forward_stats(winograd)");
-                }
-                if (pooled) {      // built for the default kernel form without addends (the local trunk's conv4)
-                    if (!(narrow && wide && !nreg) || a.res || a.plane)
-                        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: SNVC_EPI_AVGPOOL_D4 needs the default Winograd "
-                                                          "form and no residual / depth planes");
-                    launch_wino_dma_variant<CfgWinoN3, false, false, 2>(a, g, as_stream(stream));
-                    return check_launch("snvc_conv3d_forward(pooled)");
-                }
-                if (big) launch_wino_dma<CfgWinoBig>(a, g, as_stream(stream));
-                else if (narrow && wide && !nreg) launch_wino_dma<CfgWinoN3>(a, g, as_stream(stream));
-                else if (narrow && wide) launch_wino<CfgWinoN>(a, g, as_stream(stream));
-                else if (narrow) launch_wino<CfgWinoN8>(a, g, as_stream(stream));
-                else if (wide) launch_wino<CfgWino>(a, g, as_stream(stream));
-                else launch_wino<CfgWino8>(a, g, as_stream(stream));
-                return check_launch("snvc_conv3d_forward(winograd)");
-            }
-        }
-    }
-    if (stats && !(p.kind == DC_M1 && a.vec && a.fast_epi && d->Win % 2 == 0 && !a.res && !head_w))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: the layer's rows do not allow the kernel forms that carry the statistics epilogue");
-    if (side_head)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_side_head: built for 3x3x3 / stride-1 layers on the Winograd path");
-    if (pooled)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: SNVC_EPI_AVGPOOL_D4 needs 16-byte aligned rows (the Winograd path)");
-    const int64_t ntiles = (int64_t)p.tiles_d * p.tiles_h * p.tiles_w;
-    const int64_t gx = d->transposed ? ntiles * (a.dc_planar ? 2 : 4) : ntiles;
-    if (gx >= ((int64_t)1 << 31)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: too many tiles");
-    dim3 grid((unsigned)gx, (unsigned)p.groups, (unsigned)d->N);
-    hipStream_t st = as_stream(stream);
-    switch (p.kind) {
-        case K1_M1: launch_conv<CfgK1M1>(a, grid, st); break;
-        case K1_M2: launch_conv<CfgK1M2>(a, grid, st); break;
-        case K3_M1: launch_conv<CfgK3M1>(a, grid, st); break;
-        case K3_M2: launch_conv<CfgK3M2>(a, grid, st); break;
-        case K3S2_M1: launch_conv<CfgK3S2M1, true>(a, grid, st); break;
-        case K3S2_M2: launch_conv<CfgK3S2M2, true>(a, grid, st); break;
-        case K5_M1: launch_conv<CfgK5M1, true>(a, grid, st); break;
-        case K5_M2: launch_conv<CfgK5M2>(a, grid, st); break;
-        case K5D2_M1: launch_conv<CfgK5D2M1>(a, grid, st); break;
-        case K5D2_M2: launch_conv<CfgK5D2M2>(a, grid, st); break;
-        case K7_M1: launch_conv<CfgK7M1, true>(a, grid, st); break;
-        case K7_M2: launch_conv<CfgK7M2>(a, grid, st); break;
-        case P1_M1S: launch_conv<CfgP1M1s>(a, grid, st); break;
-        case P1S2_M1S: launch_conv<CfgP1S2M1s>(a, grid, st); break;
-        case P3_M1S: launch_conv<CfgP3M1s, true>(a, grid, st); break;
-        case P3S2_M1S: launch_conv<CfgP3S2M1s, true>(a, grid, st); break;
-        case P7_M1S: launch_conv<CfgP7M1s>(a, grid, st); break;
-        case P3D2_M1S: launch_conv<CfgP3D2M1s, true>(a, grid, st); break;
-        case DC_M1:
-            if (!a.vec && vec8) { a.vec = 1; launch_deconv<CfgDCM1v8>(a, grid, st); }
-            else launch_deconv<CfgDCM1>(a, grid, st);
-            break;
-        case DC_M2:
-            if (!a.vec && vec8) { a.vec = 1; launch_deconv<CfgDCM2v8>(a, grid, st); }
-            else launch_deconv<CfgDCM2>(a, grid, st);
-            break;
-        case DCP_M1:
-            if (!a.vec && vec8) { a.vec = 1; launch_deconv<CfgDCPv8>(a, grid, st); }
-            else launch_deconv<CfgDCP>(a, grid, st);
-            break;
-        default: return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: no kernel");
-    }
-    return check_launch("snvc_conv3d_forward");
+    Route r{*d, p, packed_layout(*d, p), packed_weight, as_stream(stream)};
+    r.planar = d->ksize_d == 1; r.side_head = side_head; r.pooled = pooled; r.direct_only = direct_only;
+    r.vec8 = (d->Win % 2 == 0) && aligned(8, x) && (a.x_bs % 2 == 0);
+    r.fast_common = (int64_t)d->Dout * d->Hout * d->Wout < ((int64_t)1 << 27) && d->Cout % 32 == 0 &&
+                    !(d->flags & SNVC_EPI_SIGMOID) && !(d->algo & SNVC_ALGO_GENERIC_EPILOGUE);
+    r.epi16 = d->Wout % 4 == 0 && a.y_bs % 4 == 0 && a.r_bs % 4 == 0 && aligned(16, y, a.res, depth_planes);
+    r.stream16 = aligned(16, x, y, a.res) && a.x_bs % 4 == 0 && a.y_bs % 4 == 0 && a.r_bs % 4 == 0;
+    r.S = (int64_t)d->Dout * d->Hout * d->Wout;
+    a.fast_epi = r.fast_common && r.epi16;
+
+    if (pointwise_to_few(r, a, rc) || pointwise_from_few(r, a, rc) || k3_to_one(r, a, rc) || transposed_to_one(r, a, rc) ||
+        winograd_stride2(r, a, rc) || winograd_k5k7(r, a, rc) || winograd_depth1(r, a, rc) || winograd_k3(r, a, rc))
+        return rc;
+    return direct_mfma(r, a);
 }
 
 }  // namespace snvc

@@ -868,23 +868,16 @@ __global__ void wgrad_wino_reduce_kernel(const float *__restrict__ partial, floa
     o[0] = g0; o[1] = g1; o[2] = g2;
 }
 
-template <class Cfg, int VEC>
-void launch_wgrad_variant(const WgradArgs &a, dim3 grid, hipStream_t st) {
-    constexpr int bytes = Cfg::LDS_FLOATS * 4;
-    static std::atomic<unsigned> attr_done{0};   // one bit per device: the attribute is per device
-    if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_kernel<Cfg, VEC>), bytes, attr_done)) return;
-    conv3d_wgrad_kernel<Cfg, VEC><<<grid, 256, bytes, st>>>(a);
-}
-
 template <class Cfg>
 void launch_wgrad(const WgradArgs &a, dim3 grid, hipStream_t st) {
+    constexpr int bytes = Cfg::LDS_FLOATS * 4;
     // the prefetching float4 path is built for the K-split configurations only (the tap-split ones have no
     // registers left for the prefetch: 112 accumulator registers + 60 of staging spill)
     if constexpr (Cfg::KSPLIT) {
-        if (a.vec == 2) launch_wgrad_variant<Cfg, 2>(a, grid, st);
-        else launch_wgrad_variant<Cfg, 4>(a, grid, st);
+        if (a.vec == 2) launch_lds<conv3d_wgrad_kernel<Cfg, 2>>(grid, 256, bytes, st, a);
+        else launch_lds<conv3d_wgrad_kernel<Cfg, 4>>(grid, 256, bytes, st, a);
     } else {
-        launch_wgrad_variant<Cfg, 0>(a, grid, st);
+        launch_lds<conv3d_wgrad_kernel<Cfg, 0>>(grid, 256, bytes, st, a);
     }
 }
 
@@ -1579,15 +1572,9 @@ int snvc_conv3d_wgrad_amax(const snvc_conv3d_desc *d, const float *x, const floa
                 const unsigned ab = (unsigned)std::min<int64_t>(ceil_div<int64_t>(std::max(n4x, n4g), 256 * 8), 4096);
                 wgrad_amax2_kernel<<<dim3(ab, 2, (unsigned)d->N), 256, 0, st>>>(x, g, amax, n4x, n4g, a.x_bs, a.g_bs);
             }
-            static std::atomic<unsigned> attr_x3{0}, attr_x3u{0};
             const unsigned nwg = (unsigned)(8 * ceil_div(b.njobs, 8));
-            if (a.vec == 4) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_x3_kernel<true>), X3WgCfg::LDS_ALLOC, attr_x3))
-                    conv3d_wgrad_x3_kernel<true><<<dim3(nwg), X3WgCfg::THREADS, X3WgCfg::LDS_ALLOC, st>>>(b);
-            } else {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_x3_kernel<false>), X3WgCfg::LDS_ALLOC, attr_x3u))
-                    conv3d_wgrad_x3_kernel<false><<<dim3(nwg), X3WgCfg::THREADS, X3WgCfg::LDS_ALLOC, st>>>(b);
-            }
+            if (a.vec == 4) launch_lds<conv3d_wgrad_x3_kernel<true>>(dim3(nwg), X3WgCfg::THREADS, X3WgCfg::LDS_ALLOC, st, b);
+            else launch_lds<conv3d_wgrad_x3_kernel<false>>(dim3(nwg), X3WgCfg::THREADS, X3WgCfg::LDS_ALLOC, st, b);
             int rcx = check_launch("snvc_conv3d_wgrad(split operands)");
             if (rcx) return rcx;
             const int64_t total = (int64_t)pairs * 27 * 1024;
@@ -1605,10 +1592,7 @@ int snvc_conv3d_wgrad_amax(const snvc_conv3d_desc *d, const float *x, const floa
         wgrad_units(pairs, kWgradPartitions / 2, a.P, a.upx);
         a.pairs = pairs;
         const unsigned nwg = (unsigned)(8 * a.upx * 3);
-        static std::atomic<unsigned> attr_done{0};
-        constexpr int bytes = WinoWgradCfg::LDS_FLOATS * 4;
-        if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_wino_kernel), bytes, attr_done))
-            conv3d_wgrad_wino_kernel<<<dim3(nwg), WinoWgradCfg::THREADS, bytes, st>>>(a);
+        launch_lds<conv3d_wgrad_wino_kernel>(dim3(nwg), WinoWgradCfg::THREADS, WinoWgradCfg::LDS_FLOATS * 4, st, a);
         int rcw = check_launch("snvc_conv3d_wgrad(winograd)");
         if (rcw) return rcw;
         const int64_t total = (int64_t)pairs * 9 * 1024;
@@ -1642,15 +1626,9 @@ int snvc_conv3d_wgrad_amax(const snvc_conv3d_desc *d, const float *x, const floa
                 const unsigned ab = (unsigned)std::min<int64_t>(ceil_div<int64_t>(std::max(n4x, n4g), 256 * 8), 4096);
                 wgrad_amax2_kernel<<<dim3(ab, 2, (unsigned)d->N), 256, 0, st>>>(x, g, amax, n4x, n4g, a.x_bs, a.g_bs);
             }
-            static std::atomic<unsigned> attr_x3s2{0}, attr_x3s2u{0};
             const unsigned nwg = (unsigned)(8 * ceil_div(b.njobs, 8));
-            if (a.vec == 4) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_x3s2_kernel<true>), X3S2WgCfg::LDS_BYTES, attr_x3s2))
-                    conv3d_wgrad_x3s2_kernel<true><<<dim3(nwg), X3S2WgCfg::THREADS, X3S2WgCfg::LDS_BYTES, st>>>(b);
-            } else {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_x3s2_kernel<false>), X3S2WgCfg::LDS_BYTES, attr_x3s2u))
-                    conv3d_wgrad_x3s2_kernel<false><<<dim3(nwg), X3S2WgCfg::THREADS, X3S2WgCfg::LDS_BYTES, st>>>(b);
-            }
+            if (a.vec == 4) launch_lds<conv3d_wgrad_x3s2_kernel<true>>(dim3(nwg), X3S2WgCfg::THREADS, X3S2WgCfg::LDS_BYTES, st, b);
+            else launch_lds<conv3d_wgrad_x3s2_kernel<false>>(dim3(nwg), X3S2WgCfg::THREADS, X3S2WgCfg::LDS_BYTES, st, b);
             int rcx = check_launch("snvc_conv3d_wgrad(split operands, stride 2)");
             if (rcx) return rcx;
             const int64_t total = (int64_t)pairs * 27 * 1024;
@@ -1669,14 +1647,8 @@ int snvc_conv3d_wgrad_amax(const snvc_conv3d_desc *d, const float *x, const floa
         a.pairs = pairs;
         const unsigned nwg = (unsigned)(8 * a.upx * 3);
         constexpr int bytes = S2WgradCfg::LDS_FLOATS * 4;
-        static std::atomic<unsigned> attr4{0}, attr2{0};
-        if (a.vec == 4) {
-            if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_s2_kernel<4>), bytes, attr4))
-                conv3d_wgrad_s2_kernel<4><<<dim3(nwg), S2WgradCfg::THREADS, bytes, st>>>(a);
-        } else {
-            if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_wgrad_s2_kernel<2>), bytes, attr2))
-                conv3d_wgrad_s2_kernel<2><<<dim3(nwg), S2WgradCfg::THREADS, bytes, st>>>(a);
-        }
+        if (a.vec == 4) launch_lds<conv3d_wgrad_s2_kernel<4>>(dim3(nwg), S2WgradCfg::THREADS, bytes, st, a);
+        else launch_lds<conv3d_wgrad_s2_kernel<2>>(dim3(nwg), S2WgradCfg::THREADS, bytes, st, a);
         int rcs = check_launch("snvc_conv3d_wgrad(stride 2)");
         if (rcs) return rcs;
         const int64_t total = (int64_t)pairs * 27 * 1024;

@@ -2129,9 +2129,7 @@ split_scale_kernel(const float *__restrict__ x, int64_t n, unsigned *__restrict_
 
 template <class Cfg, int EPI>
 void launch_f16(const F16Args &a, dim3 grid, hipStream_t st) {
-    static std::atomic<unsigned> attr_done{0};
-    if (!allow_large_lds(reinterpret_cast<const void *>(&conv3d_f16_kernel<Cfg, EPI>), Cfg::LDS_BYTES, attr_done)) return;
-    conv3d_f16_kernel<Cfg, EPI><<<grid, 256, Cfg::LDS_BYTES, st>>>(a);
+    launch_lds<conv3d_f16_kernel<Cfg, EPI>>(grid, 256, Cfg::LDS_BYTES, st, a);
 }
 
 }  // namespace
@@ -2288,33 +2286,17 @@ int snvc_f16_conv3d_forward(const snvc_conv3d_desc *d, const void *x, const void
     switch (p.kind) {
         case FK7QN: case FK5D2QN: case FK5QN: {
             using C7 = Q16SCfg<7, 1, 1, 1>; using C5D = Q16SCfg<5, 2, 1, 1>; using C5 = Q16SCfg<5, 1, 1, 1>;
-            static std::atomic<unsigned> at7{0}, at5{0}, at5p{0};
-            if (p.kind == FK7QN) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_q16s_kernel<C7>), C7::LDS_BYTES, at7))
-                    conv3d_q16s_kernel<C7><<<grid, 256, C7::LDS_BYTES, st>>>(a);
-            } else if (p.kind == FK5QN) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_q16s_kernel<C5>), C5::LDS_BYTES, at5p))
-                    conv3d_q16s_kernel<C5><<<grid, 256, C5::LDS_BYTES, st>>>(a);
-            } else {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_q16s_kernel<C5D>), C5D::LDS_BYTES, at5))
-                    conv3d_q16s_kernel<C5D><<<grid, 256, C5D::LDS_BYTES, st>>>(a);
-            }
+            if (p.kind == FK7QN) launch_lds<conv3d_q16s_kernel<C7>>(grid, 256, C7::LDS_BYTES, st, a);
+            else if (p.kind == FK5QN) launch_lds<conv3d_q16s_kernel<C5>>(grid, 256, C5::LDS_BYTES, st, a);
+            else launch_lds<conv3d_q16s_kernel<C5D>>(grid, 256, C5D::LDS_BYTES, st, a);
             break;
         }
         case FK7Q: case FK5D2Q: case FK5Q: {
             if (plane) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d_forward: the 16x16x32 form writes C8 tensors");
             using C7 = Q16SCfg<7, 1, 1, 2>; using C5D = Q16SCfg<5, 2, 1, 2>; using C5 = Q16SCfg<5, 1, 1, 2>;
-            static std::atomic<unsigned> at7{0}, at5{0}, at5p{0};
-            if (p.kind == FK7Q) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_q16s_kernel<C7>), C7::LDS_BYTES, at7))
-                    conv3d_q16s_kernel<C7><<<grid, 256, C7::LDS_BYTES, st>>>(a);
-            } else if (p.kind == FK5Q) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_q16s_kernel<C5>), C5::LDS_BYTES, at5p))
-                    conv3d_q16s_kernel<C5><<<grid, 256, C5::LDS_BYTES, st>>>(a);
-            } else {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_q16s_kernel<C5D>), C5D::LDS_BYTES, at5))
-                    conv3d_q16s_kernel<C5D><<<grid, 256, C5D::LDS_BYTES, st>>>(a);
-            }
+            if (p.kind == FK7Q) launch_lds<conv3d_q16s_kernel<C7>>(grid, 256, C7::LDS_BYTES, st, a);
+            else if (p.kind == FK5Q) launch_lds<conv3d_q16s_kernel<C5>>(grid, 256, C5::LDS_BYTES, st, a);
+            else launch_lds<conv3d_q16s_kernel<C5D>>(grid, 256, C5D::LDS_BYTES, st, a);
             break;
         }
         case FK1: launch_f16<F16K1, 0>(a, grid, st); break;
@@ -2477,12 +2459,10 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const void *x_hi, const void
         case FK3XH: launch_f16<F16K3X, 1>(a, grid, st); break;
         case FK5XQ: case FK5D2XQ: case FK7XQ: {
             if (to_f32 || head) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: the 16x16x32 form writes a split C8 tensor, no side head");
-#define SNVC_Q16S(CFG) do { static std::atomic<unsigned> at_{0};                                                                    \
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_q16s_kernel<CFG>), CFG::LDS_BYTES, at_))                \
-                    conv3d_q16s_kernel<CFG><<<grid, 256, CFG::LDS_BYTES, st>>>(a); } while (0)
             using C5 = Q16SCfg<5, 1>; using C5D = Q16SCfg<5, 2>; using C7 = Q16SCfg<7, 1>;
-            if (p.kind == FK5XQ) SNVC_Q16S(C5); else if (p.kind == FK5D2XQ) SNVC_Q16S(C5D); else SNVC_Q16S(C7);
-#undef SNVC_Q16S
+            if (p.kind == FK5XQ) launch_lds<conv3d_q16s_kernel<C5>>(grid, 256, C5::LDS_BYTES, st, a);
+            else if (p.kind == FK5D2XQ) launch_lds<conv3d_q16s_kernel<C5D>>(grid, 256, C5D::LDS_BYTES, st, a);
+            else launch_lds<conv3d_q16s_kernel<C7>>(grid, 256, C7::LDS_BYTES, st, a);
             break;
         }
         case FK3S2XQ: {
@@ -2493,26 +2473,16 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const void *x_hi, const void
             int g = device_cu_count();
             if (g <= 0) g = 256;
             if (total < g) g = total >= 8 ? (int)(total & ~(int64_t)7) : (int)total;
-            static std::atomic<unsigned> attr_s2{0};
-            if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_x3s2q_kernel), X3S2Cfg::LDS_BYTES, attr_s2))
-                conv3d_x3s2q_kernel<<<dim3((unsigned)g), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st>>>(a, (int)total);
+            launch_lds<conv3d_x3s2q_kernel>(dim3((unsigned)g), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)total);
             break;
         }
         case FK3XQ: {
             if (resflags || (to_f32 && head)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: the 16x16x32 form has no split residual, no side head beside a float32 result");
             if (ntiles * p.cblocks >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles");
             grid = dim3((unsigned)(ntiles * p.cblocks), 1, (unsigned)d->N);      // (tile, channel block) jobs, channel block fastest
-            static std::atomic<unsigned> attr_40{0}, attr_43{0}, attr_42{0};
-            if (to_f32) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_x3q_kernel<2>), X3QCfg::LDS_BYTES, attr_42))
-                    conv3d_x3q_kernel<2><<<grid, 256, X3QCfg::LDS_BYTES, st>>>(a);
-            } else if (head) {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_x3q_kernel<3>), X3QCfg::LDS_BYTES, attr_43))
-                    conv3d_x3q_kernel<3><<<grid, 256, X3QCfg::LDS_BYTES, st>>>(a);
-            } else {
-                if (allow_large_lds(reinterpret_cast<const void *>(&conv3d_x3q_kernel<0>), X3QCfg::LDS_BYTES, attr_40))
-                    conv3d_x3q_kernel<0><<<grid, 256, X3QCfg::LDS_BYTES, st>>>(a);
-            }
+            if (to_f32) launch_lds<conv3d_x3q_kernel<2>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
+            else if (head) launch_lds<conv3d_x3q_kernel<3>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
+            else launch_lds<conv3d_x3q_kernel<0>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
             break;
         }
         default: return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: no kernel");
@@ -2652,12 +2622,10 @@ int snvc_f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *pa
     hipStream_t st = as_stream(stream);
     if (kw == 7) {
         using C = X2QCfg<3, 7>;
-        static std::atomic<unsigned> at{0};
-        if (allow_large_lds(reinterpret_cast<const void *>(&conv2d_x3q_kernel<C>), C::LDS_BYTES, at)) conv2d_x3q_kernel<C><<<grid, 256, C::LDS_BYTES, st>>>(a);
+        launch_lds<conv2d_x3q_kernel<C>>(grid, 256, C::LDS_BYTES, st, a);
     } else {
         using C = X2QCfg<3, 3>;
-        static std::atomic<unsigned> at{0};
-        if (allow_large_lds(reinterpret_cast<const void *>(&conv2d_x3q_kernel<C>), C::LDS_BYTES, at)) conv2d_x3q_kernel<C><<<grid, 256, C::LDS_BYTES, st>>>(a);
+        launch_lds<conv2d_x3q_kernel<C>>(grid, 256, C::LDS_BYTES, st, a);
     }
     return check_launch("snvc_f16x3_conv2d_forward");
 }

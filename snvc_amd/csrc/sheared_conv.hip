@@ -1462,40 +1462,27 @@ int snvc_sheared_expand_amax(const float *g, const float *gcol, const float *pla
     const size_t lds = sizeof(float) * ((size_t)RB * q * LW + (size_t)RB * D);
     if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand: rows do not fit the LDS");
     const dim3 grid((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N);
-    static std::atomic<unsigned> attr1{0}, attr2{0}, attr4{0};
     if (q == 4) {      // r6: four phases (downsample 2 with half-pixel planes, downsample 4 with whole-pixel planes: index 4 w - m0 - d)
-        static std::atomic<unsigned> attr_m2_4{0};
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<4, 0>), (int)lds, attr4) ||
-            (amax && !allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<4, 2>), (int)lds, attr_m2_4)))
-            return check_launch("snvc_sheared_expand");
-        if (amax)
-            sheared_expand_kernel<4, 2><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, y, reinterpret_cast<double *>(amax),
-                                                                                 (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
+        if (!amax)
+            launch_lds<sheared_expand_kernel<4, 0>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, y, nullptr, (int)C, (int)D, (int)H,
+                                                    (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
         else
-            sheared_expand_kernel<4, 0><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, y, nullptr, (int)C, (int)D, (int)H,
-                                                                                 (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
+            launch_lds<sheared_expand_kernel<4, 2>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, y, reinterpret_cast<double *>(amax),
+                                                    (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
     } else if (q == 1) {
-        static std::atomic<unsigned> attr_m2_1{0};
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<1, 0>), (int)lds, attr1) ||
-            (amax && !allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<1, 2>), (int)lds, attr_m2_1)))
-            return check_launch("snvc_sheared_expand");
-        if (amax)
-            sheared_expand_kernel<1, 2><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, y, reinterpret_cast<double *>(amax),
-                                                                                 (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
+        if (!amax)
+            launch_lds<sheared_expand_kernel<1, 0>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, y, nullptr, (int)C, (int)D, (int)H,
+                                                    (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
         else
-            sheared_expand_kernel<1, 0><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, y, nullptr, (int)C, (int)D, (int)H,
-                                                                                 (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
+            launch_lds<sheared_expand_kernel<1, 2>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, y, reinterpret_cast<double *>(amax),
+                                                    (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
     } else {
-        static std::atomic<unsigned> attr_m2_2{0};
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<2, 0>), (int)lds, attr2) ||
-            (amax && !allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<2, 2>), (int)lds, attr_m2_2)))
-            return check_launch("snvc_sheared_expand");
-        if (amax)
-            sheared_expand_kernel<2, 2><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, y, reinterpret_cast<double *>(amax),
-                                                                                 (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
+        if (!amax)
+            launch_lds<sheared_expand_kernel<2, 0>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, y, nullptr, (int)C, (int)D, (int)H,
+                                                    (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
         else
-            sheared_expand_kernel<2, 0><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, y, nullptr, (int)C, (int)D, (int)H,
-                                                                                 (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
+            launch_lds<sheared_expand_kernel<2, 2>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, y, reinterpret_cast<double *>(amax),
+                                                    (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, flags);
     }
     return check_launch("snvc_sheared_expand");
 }
@@ -1527,21 +1514,16 @@ int snvc_sheared_expand_split(const float *g, const float *gcol, const float *pl
     const int threads = ceil_div((int)W, 64) * 64;
     const dim3 grid((unsigned)H, (unsigned)(G * DCH), (unsigned)N);
     const int64_t y_bs = y_batch_stride ? y_batch_stride : 2 * G * 8 * D * H * W;
-    static std::atomic<unsigned> attr1{0}, attr2{0}, attr4{0};
     _Float16 *yh = reinterpret_cast<_Float16 *>(y_hi), *yl = reinterpret_cast<_Float16 *>(y_lo);
-    if (q == 4) {
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_split_kernel<4>), (int)lds, attr4)) return check_launch("snvc_sheared_expand_split");
-        sheared_expand_split_kernel<4><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, yh, yl, overflow, (int)C, (int)D, (int)H,
-                                                                              (int)W, m0, (int)WG, off, (int)WG2, off2, DCH, DC, y_bs, flags);
-    } else if (q == 1) {
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_split_kernel<1>), (int)lds, attr1)) return check_launch("snvc_sheared_expand_split");
-        sheared_expand_split_kernel<1><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, yh, yl, overflow, (int)C, (int)D, (int)H,
-                                                                              (int)W, m0, (int)WG, off, (int)WG2, off2, DCH, DC, y_bs, flags);
-    } else {
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_split_kernel<2>), (int)lds, attr2)) return check_launch("snvc_sheared_expand_split");
-        sheared_expand_split_kernel<2><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, scale, bias, yh, yl, overflow, (int)C, (int)D, (int)H,
-                                                                              (int)W, m0, (int)WG, off, (int)WG2, off2, DCH, DC, y_bs, flags);
-    }
+    if (q == 4)
+        launch_lds<sheared_expand_split_kernel<4>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, yh, yl, overflow, (int)C, (int)D, (int)H,
+                                                   (int)W, m0, (int)WG, off, (int)WG2, off2, DCH, DC, y_bs, flags);
+    else if (q == 1)
+        launch_lds<sheared_expand_split_kernel<1>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, yh, yl, overflow, (int)C, (int)D, (int)H,
+                                                   (int)W, m0, (int)WG, off, (int)WG2, off2, DCH, DC, y_bs, flags);
+    else
+        launch_lds<sheared_expand_split_kernel<2>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, yh, yl, overflow, (int)C, (int)D, (int)H,
+                                                   (int)W, m0, (int)WG, off, (int)WG2, off2, DCH, DC, y_bs, flags);
     return check_launch("snvc_sheared_expand_split");
 }
 
@@ -1568,16 +1550,12 @@ int snvc_sheared_expand_stats(const float *g, const float *gcol, const float *pl
     if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_stats: rows do not fit the LDS");
     const dim3 grid((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N);
     double *partial = static_cast<double *>(workspace);
-    static std::atomic<unsigned> attr1{0}, attr2{0};
-    if (q == 1) {
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<1, 1>), (int)lds, attr1)) return check_launch("snvc_sheared_expand_stats");
-        sheared_expand_kernel<1, 1><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, nullptr, nullptr, nullptr, partial, (int)C, (int)D,
-                                                                             (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, 0);
-    } else {
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_expand_kernel<2, 1>), (int)lds, attr2)) return check_launch("snvc_sheared_expand_stats");
-        sheared_expand_kernel<2, 1><<<grid, threads, lds, as_stream(stream)>>>(g, gcol, planes, nullptr, nullptr, nullptr, partial, (int)C, (int)D,
-                                                                             (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, 0);
-    }
+    if (q == 1)
+        launch_lds<sheared_expand_kernel<1, 1>>(grid, threads, lds, as_stream(stream), g, gcol, planes, nullptr, nullptr, nullptr, partial, (int)C, (int)D,
+                                                (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, 0);
+    else
+        launch_lds<sheared_expand_kernel<2, 1>>(grid, threads, lds, as_stream(stream), g, gcol, planes, nullptr, nullptr, nullptr, partial, (int)C, (int)D,
+                                                (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2, RB, 0);
     int rc = check_launch("snvc_sheared_expand_stats(partial)");
     if (rc) return rc;
     launch_norm_finalize(partial, gamma, beta, scale, shift, mean, var, N, C, D * H * W, (int)grid.x, eps, as_stream(stream));
@@ -1605,16 +1583,12 @@ int snvc_sheared_backward_reduce(const float *g, const float *gcol, const float 
     if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_backward_reduce: rows do not fit the LDS");
     const dim3 grid((unsigned)ceil_div<int64_t>(H, 4), (unsigned)C, (unsigned)N);
     double *partial = static_cast<double *>(workspace);
-    static std::atomic<unsigned> attr1{0}, attr2{0};
-    if (q == 1) {
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_bwd_kernel<1>), (int)lds, attr1)) return check_launch("snvc_sheared_backward_reduce");
-        sheared_bwd_kernel<1><<<grid, 256, lds, as_stream(stream)>>>(g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
-                                                                   (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2);
-    } else {
-        if (!allow_large_lds(reinterpret_cast<const void *>(&sheared_bwd_kernel<2>), (int)lds, attr2)) return check_launch("snvc_sheared_backward_reduce");
-        sheared_bwd_kernel<2><<<grid, 256, lds, as_stream(stream)>>>(g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
-                                                                   (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2);
-    }
+    if (q == 1)
+        launch_lds<sheared_bwd_kernel<1>>(grid, 256, lds, as_stream(stream), g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
+                                          (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2);
+    else
+        launch_lds<sheared_bwd_kernel<2>>(grid, 256, lds, as_stream(stream), g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
+                                          (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2);
     int rc = check_launch("snvc_sheared_backward_reduce");
     if (rc) return rc;
     sheared_fold_kernel<<<(unsigned)ceil_div<int64_t>(N * C, 128), 128, 0, as_stream(stream)>>>(partial, sums, N * C, (int)grid.x);
@@ -1643,10 +1617,8 @@ int snvc_warped_expand(const float *p, const float *q, const float *e, const flo
         const int threads = ceil_div(RB * quads, 64) * 64;
         const size_t lds = sizeof(float) * (2 * 3 * (size_t)RB * (2 * W + 8) + 3 * (size_t)RB * D);
         if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: rows do not fit the LDS");
-        static std::atomic<unsigned> attr{0};
-        if (!allow_large_lds(reinterpret_cast<const void *>(&warped_expand_kernel), (int)lds, attr)) return check_launch("snvc_warped_expand");
-        warped_expand_kernel<<<dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), threads, lds, as_stream(stream)>>>(
-            p, q, e, planes, shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W, RB, flags & SNVC_EPI_RELU);
+        launch_lds<warped_expand_kernel>(dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), threads, lds, as_stream(stream), p, q, e, planes,
+                                         shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W, RB, flags & SNVC_EPI_RELU);
         return check_launch("snvc_warped_expand");
     }
     auto lds_of = [&](int rb) { return sizeof(float) * (2 * 3 * (size_t)rb * (W + 16) + (size_t)rb * D + 4 + 4 * (size_t)(D + 2)); };
@@ -1654,10 +1626,8 @@ int snvc_warped_expand(const float *p, const float *q, const float *e, const flo
     const int threads = ceil_div(RB * quads, 64) * 64;
     const size_t lds = lds_of(RB);
     if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: rows do not fit the LDS");
-    static std::atomic<unsigned> attr_w{0};
-    if (!allow_large_lds(reinterpret_cast<const void *>(&warped_expand_win_kernel), (int)lds, attr_w)) return check_launch("snvc_warped_expand");
-    warped_expand_win_kernel<<<dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), threads, lds, as_stream(stream)>>>(
-        p, q, e, planes, shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W, RB, flags);
+    launch_lds<warped_expand_win_kernel>(dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), threads, lds, as_stream(stream), p, q, e, planes,
+                                         shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W, RB, flags);
     return check_launch("snvc_warped_expand");
 }
 
@@ -1677,11 +1647,8 @@ int snvc_warped_expand_backward(const float *dy, const float *shift, float *a, f
     while (RB > 1 && lds_of(RB) > 150 * 1024) --RB;
     const size_t lds = lds_of(RB);
     if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_backward: rows do not fit the LDS");
-    static std::atomic<unsigned> attr{0};
-    if (!allow_large_lds(reinterpret_cast<const void *>(&warped_expand_bwd_kernel), (int)lds, attr))
-        return check_launch("snvc_warped_expand_backward");
-    warped_expand_bwd_kernel<<<dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), RB * TW, lds, as_stream(stream)>>>(
-        dy, shift, a, dplanes, (int)C, (int)D, (int)H, (int)W, RB, TW);
+    launch_lds<warped_expand_bwd_kernel>(dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), RB * TW, lds, as_stream(stream), dy, shift, a,
+                                         dplanes, (int)C, (int)D, (int)H, (int)W, RB, TW);
     return check_launch("snvc_warped_expand_backward");
 }
 
@@ -1710,11 +1677,8 @@ int snvc_warped_expand_split(const float *p, const float *q, const float *e, con
     const int threads = ceil_div((int)W, 64) * 64;
     const dim3 grid((unsigned)H, (unsigned)(G * DCH), (unsigned)N);
     const int64_t y_bs = y_batch_stride ? y_batch_stride : 2 * G * 8 * D * H * W;
-    static std::atomic<unsigned> attr{0};
-    if (!allow_large_lds(reinterpret_cast<const void *>(&warped_expand_split_kernel), (int)lds, attr)) return check_launch("snvc_warped_expand_split");
-    warped_expand_split_kernel<<<grid, threads, lds, as_stream(stream)>>>(p, q, e, planes, shift, scale, bias, reinterpret_cast<_Float16 *>(y_hi),
-                                                                          reinterpret_cast<_Float16 *>(y_lo), overflow, (int)C, (int)D, (int)H,
-                                                                          (int)W, DCH, DC, y_bs, flags);
+    launch_lds<warped_expand_split_kernel>(grid, threads, lds, as_stream(stream), p, q, e, planes, shift, scale, bias, reinterpret_cast<_Float16 *>(y_hi),
+                                           reinterpret_cast<_Float16 *>(y_lo), overflow, (int)C, (int)D, (int)H, (int)W, DCH, DC, y_bs, flags);
     return check_launch("snvc_warped_expand_split");
 }
 

@@ -371,17 +371,12 @@ int launch_gather_lds(const float *ws, const float *l_pts, const float *r_pts, v
     const int nruns = (int)ceil_div<int64_t>(V, run);
     const dim3 grid((unsigned)(8 * ceil_div(nruns, 8) * (int)(F / CS)), 1, (unsigned)N);
     float ix = 0.0f, iy = 0.0f;
-    if (pow2_res(res_x, ix) && pow2_res(res_y, iy)) {
-        static std::atomic<unsigned> attr_done{0};
-        if (allow_large_lds(reinterpret_cast<const void *>(&voxel_gather_fwd_lds<CS, OUT, BS, true>), (int)lds, attr_done))
-            voxel_gather_fwd_lds<CS, OUT, BS, true><<<grid, BS, lds, st>>>(ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V, run,
-                                                                         nruns, ix, iy, mul_dev, lo_off, out_bs);
-    } else {
-        static std::atomic<unsigned> attr_done{0};
-        if (allow_large_lds(reinterpret_cast<const void *>(&voxel_gather_fwd_lds<CS, OUT, BS, false>), (int)lds, attr_done))
-            voxel_gather_fwd_lds<CS, OUT, BS, false><<<grid, BS, lds, st>>>(ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V, run,
-                                                                          nruns, res_x, res_y, mul_dev, lo_off, out_bs);
-    }
+    if (pow2_res(res_x, ix) && pow2_res(res_y, iy))
+        launch_lds<voxel_gather_fwd_lds<CS, OUT, BS, true>>(grid, BS, lds, st, ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V, run, nruns,
+                                                            ix, iy, mul_dev, lo_off, out_bs);
+    else
+        launch_lds<voxel_gather_fwd_lds<CS, OUT, BS, false>>(grid, BS, lds, st, ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V, run, nruns,
+                                                             res_x, res_y, mul_dev, lo_off, out_bs);
     return 0;
 }
 
