@@ -439,6 +439,12 @@ class VernierScale(SplitModePolicy, nn.Module):
         from .. import decode
         return decode.ncf_to_update_2d(self.cfg, ncf, samples, grid, filter_3d, arg_max=arg_max, coordinates=coordinates)
 
+    def refine_boxes(self, ncf, samples, grid, filter_3d=None, coordinates=None):
+        """The same read-out kept on the device (snvc_amd.decode.refine_boxes): device tensors in, device tensors out, no
+        host copy and no synchronisation."""
+        from .. import decode
+        return decode.refine_boxes(self.cfg, ncf, samples, grid, filter_3d=filter_3d, coordinates=coordinates)
+
 
 def get_model(cfgs, is_train=False):
     """reference vernier.py:841-842"""
