@@ -794,6 +794,8 @@ conv3d_x3q_kernel(const F16Args a) {
     }
     const int64_t steps_total = (int64_t)a.nchunks * NQ;
     const h8 *wq = reinterpret_cast<const h8 *>(a.wp) + ((int64_t)cb * steps_total * 4) * 64 + lane;
+    const int c0 = cb * 32 + 8 * kb;               // first of this lane's 8 output channels
+    const bool has_aff = a.scale != nullptr;       // decided once: the epilogue's constants are fetched inside the last chunk
     h8 q_[PF][4];
 #pragma unroll
     for (int i = 0; i < PF; ++i) {
@@ -805,9 +807,16 @@ conv3d_x3q_kernel(const F16Args a) {
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds;
     issue(0, 0);
     __syncthreads();
-    for (int chunk = 0; chunk < a.nchunks; ++chunk) {
+    // The LAST chunk is a copy of the loop body of its own (LAST is a constant in it): it has no next chunk to fetch fragments for, so
+    // from k-step FILL_STEP on it requests nothing of the weights (they were 8 KB of the next block's fragments or padding per wave,
+    // loaded for nothing) and, at FILL_STEP, the epilogue's per-channel constants instead -- 16-byte loads into the registers the ring
+    // has just given up, which land under the last two k-steps.  Fetched behind the last barrier, one dword at a time, they cost every
+    // tile an exposed L2 round trip.  (As a branch inside ONE loop body the ring's hand-over across the branch became register copies
+    // of loads in flight, i.e. a vmcnt(0) in front of k-step FILL_STEP + 1 that waited for the refill.)
+    h8 epc[6];         // scale[0..3], scale[4..7], bias[0..3], bias[4..7], head[0..3], head[4..7] of this lane's 8 channels
+    auto run_chunk = [&](const int chunk, auto last_tag) {
+        constexpr bool LAST = decltype(last_tag)::value;
         const unsigned img = lds_base + (unsigned)((chunk & 1) * Cfg::IMG_BYTES);
-        const bool more = chunk + 1 < a.nchunks;
         h8 bfr[2][8];      // [buffer][(row of the half-step) * 4 + (row half) * 2 + plane]
         auto load_b = [&](int buf, int hs) {
 #pragma unroll
@@ -829,7 +838,7 @@ conv3d_x3q_kernel(const F16Args a) {
                     // every weight fragment in flight lands first: none is waited for between here and the barrier
 #pragma unroll
                     for (int i = 0; i < PF; ++i) asm volatile("" ::"v"(q_[i][0]), "v"(q_[i][1]), "v"(q_[i][2]), "v"(q_[i][3]));
-                    if (more) issue(chunk + 1, (chunk + 1) & 1);
+                    if constexpr (!LAST) issue(chunk + 1, (chunk + 1) & 1);
                 }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) af[m] = q_[0][m];
@@ -837,9 +846,27 @@ conv3d_x3q_kernel(const F16Args a) {
                 for (int i = 0; i + 1 < PF; ++i)
 #pragma unroll
                     for (int m = 0; m < 4; ++m) q_[i][m] = q_[i + 1][m];
+                if constexpr (!LAST) {
 #pragma unroll
-                for (int m = 0; m < 4; ++m) q_[PF - 1][m] = wq[m * 64];      // from k-step FILL_STEP on: fragments of the NEXT chunk
-                wq += 4 * 64;
+                    for (int m = 0; m < 4; ++m) q_[PF - 1][m] = wq[m * 64];      // from k-step FILL_STEP on: fragments of the NEXT chunk
+                    wq += 4 * 64;
+                } else if (hs < 2 * Cfg::FILL_STEP) {
+#pragma unroll
+                    for (int m = 0; m < 4; ++m) q_[PF - 1][m] = wq[m * 64];
+                    wq += 4 * 64;
+                } else if (hs == 2 * Cfg::FILL_STEP) {
+                    if (has_aff) {       // block-uniform, decided once
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) {
+                            epc[k] = *reinterpret_cast<const h8 *>(a.scale + c0 + 4 * k);
+                            epc[2 + k] = *reinterpret_cast<const h8 *>(a.bias + c0 + 4 * k);
+                        }
+                    }
+                    if constexpr (EPI == 3) {
+#pragma unroll
+                        for (int k = 0; k < 2; ++k) epc[4 + k] = *reinterpret_cast<const h8 *>(a.head + c0 + 4 * k);
+                    }
+                }
             }
             if (hs + 1 < 2 * NQ) {
                 load_b(nx, hs + 1);
@@ -864,19 +891,24 @@ conv3d_x3q_kernel(const F16Args a) {
             __builtin_amdgcn_sched_barrier(0);
         }
         __syncthreads();     // drains the DMA of the next chunk and retires every read of this chunk's buffer
-    }
+    };
+    for (int chunk = 0; chunk + 1 < a.nchunks; ++chunk) run_chunk(chunk, std::false_type{});
+    run_chunk(a.nchunks - 1, std::true_type{});
+    // the constants are waited for HERE, in front of the first store: a value first read behind a store (the compiler sinks the side
+    // head's sum there) is waited for with vmcnt(0), i.e. until the wave's own stores are acknowledged
+    if (has_aff) asm volatile("" ::"v"(epc[0]), "v"(epc[1]), "v"(epc[2]), "v"(epc[3]));
+    if constexpr (EPI == 3) asm volatile("" ::"v"(epc[4]), "v"(epc[5]));
 
     const int out_hw = a.Hout * a.Wout;
     const int64_t out_dhw = (int64_t)out_hw * a.Dout;
     const bool relu = (a.flags & SNVC_EPI_RELU) != 0;
-    const int c0 = cb * 32 + 8 * kb;
     float sc[8], bi[8], hw8[8];
     const float x_inv = (EPI == 2 && a.x_mul) ? 1.0f / a.x_mul[0] : 1.0f;      // see conv3d_f16_kernel's EPI 2
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
-        sc[e] = (a.scale ? a.scale[c0 + e] : 1.0f) * x_inv;
-        bi[e] = a.scale ? a.bias[c0 + e] : 0.0f;
-        hw8[e] = (EPI == 3) ? a.head[c0 + e] : 0.0f;
+        sc[e] = (has_aff ? __builtin_bit_cast(f32x4q, epc[e >> 2])[e & 3] : 1.0f) * x_inv;
+        bi[e] = has_aff ? __builtin_bit_cast(f32x4q, epc[2 + (e >> 2)])[e & 3] : 0.0f;
+        hw8[e] = (EPI == 3) ? __builtin_bit_cast(f32x4q, epc[4 + (e >> 2)])[e & 3] : 0.0f;
     }
     if constexpr (EPI == 2) {
         // the training step's layers (r6): lane (kb, col) stores its 8 channels of 16 consecutive voxels as float32 NCDHW (64-byte runs per
@@ -1227,9 +1259,13 @@ conv3d_x3s2q_kernel(const F16Args a, const int total_jobs) {
     auto geometry = [&](const Job &jb) {
         const int id0 = 2 * jb.od0 - a.pad_d, ih0 = 2 * jb.oh0 - a.pad_h, iw0 = 2 * jb.ow0 - a.pad_w;
         vmask = 0;
+        // the pieces' (dd, hh, pp) are derived from the thread index anew at every tile hand-over: kept across the step loop they are
+        // 18 more live values than the register file has (they were spilled, and reloaded one wait at a time in front of the refill)
+        int tid_ = tid;
+        asm volatile("" : "+v"(tid_));
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
-            const int i = it * 512 + tid;
+            const int i = it * 512 + tid_;
             const int dd = i / (IN_H * IN_W), r2 = i - dd * (IN_H * IN_W);
             const int hh = r2 / IN_W, pp = r2 - hh * IN_W;
             // row layout: [16 even columns][16 odd columns] twice, then column 64 -- 32 consecutive positions are 32 consecutive
@@ -1304,6 +1340,7 @@ conv3d_x3s2q_kernel(const F16Args a, const int total_jobs) {
     __syncthreads();
     const int gstride = gridDim.x;
     constexpr float kHalfMax = 65504.0f;
+    const bool has_aff = a.scale != nullptr;         // decided once, not per channel
     float vmax = 0.0f;
     int chunk = 0;
     while (true) {
@@ -1407,11 +1444,23 @@ conv3d_x3s2q_kernel(const F16Args a, const int total_jobs) {
             {
                 const int bb = chalf;
                 const int c0 = cur.cb * 64 + bb * 32 + 8 * kb;
+                // four 16-byte loads behind ONE block-uniform test (they were sixteen dwords, each behind its own).  Requested ahead of
+                // the step's last barrier instead -- into the B fragments' registers -- they cost the kernel its 256-register budget:
+                // 68-84 bytes of scratch, reloaded in front of every refill (profiles/epilogue_round_trips/)
+                f32x4q scv[2] = {f32x4q{1.0f, 1.0f, 1.0f, 1.0f}, f32x4q{1.0f, 1.0f, 1.0f, 1.0f}};
+                f32x4q biv[2] = {f32x4q{0.0f, 0.0f, 0.0f, 0.0f}, f32x4q{0.0f, 0.0f, 0.0f, 0.0f}};
+                if (has_aff) {
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        scv[k] = *reinterpret_cast<const f32x4q *>(a.scale + c0 + 4 * k);
+                        biv[k] = *reinterpret_cast<const f32x4q *>(a.bias + c0 + 4 * k);
+                    }
+                }
                 float sc[8], bi[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    sc[e] = a.scale ? a.scale[c0 + e] : 1.0f;
-                    bi[e] = a.scale ? a.bias[c0 + e] : 0.0f;
+                    sc[e] = scv[e >> 2][e & 3];
+                    bi[e] = biv[e >> 2][e & 3];
                 }
                 const int64_t gplane = (int64_t)(cur.cb * 8 + bb * 4 + kb) * out_dhw * 8;
                 _Float16 *yn = a.y + cur.n * a.y_bs + gplane, *yn_lo = a.y_lo + cur.n * a.y_bs + gplane;
