@@ -8,6 +8,7 @@
     snvc_amd.models.vernier                <->  snvc.models.vernier   (VernierScale 3D trunk)
     snvc_amd.models.hrnet                  <->  snvc.models.hrnet     (HRNet backbone; install_as_snvc(backbone="hip"))
     snvc_amd.models.loss3d                 <->  snvc.models.loss3d    (training losses)
+    snvc_amd.models.FCmodel                <->  snvc.models.FCmodel   (the FC box head of use_bbox_head)
 
 Everything executes in hand-written HIP kernels from ``libsnvc_hip.so`` (C ABI:
 ``include/snvc_hip.h``, ``include/snvc_iou3d.h``, ``include/snvc_hrnet.h``).  There is no CPU path: CPU tensors raise, and a missing shared
@@ -23,6 +24,7 @@ _ALIASES = {
     "snvc.models.submodule": "snvc_amd.models.submodule",
     "snvc.models.vernier": "snvc_amd.models.vernier",
     "snvc.models.loss3d": "snvc_amd.models.loss3d",
+    "snvc.models.FCmodel": "snvc_amd.models.FCmodel",
 }
 
 

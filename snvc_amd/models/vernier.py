@@ -13,6 +13,11 @@ reference checkpoint loads with ``strict=True``.  What changes is how ``forward`
   2D neck + heads (conv5, hm1, hm2, coord_head)        the same conv kernels in their depth-1 form
                                          :440-450       (SURVEY 8f N1), fused norm/bias/res/act
 
+With ``cfg.use_bbox_head`` (``BEV_type3`` only, as in the reference: vernier.py:33-36) the model carries ``bbox_head``, the
+residual MLP of ``snvc_amd.models.FCmodel``, and ``predict_3d_heatmaps`` returns its five-number box in the fifth slot.
+One deviation: ``forward`` then also returns it as ``'bbox'``.  The reference computes ``bboxes`` and drops them
+(vernier.py:520, :551-554), which leaves ``loss3d.BboxLoss`` nothing to read; without the head the dict is the reference's.
+
 The HRNet backbone comes from ``snvc_amd.models.hrnet`` (HIP convolutions and fusion kernel).  ``get_feat_extraction``
 is the same hook the reference uses (vernier.py:835-839): it builds HRNet for ``hrnet-w32`` / ``hrnet-w48``; assign
 another factory to it or pass ``feat_net=`` to the constructor.
@@ -69,8 +74,8 @@ class VernierScale(SplitModePolicy, nn.Module):
         self._init_grid()
         if cfg.vernier_type == "BEV_type3":       # reference vernier.py:33-36
             self._init_coord_head()
-        if getattr(self.cfg, "use_bbox_head", False):
-            raise NotImplementedError("use_bbox_head (FCmodel) is off by default and outside the path")
+            if getattr(self.cfg, "use_bbox_head", False):
+                self._init_bbox_head()
         for m in self.modules():  # reference vernier.py:38-54
             if isinstance(m, (nn.Conv3d, nn.Conv2d)):
                 nn.init.kaiming_normal_(m.weight, mode="fan_out", nonlinearity="relu")
@@ -93,6 +98,11 @@ class VernierScale(SplitModePolicy, nn.Module):
         modules.append(nn.Conv2d(num_chan * 2, num_chan * 2, kernel_size=(6, 4)))
         modules.append(nn.Sigmoid())
         self.coord_head = nn.Sequential(*modules)
+
+    def _init_bbox_head(self):
+        """reference vernier.py:95-96"""
+        from .FCmodel import get_fc_model
+        self.bbox_head = get_fc_model()
 
     def _init_grid(self):
         """reference vernier.py:99-114"""
@@ -376,7 +386,10 @@ class VernierScale(SplitModePolicy, nn.Module):
         else:
             voxel_BEV, occupancy, offset = self.trunk_3d(voxel)
         heatmaps, coordinates = self.heads_2d(voxel_BEV)
-        return heatmaps, occupancy.squeeze(1), offset, coordinates, None
+        bbox = None
+        if hasattr(self, "bbox_head"):                                            # :452-453
+            bbox = self.bbox_head(coordinates.reshape(len(heatmaps), -1))
+        return heatmaps, occupancy.squeeze(1), offset, coordinates, bbox
 
     def forward(self, left_roi, right_roi, grid_proj_left, grid_proj_right, meta_data=None, test=False):
         """reference vernier.py:460-555"""
@@ -391,7 +404,10 @@ class VernierScale(SplitModePolicy, nn.Module):
             if voxels is None:
                 voxels = self.construct_voxel(left_feat, right_feat, grid_proj_left, grid_proj_right)
         ncf, occupancy, part_offsets, coordinates, bboxes = self.predict_3d_heatmaps(voxels)
-        return {"ncf": ncf, "occupancy": occupancy, "coordinates": coordinates}
+        out = {"ncf": ncf, "occupancy": occupancy, "coordinates": coordinates}
+        if hasattr(self, "bbox_head"):
+            out["bbox"] = bboxes
+        return out
 
     def _aggregation_self_check(self, left_feat, right_feat, grid_proj_left, grid_proj_right, meta_data, voxel=None):
         """The numeric half of the reference's ``forward(test=True)`` (vernier.py:479-519; its matplotlib half is not
