@@ -29,6 +29,7 @@
 
 #include "common.hpp"
 #include "elementwise_internal.hpp"
+#include "snvc_fused.h"
 
 namespace snvc {
 namespace {
@@ -79,6 +80,32 @@ struct F16Args {
                                // layer (own weights each); 2: the 4 (depth, height) sub-grids of a dilation-2 layer
     int64_t cls_wstride;       // halves between the packed weights of consecutive classes (cls_mode 1)
     int64_t x_bs, y_bs, r_bs, yf_bs;   // batch strides in elements
+};
+
+// The channel-interleaved float32 layout (include/snvc_fused.h): [classes][C/8][H][pitch][8] per sample, column x at lp + x.
+// Float index of output channel oc (mode 0: oc = cls * C + co; mode 1: oc = co * 3 + cls) at (h, x); one definition for the
+// epilogue that writes the layout, the kernel that reads it and the host test (I: int on the device, where one sample stays below
+// 2^31 floats -- the launchers check that -- and 64-bit divisions would cost more than the stores).
+template <class I>
+__host__ __device__ __forceinline__ I il_index(int mode, I oc, I C, I H, I pitch, I lp, I cls0, I h, I x) {
+    const I cls = mode ? oc % 3 : oc / C, co = mode ? oc / 3 : oc % C, groups = (C + 7) / 8;
+    return ((((cls0 + cls) * groups + (co >> 3)) * H + h) * pitch + lp + x) * 8 + (co & 7);
+}
+
+// conv2d_x3q_kernel<Cfg, 1>: the fp32 result is written a second time, channel-interleaved
+struct F16IlArgs : F16Args {
+    float *y_il;
+    int64_t il_bs;             // floats between samples of y_il
+    int il_mode, il_C, il_pitch, il_lp, il_cls0;
+};
+
+// conv3d_x3q_kernel<EPI, 1>: the image is the sheared first layer's result, formed from its 2D operands (x / x_lo are not read)
+struct F16SrcArgs : F16Args {
+    const float *gi;           // [N][6][CGin][Hin][pitch][8]: G (classes 0..2) and G' (3..5), zero outside the rows
+    const float *p_il;         // [N][3][CGin][Hin][Win][8]: the left half's depth-class planes
+    const float *v_scale, *v_bias;      // the first layer's folded affine, [8 * CGin]
+    int64_t gi_bs;             // floats between samples of gi
+    int v_pitch, v_lp, v_q, v_m0, v_off, v_off2, v_flags;
 };
 
 // A-fragment register ring depth (k-steps ahead).  Measured on cfg5 (k7 / k5 / k3 ms): 2: 9.70 / 1.92 / 0.91;
@@ -705,6 +732,7 @@ conv3d_f16_kernel(const F16Args a_) {
 //   still in flight -- and no register load issued after it is consumed before the barrier that ends the chunk (FILL_STEP = 7 - PF):
 //   the refill has the last PF k-steps of MFMAs to land in.
 typedef float f32x4q __attribute__((ext_vector_type(4)));
+typedef _Float16 h4q __attribute__((ext_vector_type(4)));
 
 struct X3QCfg {
     static constexpr int TD = 4, TH = 4, NB = 4, IN_D = 6, IN_H = 6, IN_W = 34, VOX = IN_D * IN_H * IN_W, GB = VOX * 16;
@@ -726,9 +754,25 @@ __device__ __forceinline__ void wait_lgkm_for(h8 (&b)[8]) {
                  : "memory");
 }
 
-template <int EPI>      // 0: split C8 output; 3: + the side head (Cout == 32); 2 (r6): float32 NCDHW output (+ float32 residual, + statistics)
+// SRC 1 (the fused sheared first layer): nothing is fetched by DMA -- the workgroup FORMS the next chunk's image, the first layer's
+// result v1 = med3(fma(G + P, scale, bias)) as a split pair, and writes it into the other buffer with ds_write_b128, piece by piece
+// where the DMA would have put it.  Thread t < 204 owns image column (hh, ww) = (t / 34, t % 34) and walks its 6 depth positions in
+// twelve HALF pieces (4 channels of one plane): half piece j is formed among the first MFMAs of half-step j + 1 from the 16 bytes of
+// G (whose index drops by one per plane) and 16 of P (both channel-interleaved) fetched behind half piece j - 1's arithmetic in
+// half-step j, into the same registers; the second half completes the pair and writes it.  The scale sits in scalar registers.
+// Threads 204..255 repeat columns 0..51 (the same values to the same addresses: no divergence).  Nothing depends on the lane's
+// voxel being inside the tensor: coordinates are clamped into it (every address is that of a voxel of the tensor; gi is zero around
+// its rows, so an out-of-range G index reads the 0 the expand pass substitutes), and a voxel outside gets med3's bounds (0, 0): a
+// zero piece.  The arithmetic is sheared_expand_split_kernel's `emit`, operation for operation.
+template <int SRC, class A>
+__device__ __forceinline__ const F16SrcArgs &src_args_of(const A &a) {
+    if constexpr (SRC == 1) return a;
+    else return *reinterpret_cast<const F16SrcArgs *>(&a);
+}
+
+template <int EPI, int SRC = 0>      // EPI 0: split C8 output; 3: + the side head (Cout == 32); 2 (r6): float32 NCDHW output (+ float32 residual, + statistics)
 __global__ void __launch_bounds__(256, 2)
-conv3d_x3q_kernel(const F16Args a) {
+conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
     using Cfg = X3QCfg;
     constexpr int NB = Cfg::NB, TH = Cfg::TH, IN_H = Cfg::IN_H, IN_W = Cfg::IN_W, VOX = Cfg::VOX, NIT = Cfg::NIT, NQ = Cfg::NQ;
     constexpr int ITEMS = Cfg::ITEMS, PF = Cfg::PF;
@@ -805,7 +849,88 @@ conv3d_x3q_kernel(const F16Args a) {
     }
 
     const unsigned lds_base = (unsigned)(uintptr_t)(__attribute__((address_space(3))) char *)lds;
-    issue(0, 0);
+    // SRC 1: the state of this thread's image column (see the head comment); untouched, and removed, with SRC 0
+    constexpr int COLS = IN_H * IN_W;
+    const F16SrcArgs &aa = src_args_of<SRC>(a);      // SRC 0: never read
+    struct {
+        unsigned g_off, p_off, w_off, g_slab, p_slab;      // bytes
+        float hi, lo, vmax;
+        const char *gb, *pb;
+        f32x4q g, p, bi[2];      // the operands of one half piece (4 channels); the channel group's bias
+        float sc[8];             // the channel group's scale: uniform, held in scalar registers
+        h4q chi, clo;            // the first half piece, until the second completes the pair
+    } pr{};
+    auto prod_setup = [&]() {
+        const int cid = tid < COLS ? tid : tid - COLS;
+        const int hh = cid / IN_W, ww = cid - hh * IN_W;
+        const int gh = ih0 + hh, gw = iw0 + ww;
+        const bool col_ok = (unsigned)gh < (unsigned)aa.Hin && (unsigned)gw < (unsigned)aa.Win;
+        const int ghc = gh < 0 ? 0 : (gh < aa.Hin ? gh : aa.Hin - 1), gwc = gw < 0 ? 0 : (gw < aa.Win ? gw : aa.Win - 1);
+        const bool last = gwc == aa.Win - 1;
+        const int i0 = last ? aa.v_q * (aa.Win - 1) - aa.v_m0 + aa.v_off2 : aa.v_q * gwc - aa.v_m0 + aa.v_off;      // the G | G' index at d = 0
+        pr.g_off = (unsigned)((((last ? 3 * aa.CGin : 0) * aa.Hin + ghc) * aa.v_pitch + aa.v_lp + i0) * 32);
+        pr.p_off = (unsigned)((ghc * aa.Win + gwc) * 32);
+        pr.g_slab = (unsigned)(aa.Hin * aa.v_pitch * 32);
+        pr.p_slab = (unsigned)(aa.Hin * aa.Win * 32);
+        pr.w_off = (unsigned)(cid * 16);
+        pr.hi = col_ok ? 65504.0f : 0.0f;
+        pr.lo = (col_ok && !(aa.v_flags & SNVC_EPI_RELU)) ? -65504.0f : 0.0f;
+        pr.gb = reinterpret_cast<const char *>(aa.gi + n * aa.gi_bs);
+        pr.pb = reinterpret_cast<const char *>(aa.p_il + n * 3 * (int64_t)aa.CGin * aa.Hin * aa.Win * 8);
+    };
+    auto prod_affine = [&](int group) {      // per-lane loads of a uniform address: no scalar load enters the hand-counted loop
+        int z = 0;
+        asm volatile("" : "+v"(z));
+        const f32x4q *s = reinterpret_cast<const f32x4q *>(aa.v_scale + group * 8 + z), *b = reinterpret_cast<const f32x4q *>(aa.v_bias + group * 8 + z);
+        const f32x4q s0 = s[0], s1 = s[1];
+        pr.bi[0] = b[0]; pr.bi[1] = b[1];
+#pragma unroll
+        for (int e = 0; e < 8; ++e)
+            pr.sc[e] = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, e < 4 ? s0[e & 3] : s1[e & 3])));
+    };
+    // half piece j = 2 dd + half: channels 4 half .. 4 half + 3 of plane dd of the column
+    auto prod_load = [&](int group, int j) {
+        const int gd = id0 + (j >> 1);
+        const int gdc = gd < 0 ? 0 : (gd < aa.Din ? gd : aa.Din - 1);
+        const int cls = gdc == aa.Din - 1 ? 2 : (gdc == 0 ? 0 : 1);
+        const unsigned slab = (unsigned)(cls * aa.CGin + group);
+        pr.g = *reinterpret_cast<const f32x4q *>(pr.gb + (pr.g_off + (slab * pr.g_slab - (unsigned)gdc * 32u + 16u * (j & 1))));
+        pr.p = *reinterpret_cast<const f32x4q *>(pr.pb + (pr.p_off + (slab * pr.p_slab + 16u * (j & 1))));
+    };
+    auto prod_form = [&](int buf, int j) {
+        const int dd = j >> 1, half = j & 1;
+        const bool d_ok = (unsigned)(id0 + dd) < (unsigned)aa.Din;
+        const float hb = d_ok ? pr.hi : 0.0f, lb = d_ok ? pr.lo : 0.0f;
+        h4q o, ol;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float t = __builtin_fmaf(pr.g[e] + pr.p[e], pr.sc[4 * half + e], pr.bi[half][e]);
+            const float tc = __builtin_amdgcn_fmed3f(t, lb, hb);
+            pr.vmax = __builtin_fmaxf(pr.vmax, __builtin_fabsf(tc));
+            o[e] = (_Float16)tc;
+            ol[e] = (_Float16)(tc - (float)o[e]);
+        }
+        if (half == 0) {
+            pr.chi = o;
+            pr.clo = ol;
+        } else {
+            char *const dst = lds + pr.w_off + buf * Cfg::IMG_BYTES + dd * (COLS * 16);
+            *reinterpret_cast<h8 *>(dst) = __builtin_shufflevector(pr.chi, o, 0, 1, 2, 3, 4, 5, 6, 7);
+            *reinterpret_cast<h8 *>(dst + Cfg::PLANE_BYTES) = __builtin_shufflevector(pr.clo, ol, 0, 1, 2, 3, 4, 5, 6, 7);
+        }
+    };
+    constexpr int NHP = 2 * Cfg::IN_D;      // half pieces per column and chunk
+    if constexpr (SRC == 1) {
+        prod_setup();
+        prod_affine(0);
+#pragma unroll
+        for (int j = 0; j < NHP; ++j) {
+            prod_load(0, j);
+            prod_form(0, j);
+        }
+    } else {
+        issue(0, 0);
+    }
     __syncthreads();
     // The LAST chunk is a copy of the loop body of its own (LAST is a constant in it): it has no next chunk to fetch fragments for, so
     // from k-step FILL_STEP on it requests nothing of the weights (they were 8 KB of the next block's fragments or padding per wave,
@@ -838,7 +963,7 @@ conv3d_x3q_kernel(const F16Args a) {
                     // every weight fragment in flight lands first: none is waited for between here and the barrier
 #pragma unroll
                     for (int i = 0; i < PF; ++i) asm volatile("" ::"v"(q_[i][0]), "v"(q_[i][1]), "v"(q_[i][2]), "v"(q_[i][3]));
-                    if constexpr (!LAST) issue(chunk + 1, (chunk + 1) & 1);
+                    if constexpr (!LAST && SRC == 0) issue(chunk + 1, (chunk + 1) & 1);
                 }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) af[m] = q_[0][m];
@@ -846,6 +971,9 @@ conv3d_x3q_kernel(const F16Args a) {
                 for (int i = 0; i + 1 < PF; ++i)
 #pragma unroll
                     for (int m = 0; m < 4; ++m) q_[i][m] = q_[i + 1][m];
+                if constexpr (!LAST && SRC == 1) {      // once per chunk: the next channel group's affine
+                    if (hs == 0) prod_affine(chunk + 1);
+                }
                 if constexpr (!LAST) {
 #pragma unroll
                     for (int m = 0; m < 4; ++m) q_[PF - 1][m] = wq[m * 64];      // from k-step FILL_STEP on: fragments of the NEXT chunk
@@ -875,6 +1003,14 @@ conv3d_x3q_kernel(const F16Args a) {
                 wait_lgkm_for<0>(bfr[cur]);
             }
             __builtin_amdgcn_sched_barrier(0);
+            // SRC 1: half piece hs - 1 of the next image is formed among this half-step's MFMAs from the operands fetched in the last one, then
+            // half piece hs's operands are fetched into the same registers; a completed pair is written behind the wait above, in front of
+            // the next half-step's reads: `lgkmcnt(8)` there still names exactly the 8 reads issued last
+            constexpr bool FORM = !LAST && SRC == 1;
+            if constexpr (FORM) {
+                if (hs >= 1 && hs <= NHP) prod_form((chunk + 1) & 1, hs - 1);
+                if (hs < NHP) prod_load(chunk + 1, hs);
+            }
 #pragma unroll
             for (int term = 0; term < 3; ++term)
 #pragma unroll
@@ -888,12 +1024,26 @@ conv3d_x3q_kernel(const F16Args a) {
                             acc[2 * (hs & 1) + rr][ph][h] =
                                 __builtin_amdgcn_mfma_f32_16x16x32_f16(aw, bx, acc[2 * (hs & 1) + rr][ph][h], 0, 0, 0);
                         }
+            if constexpr (FORM) {
+                if (hs >= 1 && hs <= NHP) {
+#pragma unroll
+                    for (int k = 0; k < 12; ++k) {      // the VALU work between the first MFMAs, the fetches behind it, the rest of the MFMAs under them
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);
+                    }
+                    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
+                }
+            }
             __builtin_amdgcn_sched_barrier(0);
         }
-        __syncthreads();     // drains the DMA of the next chunk and retires every read of this chunk's buffer
+        __syncthreads();     // drains the DMA of the next chunk and retires every read (SRC 1: every write) of the buffers
     };
     for (int chunk = 0; chunk + 1 < a.nchunks; ++chunk) run_chunk(chunk, std::false_type{});
     run_chunk(a.nchunks - 1, std::true_type{});
+    if constexpr (SRC == 1) {      // the expand pass's flag: a stored |v1| at half's limit (halo voxels are other tiles' own: same OR)
+        if (pr.vmax >= 65504.0f && a.overflow) atomicOr(a.overflow, 1);
+    }
     // the constants are waited for HERE, in front of the first store: a value first read behind a store (the compiler sinks the side
     // head's sum there) is waited for with vmcnt(0), i.e. until the wave's own stores are acknowledged
     if (has_aff) asm volatile("" ::"v"(epc[0]), "v"(epc[1]), "v"(epc[2]), "v"(epc[3]));
@@ -1024,9 +1174,10 @@ struct X2QCfg {
     static_assert(NQ > PF, "the refill is issued PF k-steps before the chunk ends");
 };
 
-template <class Cfg>
+// IL 1: the result is written a second time in the channel-interleaved layout (il_index) the fused first layer reads.
+template <class Cfg, int IL = 0>
 __global__ void __launch_bounds__(256, 2)
-conv2d_x3q_kernel(const F16Args a) {
+conv2d_x3q_kernel(const std::conditional_t<IL == 1, F16IlArgs, F16Args> a) {
     constexpr int NB = Cfg::NB, IN_W = Cfg::IN_W, VOX = Cfg::VOX, NIT = Cfg::NIT, NQ = Cfg::NQ;
     constexpr int ITEMS = Cfg::ITEMS, PF = Cfg::PF;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -1177,11 +1328,24 @@ conv2d_x3q_kernel(const F16Args a) {
             const int pw = ow0 + 16 * ph + col;
             if (phh < a.nh && pw < a.nw) {
                 float *yp = yn + (int64_t)phh * a.Wout + pw;
+                float v8[8];
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     float v = __builtin_fmaf(acc[nb][ph][e >> 2][e & 3], sc[e], bi[e]);
                     if (relu) v = __builtin_fmaxf(v, 0.0f);
                     yp[e * out_hw] = v;
+                    v8[e] = v;
+                }
+                if constexpr (IL == 1) {
+                    float *il = a.y_il + n * a.il_bs;
+                    if (a.il_mode == 0) {      // class-major, C % 8 == 0: the lane's 8 channels are one channel group
+                        float *dst = il + il_index<int>(0, c0, a.il_C, a.Hout, a.il_pitch, a.il_lp, a.il_cls0, phh, pw);
+                        *reinterpret_cast<f32x4q *>(dst) = f32x4q{v8[0], v8[1], v8[2], v8[3]};
+                        *reinterpret_cast<f32x4q *>(dst + 4) = f32x4q{v8[4], v8[5], v8[6], v8[7]};
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) il[il_index<int>(1, c0 + e, a.il_C, a.Hout, a.il_pitch, a.il_lp, a.il_cls0, phh, pw)] = v8[e];
+                    }
                 }
             }
         }
@@ -2372,7 +2536,7 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const void *x_hi, const void
                          const float *scale, const float *bias, const void *res_hi, const void *res_lo, void *y_hi,
                          void *y_lo, float *y_f32, const float *head, float *y_head, float head_mul, float res_mul,
                          int *overflow, const void *tail_w, float *t_out, float tail_mul, void *stream, double *stats = nullptr,
-                         int64_t *stats_slots = nullptr, const float *x_mul = nullptr) {
+                         int64_t *stats_slots = nullptr, const float *x_mul = nullptr, const snvc::F16SrcArgs *src = nullptr) {
     using namespace snvc;
     F16Plan p;
     if (!d) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: null desc");
@@ -2385,7 +2549,7 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const void *x_hi, const void
     const bool plane = d->Cout == 1;              // the occupancy head: y_f32 is then the fp32 plane [N][1][D][H][W] (Sigmoid honoured)
     const bool to_f32 = y_f32 != nullptr;
     if (plane && !to_f32) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: a one-channel layer writes y_f32");
-    if (!x_hi || !x_lo || !packed_weight || (!tail && !to_f32 && (!y_hi || !y_lo)))
+    if ((!src && (!x_hi || !x_lo)) || !packed_weight || (!tail && !to_f32 && (!y_hi || !y_lo)))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: null pointer");
     if ((scale == nullptr) != (bias == nullptr))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: scale and bias must both be given or both be NULL");
@@ -2477,6 +2641,8 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const void *x_hi, const void
             if (e != hipSuccess) return fail(SNVC_ERR_HIP, "snvc_f16x3_conv3d_forward_stats: hipMemsetAsync failed");
         }
     }
+    if (src && p.kind != FK3XQ)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a 3x3x3 stride-1 layer on the 16x16x32 form (SNVC_ALGO_X3_Q16)");
 #define SNVC_X3_LAUNCH(CFG) do { if (to_f32) launch_f16<CFG, 2>(a, grid, st); else launch_f16<CFG, 0>(a, grid, st); } while (0)
     switch (p.kind) {
         case FK3X:
@@ -2529,6 +2695,14 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const void *x_hi, const void
             if (resflags || (to_f32 && head)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: the 16x16x32 form has no split residual, no side head beside a float32 result");
             if (ntiles * p.cblocks >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles");
             grid = dim3((unsigned)(ntiles * p.cblocks), 1, (unsigned)d->N);      // (tile, channel block) jobs, channel block fastest
+            if (src) {      // the fused sheared first layer: the image is formed in the launch
+                if (to_f32) return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a split C8 output");
+                F16SrcArgs b = *src;
+                static_cast<F16Args &>(b) = a;
+                if (head) launch_lds<conv3d_x3q_kernel<3, 1>>(grid, 256, X3QCfg::LDS_BYTES, st, b);
+                else launch_lds<conv3d_x3q_kernel<0, 1>>(grid, 256, X3QCfg::LDS_BYTES, st, b);
+                break;
+            }
             if (to_f32) launch_lds<conv3d_x3q_kernel<2>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
             else if (head) launch_lds<conv3d_x3q_kernel<3>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
             else launch_lds<conv3d_x3q_kernel<0>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
@@ -2546,6 +2720,32 @@ int snvc_f16x3_conv3d_forward(const snvc_conv3d_desc *d, const void *x_hi, const
                               int *overflow, void *stream) {
     return f16x3_forward(d, x_hi, x_lo, packed_weight, scale, bias, res_hi, res_lo, y_hi, y_lo, y_f32, head, y_head, head_mul, res_mul,
                          overflow, nullptr, nullptr, 0.0f, stream);
+}
+
+int snvc_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias, void *y_hi,
+                                    void *y_lo, const float *head, float *y_head, float head_mul, int *overflow, const float *gi,
+                                    int64_t pitch, int64_t lp, const float *p_il, const float *v_scale, const float *v_bias, int q, int m0,
+                                    int off, int off2, int v_flags, void *stream) {
+    using namespace snvc;
+    if (!d || !gi || !p_il || !v_scale || !v_bias) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_first_conv3d_forward: null pointer");
+    if (d->transposed || d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->dilation != 1 || d->Cin % 8 || d->Din < 1 || d->Hin < 1 || d->Win < 1 ||
+        (q != 1 && q != 2) || (v_flags & ~SNVC_EPI_RELU))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a 3x3x3 / stride 1 / pad 1 layer, Cin % 8 == 0, q = 1 | 2");
+    if ((reinterpret_cast<uintptr_t>(gi) | reinterpret_cast<uintptr_t>(p_il) | reinterpret_cast<uintptr_t>(v_scale) | reinterpret_cast<uintptr_t>(v_bias)) & 31)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_first_conv3d_forward: gi / p_il / v_scale / v_bias must be 32-byte aligned");
+    // every G | G' index of a voxel of the tensor stays inside a (zero-padded) row of gi
+    const int64_t D = d->Din, H = d->Hin, W = d->Win, CG = d->Cin / 8;
+    const int64_t lo_g = -(D - 1) - m0 + off, hi_g = (int64_t)q * (W - 2) - m0 + off;
+    const int64_t lo_c = (int64_t)q * (W - 1) - (D - 1) - m0 + off2, hi_c = (int64_t)q * (W - 1) - m0 + off2;
+    if (lp < 0 || pitch <= 0 || lp + lo_c < 0 || lp + hi_c >= pitch || (W > 1 && (lp + lo_g < 0 || lp + hi_g >= pitch)))
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_first_conv3d_forward: pitch / lp do not cover the G indices of this shape");
+    if (6 * CG * H * pitch * 32 >= ((int64_t)1 << 31) || 3 * CG * H * W * 32 >= ((int64_t)1 << 31))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: one sample of gi / p_il must stay below 2 GiB");
+    F16SrcArgs s{};
+    s.gi = gi; s.p_il = p_il; s.v_scale = v_scale; s.v_bias = v_bias; s.gi_bs = 6 * CG * H * pitch * 8;
+    s.v_pitch = (int)pitch; s.v_lp = (int)lp; s.v_q = q; s.v_m0 = m0; s.v_off = off; s.v_off2 = off2; s.v_flags = v_flags;
+    return f16x3_forward(d, nullptr, nullptr, packed_weight, scale, bias, nullptr, nullptr, y_hi, y_lo, nullptr, head, y_head, head_mul, 1.0f,
+                         overflow, nullptr, nullptr, 0.0f, stream, nullptr, nullptr, nullptr, &s);
 }
 
 // slots per sample of the statistics epilogue = (z classes) * gridDim.x * 4 waves, as f16x3_forward lays its grid out
@@ -2640,9 +2840,26 @@ int snvc_f16x3_conv2d_pack_weights(const float *weight, int cout, int cin, int k
     return check_launch("snvc_f16x3_conv2d_pack_weights");
 }
 
+// the interleaved second output of a depth-1 layer (include/snvc_fused.h): C = Cout / 3 channels in 3 classes
+struct snvc_il_out {
+    float *y_il;
+    int64_t bs, pitch, lp, cls0, classes;
+    int mode;
+};
+
+static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
+                                float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
+                                const float *x_mul_dev, int flags, void *stream, const snvc_il_out *il);
+
 int snvc_f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
                               float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
                               const float *x_mul_dev, int flags, void *stream) {
+    return f16x3_conv2d_forward(x_hi, x_lo, packed_weight, scale, bias, y, N, Cin, Cout, H, W, kh, kw, out_mul, x_mul_dev, flags, stream, nullptr);
+}
+
+static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
+                                float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
+                                const float *x_mul_dev, int flags, void *stream, const snvc_il_out *il) {
     using namespace snvc;
     if (N < 0 || H <= 0 || W <= 0 || snvc_f16x3_conv2d_packed_weight_bytes((int)Cout, (int)Cin, kh, kw) < 0)
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv2d_forward: 3x7 or 3x3 kernels, Cin % 8 == 0, Cout % 32 == 0");
@@ -2669,7 +2886,23 @@ int snvc_f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *pa
     if (jobs >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv2d_forward: too many tiles");
     const dim3 grid((unsigned)jobs, 1, (unsigned)N);
     hipStream_t st = as_stream(stream);
-    if (kw == 7) {
+    if (il) {
+        const int64_t C = Cout / 3, need = il->classes * ((C + 7) / 8) * H * il->pitch * 8;
+        if (!il->y_il || Cout % 3 || (il->mode == 0 && C % 8) || il->lp < 0 || il->lp + W > il->pitch || il->cls0 < 0 || il->cls0 + 3 > il->classes ||
+            need > il->bs || need >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(il->y_il) & 31) || il->bs % 8)
+            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused: the interleaved output does not hold the layer's result");
+        F16IlArgs b{};
+        static_cast<F16Args &>(b) = a;
+        b.y_il = il->y_il; b.il_bs = il->bs; b.il_mode = il->mode; b.il_C = (int)C; b.il_pitch = (int)il->pitch; b.il_lp = (int)il->lp;
+        b.il_cls0 = (int)il->cls0;
+        if (kw == 7) {
+            using C7 = X2QCfg<3, 7>;
+            launch_lds<conv2d_x3q_kernel<C7, 1>>(grid, 256, C7::LDS_BYTES, st, b);
+        } else {
+            using C3 = X2QCfg<3, 3>;
+            launch_lds<conv2d_x3q_kernel<C3, 1>>(grid, 256, C3::LDS_BYTES, st, b);
+        }
+    } else if (kw == 7) {
         using C = X2QCfg<3, 7>;
         launch_lds<conv2d_x3q_kernel<C>>(grid, 256, C::LDS_BYTES, st, a);
     } else {
@@ -2683,10 +2916,34 @@ int snvc_f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *pa
 // sync the GPU is empty, and five Python-level launches of 5-20 us kernels starve it (measured: +0.08-0.14 ms per step against
 // the same kernels queued by a host that runs ahead).
 extern "C" int snvc_sheared_upsample_split(const float *, void *, void *, const float *, int64_t, int64_t, int64_t, int64_t, int, int64_t, int, void *);
+static int sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
+                           const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
+                           void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, void *stream, float *gi, int64_t pitch,
+                           int64_t lp);
+
 int snvc_sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
                          const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
                          void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, void *stream) {
+    return sheared_prep_x3(right, N, C, H, W, q, WU, off, WU2, off2, packed_g, packed_col, Cout3, out_mul_g, out_mul_col, rq_split, rq2_split,
+                           scratch8, mul_dev, g, gcol, stream, nullptr, 0, 0);
+}
+
+int snvc_fused_sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2,
+                               int off2, const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col,
+                               void *rq_split, void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, float *gi,
+                               int64_t pitch, int64_t lp, void *stream) {
+    if (!gi || Cout3 != 3 * C) return snvc::fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_sheared_prep_x3: gi is NULL or Cout3 != 3 * C");
+    return sheared_prep_x3(right, N, C, H, W, q, WU, off, WU2, off2, packed_g, packed_col, Cout3, out_mul_g, out_mul_col, rq_split, rq2_split,
+                           scratch8, mul_dev, g, gcol, stream, gi, pitch, lp);
+}
+
+static int sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
+                           const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
+                           void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, void *stream, float *gi, int64_t pitch,
+                           int64_t lp) {
     using namespace snvc;
+    const int64_t gi_bs = 6 * (C / 8) * H * pitch * 8;
+    const snvc_il_out il_g{gi, gi_bs, pitch, lp, 0, 6, 0}, il_col{gi, gi_bs, pitch, lp, 3, 6, 0};
     if (!right || !packed_g || !packed_col || !rq_split || !rq2_split || !scratch8 || !mul_dev || !g || !gcol)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_prep_x3: null pointer");
     if (N <= 0 || C % 8 || Cout3 % 32) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_prep_x3: C % 8 == 0, 3 * Cout % 32 == 0");
@@ -2696,12 +2953,37 @@ int snvc_sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, in
     _Float16 *a = reinterpret_cast<_Float16 *>(rq_split), *b = reinterpret_cast<_Float16 *>(rq2_split);
     rc = snvc_sheared_upsample_split(right, a, a + G * H * WU * 8, mul_dev, N, C, H, W, q, WU, off, stream);
     if (rc) return rc;
-    rc = snvc_f16x3_conv2d_forward(a, a + G * H * WU * 8, packed_g, nullptr, nullptr, g, N, C, Cout3, H, WU, 3, 7, out_mul_g, mul_dev, 0, stream);
+    rc = f16x3_conv2d_forward(a, a + G * H * WU * 8, packed_g, nullptr, nullptr, g, N, C, Cout3, H, WU, 3, 7, out_mul_g, mul_dev, 0, stream,
+                              gi ? &il_g : nullptr);
     if (rc) return rc;
     rc = snvc_sheared_upsample_split(right, b, b + G * H * WU2 * 8, mul_dev, N, C, H, W, q, WU2, off2, stream);
     if (rc) return rc;
-    return snvc_f16x3_conv2d_forward(b, b + G * H * WU2 * 8, packed_col, nullptr, nullptr, gcol, N, C, Cout3, H, WU2, 3, 7, out_mul_col, mul_dev, 0,
-                                     stream);
+    return f16x3_conv2d_forward(b, b + G * H * WU2 * 8, packed_col, nullptr, nullptr, gcol, N, C, Cout3, H, WU2, 3, 7, out_mul_col, mul_dev, 0,
+                                stream, gi ? &il_col : nullptr);
+}
+
+int snvc_fused_abi_version(void) { return 1; }
+
+int64_t snvc_fused_il_index(int mode, int64_t oc, int64_t C, int64_t H, int64_t pitch, int64_t lp, int64_t cls0, int64_t h, int64_t x) {
+    if ((mode != 0 && mode != 1) || C <= 0 || oc < 0 || oc >= 3 * C || H <= 0 || h < 0 || h >= H || lp < 0 || x < 0 || lp + x >= pitch || cls0 < 0)
+        return -1;
+    return snvc::il_index<int64_t>(mode, oc, C, H, pitch, lp, cls0, h, x);
+}
+
+extern "C" int snvc_f16x3_from_ncdhw(const float *, void *, void *, int64_t, int64_t, int64_t, int64_t, int64_t, float, const float *, void *);
+int snvc_fused_planes_from_f32(const float *x, int64_t N, int64_t C, int64_t H, int64_t W, const void *packed, int64_t cout, float out_mul,
+                               float *y, float *p_il, void *ws_split, void *scratch8, float *mul_dev, void *stream) {
+    using namespace snvc;
+    if (!x || !packed || !y || !p_il || !ws_split || !scratch8 || !mul_dev)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_planes_from_f32: null pointer");
+    if (N <= 0 || C % 8 || cout != 3 * C) return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_planes_from_f32: C % 8 == 0, cout == 3 * C");
+    int rc = snvc_f16x3_split_scale(x, N * C * H * W, scratch8, mul_dev, stream);
+    if (rc) return rc;
+    _Float16 *a = reinterpret_cast<_Float16 *>(ws_split);
+    rc = snvc_f16x3_from_ncdhw(x, a, a + C * H * W, N, C, H * W, 0, 0, 1.0f, mul_dev, stream);
+    if (rc) return rc;
+    const snvc_il_out il{p_il, 3 * (C / 8) * H * W * 8, W, 0, 0, 3, 1};
+    return f16x3_conv2d_forward(a, a + C * H * W, packed, nullptr, nullptr, y, N, C, cout, H, W, 3, 3, out_mul, mul_dev, 0, stream, &il);
 }
 
 // n_layers depth-1 split layers of ONE fp32 [N][C][H][W] input in one host call: its scale, its split pair (ws: N*2*C*H*W halves), then

@@ -103,6 +103,8 @@ class GlobalStack(SplitModePolicy, nn.Module):
         in split mode and the workspace holds the (hi, lo) pair) -- for tests and debugging."""
         ws = self.__dict__.get("_snvc_ws", {})
         which = self.__dict__.get("_snvc_last_v1", "v1")
+        if which == "v1s_lazy":      # the fused route never stored it: the expand pass on the operands the call left in the prep workspace
+            return ops.from_split(ws[("v1s_lazy", (), None)](), self.__dict__["_snvc_x3"]["exp"]["v1"])
         for k, v in ws.items():
             if k[0] == which:
                 return ops.from_split(v, self.__dict__["_snvc_x3"]["exp"]["v1"]) if which == "v1s" else v
@@ -137,6 +139,10 @@ class GlobalStack(SplitModePolicy, nn.Module):
     # 165 us back to back) but the step LOSES 0.013 ms (tools/ab_step.py, profiles/r5/ab_step_v5.txt): conv2 reads the pair right
     # behind it.  Off.
     stream_out = False
+    # split mode, sheared route, q = 1 | 2: conv2's launch forms the first layer's result itself from G | G' and the left planes
+    # (csrc/conv3d_f16.hip, conv3d_x3q_kernel<EPI, 1>): the expand pass, its 0.74 GB pair and conv2's reads of it are gone.  Same bits.
+    # False: the expand pass writes the pair, conv2 reads it (every other route does that anyway).
+    fused_first = True
     split_prep = True    # split mode: the sheared first layer's depth-1 3 x 7 layers (G, G') on the half pipe too (False: fp32 MFMA, as r4)
     fused_tail = True    # split mode: conv5's epilogue contracts its result with the folded one-channel tail (False: r4's two launches)
 
@@ -215,16 +221,26 @@ class GlobalStack(SplitModePolicy, nn.Module):
             return None
         return st if self.split_guard(device, mode) is not None else None      # None: overflow_check = "deferred", the previous call's flag
 
-    def _tail_x3(self, st, v1s, timing=None):
+    def _tail_x3(self, st, v1s, timing=None, fused=None):
         """conv2 (+ side head) -> hourglass -> folded one-channel tail on a split-C8 first-layer result ``v1s`` (exponent
-        st['exp']['v1']).  Full-resolution intermediates: v1s, v2s (0.74 GB each at cfg2, like their fp32 counterparts)."""
+        st['exp']['v1']).  Full-resolution intermediates: v1s, v2s (0.74 GB each at cfg2, like their fp32 counterparts).
+        ``fused`` (then ``v1s`` is None): ``(shape, device, kwargs)`` of ``Conv3dLayerX3.forward_fused_first`` -- conv2 forms v1s itself."""
         L, A, E, flag = st["layers"], st["affine"], st["exp"], st["flag"]
-        n, dev = v1s.size(0), v1s.device
-        d, h, w = v1s.shape[3:6]
+        if fused is not None:
+            (n, _, d, h, w), dev = fused[0], fused[1]
+        else:
+            n, dev = v1s.size(0), v1s.device
+            d, h, w = v1s.shape[3:6]
         hg = self.hg_conv3d
         _mark(timing, "conv2", 0)
-        v2s, hv = L["conv2"](v1s, E["v1"], *A["conv2"], flags=EPI_RELU, out_exp=E["conv2"], head=self.classifier.weight, overflow=flag,
-                             out=self._buffer("v2s", (n, 2, 4, d, h, w, 8), dev, torch.float16))
+        v2_out = self._buffer("v2s", (n, 2, 4, d, h, w, 8), dev, torch.float16)
+        if fused is not None:
+            v2s, hv = L["conv2"].forward_fused_first(n=n, in_sp=(d, h, w), x_exp=E["v1"], scale=A["conv2"][0], bias=A["conv2"][1], flags=EPI_RELU,
+                                                     out_exp=E["conv2"], head=self.classifier.weight, overflow=flag, out=v2_out, **fused[2])
+            _ROUTES["fused_first_conv"] += 1
+        else:
+            v2s, hv = L["conv2"](v1s, E["v1"], *A["conv2"], flags=EPI_RELU, out_exp=E["conv2"], head=self.classifier.weight, overflow=flag,
+                                 out=v2_out)
         _mark(timing, "conv2", 1)
         _ROUTES["side_head"] += 1
         o = L["h1"](v2s, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)                  # 1/2 res, 2C channels
@@ -780,8 +796,16 @@ class GlobalStack(SplitModePolicy, nn.Module):
             lx = plans.get("left2d_x3")
             if lx is None:
                 lx = plans["left2d_x3"] = ops.Conv2dLayerX3(self._left_planes_weight(w.detach()[:, :c]))
-            planes = ops.conv2d_x3_from_f32(left, [lx], prep_ws.setdefault("planes", {}))[0]
+            # the fused first layer (fused_first) reads the planes channel-interleaved: a second output of the same launch
+            st_f = self._x3_select(left.device, arithmetic)
+            fuse = bool(self.fused_first and sheared and conv.out_channels == c and isinstance(bn, nn.BatchNorm3d) and left.size(0) > 0
+                        and st_f["layers"]["conv2"].fused_first_form(left.size(0), (shift.size(1),) + tuple(left.shape[2:])))
+            if fuse:
+                planes, p_il = ops.planes_x3_il(left, lx, prep_ws.setdefault("planes_il", {}))
+            else:
+                planes = ops.conv2d_x3_from_f32(left, [lx], prep_ws.setdefault("planes", {}))[0]
         else:
+            fuse = False
             planes = self._left_planes_layer(plans, w.detach()[:, :c])(left.unsqueeze(2))   # [N,3C,1,H,W] ...
         planes = planes.view(left.size(0), c, 3, left.size(2), left.size(3))                 # ... = [N,C,3,H,W]: first / interior / last
         shape = (left.size(0), c, shift.size(1)) + tuple(left.shape[2:])
@@ -794,14 +818,20 @@ class GlobalStack(SplitModePolicy, nn.Module):
                 lx_g, lx_col = self._sheared_layers_x3(plans, w.detach()[:, c:], q)
                 # one host call for the five launches (behind the step's host sync the GPU is empty: five Python-level launches of
                 # 5-20 us kernels starve it); G / G' live in a per-model workspace until this call's expand pass has read them
+                if fuse and q in (1, 2):      # G | G' also channel-interleaved, zero around the rows: what conv2's launch reads
+                    pitch, lp = ops.fused_il_geometry(q, m0, shift.size(1), left.size(3), wu, off, wu_col, off_col)
+                    g, gcol, gi = ops.sheared_prep_x3_il(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep_ws.setdefault("sheared_il", {}),
+                                                         pitch, lp)
+                    _ROUTES["sheared_prep_x3"] += 1
+                    return g, gcol, off, off_col, (gi, pitch, lp)
                 g, gcol = ops.sheared_prep_x3(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep_ws.setdefault("sheared", {}))
                 _ROUTES["sheared_prep_x3"] += 1
-                return g, gcol, off, off_col
+                return g, gcol, off, off_col, None
             lay_g, lay_col = self._sheared_layers(plans, w.detach()[:, c:], q)
             if not self.prep_streams:
                 g = lay_g(ops.sheared_upsample(right, q, wu, off).unsqueeze(2)).squeeze(2)             # [N,3C,H,WU]
                 gcol = lay_col(ops.sheared_upsample(right, q, wu_col, off_col).unsqueeze(2)).squeeze(2)   # [N,3C,H,WU2]
-                return g, gcol, off, off_col
+                return g, gcol, off, off_col, None
             # r5: G and G' are two independent chains of small launches (an upsample + a depth-1 convolution of ~100 workgroups each:
             # their time is one workgroup's latency, not throughput) beside the left half's planes already queued on this stream.
             # They run on two side streams and join before the expand pass: three chains side by side instead of end to end.
@@ -820,7 +850,7 @@ class GlobalStack(SplitModePolicy, nn.Module):
                 out.append((t, done))
             for _, done in out:
                 cur.wait_event(done)
-            return out[0][0], out[1][0], off, off_col
+            return out[0][0], out[1][0], off, off_col, None
 
         def commuted_inputs():
             # any other shift array: three 2D convolutions of the right feature (P, Q) and of its first columns (E)
@@ -871,10 +901,26 @@ class GlobalStack(SplitModePolicy, nn.Module):
             if ready is None or tuple(guess[:2]) != tuple(structure):
                 _mark(timing, "volume", 0)
                 ready = sheared_inputs(q, m0)    # first call, or the spacing changed: the guess is dropped
-            g, gcol, off, off_col = ready
+            g, gcol, off, off_col, il = ready
             _mark(timing, "volume", 1)
             _mark(timing, "conv1", 0)
             st = self._x3_select(left.device, arithmetic)
+            if st is not None and il is not None:
+                # the fused first layer: nothing runs here -- conv2's launch (the "conv2" marks) forms the pair itself
+                _mark(timing, "conv1", 1)
+                _ROUTES["sheared_first_conv"] += 1
+                v1_sc, v1_bi = self._x3_v1_affine(st, scale, bias)
+
+                def expand():      # last_first_layer(): the pair, from the operands this call leaves in the prep workspace
+                    t = self._buffer("v1s", (shape[0], 2, c // 8) + tuple(shape[2:]) + (8,), left.device, torch.float16)
+                    ops.sheared_expand_split(g, gcol, planes, v1_sc, v1_bi, t, q, m0, off, off_col, ops.EPI_RELU, None)
+                    return t
+                self.__dict__["_snvc_ws"] = self.__dict__.get("_snvc_ws", {})
+                self.__dict__["_snvc_ws"][("v1s_lazy", (), None)] = expand
+                self.__dict__["_snvc_last_v1"] = "v1s_lazy"
+                return self._tail_x3(st, None, timing, fused=(shape, left.device, dict(
+                    gi=il[0], pitch=il[1], lp=il[2], p_il=p_il, v_scale=v1_sc, v_bias=v1_bi, q=q, m0=m0, off=off, off_col=off_col,
+                    v_flags=ops.EPI_RELU)))
             if st is not None and c % 8 == 0:
                 # split mode: the expand pass writes the (hi, lo) pair conv2 reads (same bytes as the fp32 tensor, no layout pass)
                 v1s = self._buffer("v1s", (shape[0], 2, c // 8) + tuple(shape[2:]) + (8,), left.device, torch.float16)

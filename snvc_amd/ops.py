@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _derived, _lib
+from . import _derived, _fused, _lib
 from ._lib import (EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID, EPI_STREAM_OUT, F32, F64, Conv3dDesc,
                    Unsupported, check)
 
@@ -1623,6 +1623,71 @@ def conv2d_x3_from_f32(x, layers, ws: dict):
     return ws["y"]
 
 
+# ---- the fused sheared first layer (include/snvc_fused.h): conv2 forms its own input from the first layer's 2D operands
+
+def il_index(mode: int, oc: int, c: int, h_dim: int, pitch: int, lp: int, cls0: int, h: int, x: int) -> int:
+    """Float index of output channel ``oc`` at (h, x) in one sample of a channel-interleaved buffer (snvc_fused_il_index: the
+    function the kernels use)."""
+    return int(_fused.lib().snvc_fused_il_index(mode, oc, c, h_dim, pitch, lp, cls0, h, x))
+
+
+def fused_il_geometry(q: int, m0: int, d: int, w: int, wu: int, off: int, wu_col: int, off_col: int):
+    """(pitch, lp) of the interleaved G | G' buffer: every index q*w - d - m0 + off (w < W - 1) and q*(W-1) - d - m0 + off_col of a
+    voxel of the [d, ., w] tensor, and every column the two layers write, lies in [0, pitch) once shifted by lp."""
+    lo = min(0, q * (w - 1) - (d - 1) - m0 + off_col, -(d - 1) - m0 + off if w > 1 else 0)
+    hi = max(wu - 1, wu_col - 1, q * (w - 1) - m0 + off_col, q * (w - 2) - m0 + off if w > 1 else 0)
+    return hi - lo + 1, -lo
+
+
+def sheared_prep_x3_il(right, q: int, wu: int, off: int, wu_col: int, off_col: int, lay_g: "Conv2dLayerX3", lay_col: "Conv2dLayerX3", ws: dict,
+                       pitch: int, lp: int):
+    """``sheared_prep_x3`` whose two 3 x 7 layers also write G | G' as the channel-interleaved buffer ``gi`` [N,6,C/8,H,pitch,8]
+    (snvc_fused_sheared_prep_x3; zero outside the rows, zeroed once per shape).  Returns (g, gcol, gi)."""
+    _gpu(right, "right")
+    right = right.contiguous()
+    n, c, h, w = right.shape
+    key = (n, c, h, w, wu, wu_col, pitch, lp, right.device)
+    if ws.get("key") != key:
+        dev = right.device
+        ws.clear()
+        ws.update(key=key, rq=torch.empty(n * 2 * c * h * wu, dtype=torch.float16, device=dev),
+                  rq2=torch.empty(n * 2 * c * h * wu_col, dtype=torch.float16, device=dev), mul=torch.empty(1, dtype=torch.float32, device=dev),
+                  g=torch.empty((n, lay_g.cout, h, wu), dtype=torch.float32, device=dev),
+                  gcol=torch.empty((n, lay_col.cout, h, wu_col), dtype=torch.float32, device=dev),
+                  gi=torch.zeros((n, 6, c // 8, h, pitch, 8), dtype=torch.float32, device=dev))
+    scratch = _scale_scratch(right.device)
+    with torch.cuda.device(right.device):
+        check(_fused.lib().snvc_fused_sheared_prep_x3(_ptr(right), n, c, h, w, int(q), int(wu), int(off), int(wu_col), int(off_col),
+                                                      _ptr(lay_g.packed), _ptr(lay_col.packed), lay_g.cout, float(2.0 ** -lay_g.w_exp),
+                                                      float(2.0 ** -lay_col.w_exp), _ptr(ws["rq"]), _ptr(ws["rq2"]), _ptr(scratch), _ptr(ws["mul"]),
+                                                      _ptr(ws["g"]), _ptr(ws["gcol"]), _ptr(ws["gi"]), int(pitch), int(lp), _stream(right)),
+              "snvc_fused_sheared_prep_x3")
+    return ws["g"], ws["gcol"], ws["gi"]
+
+
+def planes_x3_il(x, layer: "Conv2dLayerX3", ws: dict):
+    """``conv2d_x3_from_f32(x, [layer], ws)[0]`` for the left half's 3 x 3 depth-class layer (3C output channels, class-minor) that also
+    writes the result channel-interleaved, [N,3,C/8,H,W,8] (snvc_fused_planes_from_f32).  Returns (planes, p_il)."""
+    _gpu(x, "x")
+    x = x.contiguous()
+    if x.dtype != torch.float32 or x.dim() != 4:
+        raise RuntimeError("planes_x3_il needs a float32 [N,C,H,W] tensor")
+    n, c, h, w = x.shape
+    key = (n, c, h, w, id(layer), "il", x.device)
+    if ws.get("key") != key:
+        ws.clear()
+        ws.update(key=key, split=torch.empty(n * 2 * c * h * w, dtype=torch.float16, device=x.device),
+                  mul=torch.empty(1, dtype=torch.float32, device=x.device),
+                  y=[torch.empty((n, layer.cout, h, w), dtype=torch.float32, device=x.device)],
+                  p_il=torch.empty((n, 3, c // 8, h, w, 8), dtype=torch.float32, device=x.device), layers=[layer])
+    scratch = _scale_scratch(x.device)
+    with torch.cuda.device(x.device):
+        check(_fused.lib().snvc_fused_planes_from_f32(_ptr(x), n, c, h, w, _ptr(layer.packed), layer.cout, float(2.0 ** -layer.w_exp),
+                                                      _ptr(ws["y"][0]), _ptr(ws["p_il"]), _ptr(ws["split"]), _ptr(scratch), _ptr(ws["mul"]),
+                                                      _stream(x)), "snvc_fused_planes_from_f32")
+    return ws["y"][0], ws["p_il"]
+
+
 def from_split(x: torch.Tensor, exp: int = 0, channels: Optional[int] = None) -> torch.Tensor:
     """split C8 -> float32 [N,C,D,H,W]: (hi + lo) * 2**-exp."""
     _split_check(x, "x")
@@ -1827,6 +1892,43 @@ class Conv3dLayerX3(_ConvGeometry):
                                                        _ptr(overflow), _stream(x)), "snvc_f16x3_conv3d_forward")
         if f32:
             return out_f32          # the kernel multiplied by 2^-out_exp on the way out
+        return (out, y_head) if head is not None else out
+
+    def fused_first_form(self, n: int, sp) -> bool:
+        """True when a launch on a [n, Cin, *sp] input would take the 16x16x32 form -- the one that can form the sheared first
+        layer's result itself (``forward_fused_first``)."""
+        return (self.ksize == 3 and self.stride == 1 and not self.transposed and self.w_mul_dev is None and self.cin % 8 == 0
+                and x3_form(self.cout, 3, 1, self.dilation, False, n, tuple(sp), True, False, self.forced_algo) == _lib.ALGO_X3_Q16)
+
+    def forward_fused_first(self, gi, pitch: int, lp: int, p_il, v_scale, v_bias, q: int, m0: int, off: int, off_col: int, v_flags: int,
+                            n: int, in_sp, x_exp: int = 0, scale=None, bias=None, flags: int = 0, out=None, out_exp: int = 0, head=None,
+                            overflow=None):
+        """``self(v1s, x_exp, ...)`` with v1s = the sheared first layer's split result (``sheared_expand_split`` of the same operands:
+        ``gi`` / ``p_il`` channel-interleaved, ``v_scale`` / ``v_bias`` its folded affine carrying 2**x_exp) formed inside the launch
+        (snvc_fused_first_conv3d_forward): same bits, v1s is never stored.  Raises Unsupported when the launch would not take the
+        16x16x32 form."""
+        in_sp = tuple(int(v) for v in in_sp)
+        if not self.fused_first_form(n, in_sp):
+            raise Unsupported("forward_fused_first: the layer does not run on the 16x16x32 form at this size")
+        algo = self.algo = _lib.ALGO_X3_Q16
+        packed = self._pack(algo)
+        out_sp = self.out_spatial(in_sp)
+        out = _result(out, (n, 2, self.cout // 8) + out_sp + (8,), torch.float16, gi.device,
+                      "conv3d `out` must be a split C8 tensor of the output shape", _split_check)
+        y_head = None
+        if head is not None:
+            head = head.detach().reshape(-1).float().contiguous()
+            y_head = torch.empty((n, 1) + out_sp, dtype=torch.float32, device=gi.device)
+        sc, bi = self.folded(scale, bias, x_exp, out_exp)
+        if n == 0:
+            return (out, y_head) if head is not None else out
+        d = self._desc(n, in_sp, flags, algo, 0, _batch_stride(out), 0)
+        with torch.cuda.device(gi.device):
+            check(_fused.lib().snvc_fused_first_conv3d_forward(ctypes.byref(d), _ptr(packed), _ptr(sc), _ptr(bi), _ptr(out), _lo_ptr(out),
+                                                               _ptr(head), _ptr(y_head), float(2.0 ** -out_exp), _ptr(overflow), _ptr(gi),
+                                                               int(pitch), int(lp), _ptr(p_il), _ptr(v_scale), _ptr(v_bias), int(q), int(m0),
+                                                               int(off), int(off_col), int(v_flags), _stream(gi)),
+                  "snvc_fused_first_conv3d_forward")
         return (out, y_head) if head is not None else out
 
     def forward_f32(self, x, x_mul_dev, residual_f32: Optional[torch.Tensor] = None, relu: bool = False):
