@@ -985,7 +985,9 @@ def act_backward_apply(raw, gy, residual, scale, shift, coef_g, coef_raw, coef_c
     s = raw[0, 0].numel()
     draw = torch.empty(raw.shape, dtype=torch.float32, device=raw.device)
     g_out = torch.empty(raw.shape, dtype=torch.float32, device=raw.device) if want_g else None
-    if twin_mul is not None and twin_ok(draw) and _dense_inner(raw) and _dense_inner(gy) and (residual is None or _dense_inner(residual)):
+    if (twin_mul is not None and twin_ok(draw) and _dense_inner(raw) and _dense_inner(gy) and (residual is None or _dense_inner(residual))
+            and raw.data_ptr() % 16 == 0 and gy.data_ptr() % 16 == 0 and (residual is None or residual.data_ptr() % 16 == 0)):
+        # (the twin pass reads 16-byte pieces, as affine_act's does: operands off 16 bytes take the plain pass and get no twin)
         pair = twin_empty(draw)
         with torch.cuda.device(raw.device):
             check(_lib.lib().snvc_act_backward_apply_twin(
