@@ -2076,164 +2076,6 @@ using F16K5D2X = F16Cfg<5, 5, 5, 1, 1, 1, 4, 4, 1, 1, false, 2, 2, 3>;
 using F16K7X   = F16Cfg<7, 7, 7, 1, 1, 1, 4, 4, 1, 1, false, 2, 1, 3>;
 using F16DCXN  = F16Cfg<2, 2, 2, 1, 1, 1, 4, 4, 2, 1, false, 3, 1, 2, true>;
 
-enum F16Kind { FK1, FK3, FK3H, FK3S2, FK5, FK5D2, FK7, FDC, FK1N, FK3N, FK3S2N, FK5N, FK5D2N, FK7N, FDCN, FK3X, FK3X2, FK3S2X, FDCX, FK3XS, FK3X2S, FK3XT, FK1X, FK5X, FK5D2X, FK7X, FDCXN, FK3XH, FK3XQ, FK5XQ, FK5D2XQ, FK7XQ, FK5D2Q, FK7Q, FK5D2QN, FK7QN, FK5Q, FK5QN, FK3S2XT, FDCXT, FK3S2XQ, FNONE };
-
-struct F16Plan {
-    int kind, MI, KCG, MODE, TD, TH, STEPS, SEGS, TSEG, NPS, NS, KD, KH, KW, unroll_d, PL, PF, PASSES, dyn;
-    int nchunks, cblocks;
-    int64_t block_halves;      // packed halves of one class (without padding)
-};
-
-template <class Cfg>
-F16Plan plan_from(int kind) {
-    F16Plan p{};
-    p.kind = kind; p.MI = Cfg::MI; p.KCG = Cfg::KCG; p.MODE = Cfg::MODE; p.TD = Cfg::TD; p.TH = Cfg::TH;
-    p.STEPS = Cfg::STEPS; p.SEGS = Cfg::SEGS; p.TSEG = Cfg::TSEG; p.NPS = Cfg::NPS; p.NS = Cfg::NS;
-    p.KD = Cfg::KD; p.KH = Cfg::KH; p.KW = Cfg::KW; p.unroll_d = Cfg::UNROLL_D ? 1 : 0;
-    p.PL = Cfg::PL; p.PF = Cfg::PF; p.PASSES = Cfg::PASSES; p.dyn = Cfg::DYN ? 1 : 0;
-    return p;
-}
-
-int make_f16_plan(const snvc_conv3d_desc &d, F16Plan &p, bool split = false) {
-    if (d.N < 0 || d.Cin <= 0 || d.Cout <= 0 || d.Din <= 0 || d.Hin <= 0 || d.Win <= 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16_conv3d: sizes must be positive");
-    if (d.Cin % 8 != 0) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: Cin must be a multiple of 8 (C8 layout)");
-    if (split) {
-        if (d.transposed) {
-            if (d.ksize != 3 || d.stride != 2 || d.pad != 1 || d.dilation != 1 || d.Cout % 32 != 0)
-                return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: transposed layers: k3,s2,p1,op1 with Cout % 32 == 0");
-            if (d.Dout != 2 * d.Din || d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win)
-                return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d: transposed output must be 2x the input");
-            p = d.Cout % 64 == 0 ? ((d.algo & SNVC_ALGO_X3_SMALL) ? plan_from<F16DCXT>(FDCXT) : plan_from<F16DCX>(FDCX)) : plan_from<F16DCXN>(FDCXN);
-        } else {
-            if (d.pad != d.dilation * (d.ksize - 1) / 2)
-                return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: pad must equal dilation*(ksize-1)/2");
-            const int eff = d.dilation * (d.ksize - 1) + 1;
-            if (d.Dout != (d.Din + 2 * d.pad - eff) / d.stride + 1 || d.Hout != (d.Hin + 2 * d.pad - eff) / d.stride + 1 ||
-                d.Wout != (d.Win + 2 * d.pad - eff) / d.stride + 1)
-                return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d: output size does not match the convolution arithmetic");
-            const int key = d.ksize * 100 + d.stride * 10 + d.dilation;
-            if (d.Cout == 1) {
-                if (key != 311) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: one-channel output is built for k3/s1 only");
-                p = plan_from<F16K3X>(FK3XH);
-            } else if (key == 321) {
-                if (d.Cout % 64 != 0) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: stride-2 layers need Cout % 64 == 0");
-                if (d.algo & SNVC_ALGO_X3_Q16) {      // the 16x16x32 form: both planes, three image slots, one workgroup per CU
-                    p = plan_from<F16K3S2X>(FK3S2XQ);
-                    p.KCG = 1; p.MI = 2; p.STEPS = X3S2Cfg::NQ; p.NS = X3S2Cfg::NQ; p.PF = 0; p.PASSES = 1;
-                    p.nchunks = d.Cin / 8;
-                    p.cblocks = d.Cout / 64;
-                    p.block_halves = (int64_t)p.cblocks * p.nchunks * X3S2Cfg::NQ * 8 * 64 * 8;
-                    if (p.cblocks > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: too many channel blocks or samples");
-                    return SNVC_OK;
-                }
-                p = (d.algo & SNVC_ALGO_X3_SMALL) ? plan_from<F16K3S2XT>(FK3S2XT) : plan_from<F16K3S2X>(FK3S2X);
-            } else {
-                if (d.Cout % 32 != 0) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: Cout % 32 == 0");
-                if ((d.algo & SNVC_ALGO_X3_Q16) && (key == 511 || key == 512 || key == 711)) {      // 16x16x32 form, planes serial
-                    const int ks = d.ksize;
-                    p = key == 511 ? plan_from<F16K5X>(FK5XQ) : (key == 512 ? plan_from<F16K5D2X>(FK5D2XQ) : plan_from<F16K7X>(FK7XQ));
-                    p.KCG = 1; p.MI = 1; p.PF = 2; p.STEPS = q16s_steps(ks);
-                    p.nchunks = d.Cin / 8;
-                    p.cblocks = d.Cout / 32;
-                    p.block_halves = (int64_t)p.cblocks * p.nchunks * 2 * p.STEPS * 4 * 64 * 8;
-                    if (p.cblocks > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: too many channel blocks or samples");
-                    return SNVC_OK;
-                }
-                switch (key) {
-                    case 111: p = plan_from<F16K1X>(FK1X); break;
-                    case 511: p = plan_from<F16K5X>(FK5X); break;
-                    case 512: p = plan_from<F16K5D2X>(FK5D2X); break;
-                    case 711: p = plan_from<F16K7X>(FK7X); break;
-                    case 311:
-                        if (d.algo & SNVC_ALGO_X3_Q16) {      // the 16x16x32 form (four taps x one channel group per MFMA): its own packing
-                            p = plan_from<F16K3X>(FK3XQ);
-                            p.KCG = 1; p.MI = 1; p.STEPS = X3QCfg::NQ; p.NS = X3QCfg::NQ; p.PF = X3QCfg::PF;
-                            p.nchunks = d.Cin / 8;
-                            p.cblocks = d.Cout / 32;
-                            p.block_halves = (int64_t)p.cblocks * p.nchunks * X3QCfg::NQ * 4 * 64 * 8;
-                            if (p.cblocks > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: too many channel blocks or samples");
-                            return SNVC_OK;
-                        }
-                        if (d.algo & SNVC_ALGO_X3_SMALL) p = plan_from<F16K3XT>(FK3XT);
-                        else if (d.algo & SNVC_ALGO_X3_NARROW) p = plan_from<F16K3X>(FK3X);
-                        else if (d.algo & SNVC_ALGO_X3_SERIAL) p = d.Cout == 32 ? plan_from<F16K3XS>(FK3XS) : plan_from<F16K3X2S>(FK3X2S);
-                        else p = d.Cout == 32 ? plan_from<F16K3X>(FK3X) : plan_from<F16K3X2>(FK3X2);
-                        break;
-                    default:
-                        return fail(SNVC_ERR_UNSUPPORTED,
-                                    "snvc_f16x3_conv3d: (ksize,stride,dilation) not in {(1,1,1),(3,1,1),(3,2,1),(5,1,1),(5,1,2),(7,1,1)}");
-                }
-            }
-        }
-        p.nchunks = ceil_div(d.Cin / 8, p.KCG);
-        p.cblocks = ceil_div(d.Cout, 32 * p.MI);
-        p.block_halves = (int64_t)p.cblocks * p.nchunks * p.PASSES * p.STEPS * p.MI * 2 * 64 * 8;
-        if (p.cblocks > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: too many channel blocks or samples");
-        return SNVC_OK;
-    }
-    if (d.Cout != 1 && d.Cout % 32 != 0)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: Cout must be a multiple of 32, or 1 (fp32 plane output)");
-    if (d.transposed) {
-        if (d.ksize != 3 || d.stride != 2 || d.pad != 1 || d.dilation != 1)
-            return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: transposed conv supports k3,s2,p1,op1 only");
-        if (d.Dout != 2 * d.Din || d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win)
-            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16_conv3d: transposed output must be 2x the input");
-        if (d.Cout == 1) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: transposed conv to one channel");
-        p = d.Cout == 32 ? plan_from<F16DCN>(FDCN) : plan_from<F16DC>(FDC);
-    } else {
-        if (d.pad != d.dilation * (d.ksize - 1) / 2)
-            return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: pad must equal dilation*(ksize-1)/2");
-        const int eff = d.dilation * (d.ksize - 1) + 1;
-        if (d.Dout != (d.Din + 2 * d.pad - eff) / d.stride + 1 || d.Hout != (d.Hin + 2 * d.pad - eff) / d.stride + 1 ||
-            d.Wout != (d.Win + 2 * d.pad - eff) / d.stride + 1)
-            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16_conv3d: output size does not match the convolution arithmetic");
-        const int key = d.ksize * 100 + d.stride * 10 + d.dilation;
-        if (d.Cout == 1) {
-            if (key != 311) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: one-channel output is built for k3/s1 only");
-            p = plan_from<F16K3H>(FK3H);
-        } else {
-            const bool narrow = d.Cout == 32;      // one 32-channel block: the MI = 1 forms
-            if ((d.algo & SNVC_ALGO_X3_Q16) && (key == 711 || key == 512 || key == 511) && d.Cout % 32 == 0) {     // 16x16x32 form, two blocks per
-                const int ks = d.ksize;                                                             // workgroup (one for Cout = 32 * odd)
-                const bool two = d.Cout % 64 == 0;
-                p = key == 711 ? plan_from<F16K7>(two ? FK7Q : FK7QN) : key == 512 ? plan_from<F16K5D2>(two ? FK5D2Q : FK5D2QN)
-                                                                                   : plan_from<F16K5>(two ? FK5Q : FK5QN);
-                p.KCG = 1; p.MI = two ? 2 : 1; p.PF = 2; p.STEPS = q16s_steps(ks);
-                p.nchunks = d.Cin / 8;
-                p.cblocks = d.Cout / (two ? 64 : 32);
-                p.block_halves = (int64_t)p.cblocks * p.nchunks * p.STEPS * (two ? 4 : 2) * 64 * 8;
-                if (p.cblocks > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: too many channel blocks or samples");
-                return SNVC_OK;
-            }
-            switch (key) {
-                case 111: p = narrow ? plan_from<F16K1N>(FK1N) : plan_from<F16K1>(FK1); break;
-                case 311: p = narrow ? plan_from<F16K3H>(FK3N) : plan_from<F16K3>(FK3); break;
-                case 321: p = narrow ? plan_from<F16K3S2N>(FK3S2N) : plan_from<F16K3S2>(FK3S2); break;
-                case 511: p = narrow ? plan_from<F16K5N>(FK5N) : plan_from<F16K5>(FK5); break;
-                case 512: p = narrow ? plan_from<F16K5D2N>(FK5D2N) : plan_from<F16K5D2>(FK5D2); break;
-                case 711: p = narrow ? plan_from<F16K7N>(FK7N) : plan_from<F16K7>(FK7); break;
-                default:
-                    return fail(SNVC_ERR_UNSUPPORTED,
-                                "snvc_f16_conv3d: (ksize,stride,dilation) not in {(1,1,1),(3,1,1),(3,2,1),(5,1,1),(5,1,2),(7,1,1)}");
-            }
-        }
-    }
-    p.nchunks = ceil_div(d.Cin / 8, p.KCG);
-    p.cblocks = ceil_div(d.Cout, 32 * p.MI);
-    p.block_halves = (int64_t)p.cblocks * p.nchunks * p.STEPS * p.MI * 64 * 8;
-    if (p.cblocks > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: too many channel blocks or samples");
-    return SNVC_OK;
-}
-
-inline int64_t f16_class_stride(const F16Plan &p) {
-    if (p.kind == FK3S2XQ) return p.block_halves + (int64_t)X3S2Cfg::NQ * 8 * 64 * 8;      // the last chunk's phase H never reads ahead, but stays in bounds if it did
-    if (p.kind == FK3XQ || p.kind == FK5XQ || p.kind == FK5D2XQ || p.kind == FK7XQ || p.kind == FK5D2Q || p.kind == FK7Q || p.kind == FK5Q)
-        return p.block_halves + (int64_t)p.PF * 4 * 64 * 8;
-    if (p.kind == FK5D2QN || p.kind == FK7QN || p.kind == FK5QN) return p.block_halves + (int64_t)p.PF * 2 * 64 * 8;
-    return p.block_halves + (int64_t)p.PF * p.MI * (p.PL >= 2 ? 2 : 1) * 64 * 8;
-}
-
 // A fragments of the tail projection (conv3d_f16_kernel EPI 4): [m][j][hi | lo][lane][8]; row (lane & 31) = tap, k = 8 * (lane >> 5) + e
 // is channel 32 m + 16 (lane >> 5) + 8 j + e -- the channel that accumulator register 8 j + e of lane (voxel, lane >> 5) holds
 __global__ void pack_tail_weights_kernel(const float *__restrict__ w, _Float16 *__restrict__ out, int Cin, float wmul, int total) {
@@ -2340,9 +2182,287 @@ split_scale_kernel(const float *__restrict__ x, int64_t n, unsigned *__restrict_
     }
 }
 
+// ------------------------------------------------------------------------------------ kernel forms
+// One record per kernel form: the weight layout its packer writes, how its launch is laid out, which calls it takes and the launcher
+// of each.  make_f16_plan picks the record of a layer; the packers, f16_geometry and the two forward calls read it and never ask
+// which form it is.  A new form is one new record, and the line of plain_form / split_form that chooses it.
+struct F16Geom {
+    int classes;               // parity classes of the launch (the 8 transposed ones: 4 on gridDim.z, 2 on gridDim.x)
+    int64_t ntiles;            // tiles of the largest class
+    int64_t jobs;              // GRID_JOBS: (tile, channel block) jobs per sample; GRID_PERSISTENT: over all samples
+    int64_t stats_slots;       // statistics epilogue: slots per sample, one per wave of every workgroup that a sample has on x and z
+    dim3 grid;
+};
+using F16Launch = void (*)(const F16Args &, const F16Geom &, hipStream_t);
+
+// what a call asks of a form, in the order a record's launchers stand; TO_C8: a C8 tensor -- the split pair, or fp16 storage's one half
+enum F16Call { TO_SRC_HEAD, TO_SRC, TO_TAIL, TO_F32, TO_HEAD, TO_C8, TO_PLANE, F16_CALLS };
+enum F16Classes { CLS_ONE = 0, CLS_TRANSPOSED = 1, CLS_SUBGRID = 2 };      // F16Args::cls_mode: one class, 8 transposed, 4 shared (d, h) parity
+// (tiles, channel blocks, N x classes) | (tile, channel block) jobs on x, samples on z | persistent, one workgroup per CU
+enum F16Grid { GRID_TILES, GRID_JOBS, GRID_PERSISTENT };
+
+// pack_q16s_weights_kernel's layout [cb][chunk][pass][segment][quad][co half (NH)][hi | lo (NPL)][lane][8]; NQ = 0: pack_f16_weights_kernel's
+struct Q16Layout { int K3, NSEG, NQ, NH, NPL, PASSES; };
+
+struct F16Form {
+    PackArgs pack;             // pack_f16_weights_kernel's layout: the Cfg's constants (the per-call fields are zero)
+    Q16Layout q16;
+    int MI, KCG;               // 32-channel blocks per workgroup, channel groups per chunk
+    int chunk_frags;           // 64 x 8 fragments of one (channel block, chunk)
+    int pad_frags;             // fragments of read-ahead padding behind a class
+    int cls_mode, TD, TH, grid;
+    bool split_res, stats;     // takes a split residual; has the statistics epilogue (on TO_F32)
+    const char *unsupported;   // what a call without a launcher (or a residual without split_res) is told
+    F16Launch launch[F16_CALLS];
+
+    constexpr F16Form on(F16Call c, F16Launch l) const { F16Form f = *this; f.launch[c] = l; return f; }
+};
+
 template <class Cfg, int EPI>
-void launch_f16(const F16Args &a, dim3 grid, hipStream_t st) {
-    launch_lds<conv3d_f16_kernel<Cfg, EPI>>(grid, 256, Cfg::LDS_BYTES, st, a);
+void launch_f16(const F16Args &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_f16_kernel<Cfg, EPI>>(g.grid, 256, Cfg::LDS_BYTES, st, a);
+}
+template <class Cfg>
+void launch_q16s(const F16Args &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_q16s_kernel<Cfg>>(g.grid, 256, Cfg::LDS_BYTES, st, a);
+}
+template <int EPI>
+void launch_x3q(const F16Args &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_x3q_kernel<EPI>>(g.grid, 256, X3QCfg::LDS_BYTES, st, a);
+}
+template <int EPI>      // the fused sheared first layer: the image is formed in the launch; a is the F16SrcArgs the caller built
+void launch_x3q_src(const F16Args &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_x3q_kernel<EPI, 1>>(g.grid, 256, X3QCfg::LDS_BYTES, st, static_cast<const F16SrcArgs &>(a));
+}
+// persistent: one workgroup per CU (144 KB of LDS each), a multiple of 8 so that a workgroup's jobs b, b + G, ... stay on its XCD
+void launch_x3s2q(const F16Args &a, const F16Geom &g, hipStream_t st) {
+    int wg = device_cu_count();
+    if (wg <= 0) wg = 256;
+    if (g.jobs < wg) wg = g.jobs >= 8 ? (int)(g.jobs & ~(int64_t)7) : (int)g.jobs;
+    launch_lds<conv3d_x3s2q_kernel>(dim3((unsigned)wg), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)g.jobs);
+}
+
+// a 32x32x16 form: everything but its class mode and its statistics bit follows from the Cfg; EPI 0 C8, 1 plane, 2 float32, 3 side head, 4 tail
+template <class Cfg, int... EPI>
+constexpr F16Form f16_form(int cls_mode, bool stats = false) {
+    constexpr F16Call call_of[5] = {TO_C8, TO_PLANE, TO_F32, TO_HEAD, TO_TAIL};
+    constexpr int npl = Cfg::PL >= 2 ? 2 : 1;
+    F16Form f{};
+    f.pack.KD = Cfg::KD; f.pack.KH = Cfg::KH; f.pack.KW = Cfg::KW; f.pack.KCG = Cfg::KCG; f.pack.MODE = Cfg::MODE; f.pack.MI = Cfg::MI;
+    f.pack.SEGS = Cfg::SEGS; f.pack.TSEG = Cfg::TSEG; f.pack.NPS = Cfg::NPS; f.pack.NS = Cfg::NS; f.pack.unroll_d = Cfg::UNROLL_D ? 1 : 0;
+    f.pack.PL = Cfg::PL; f.pack.PASSES = Cfg::PASSES; f.pack.dyn = Cfg::DYN ? 1 : 0;
+    f.MI = Cfg::MI; f.KCG = Cfg::KCG; f.TD = Cfg::TD; f.TH = Cfg::TH;
+    f.chunk_frags = Cfg::PASSES * Cfg::STEPS * Cfg::MI * npl;
+    f.pad_frags = Cfg::PF * Cfg::MI * npl;
+    f.cls_mode = cls_mode; f.grid = GRID_TILES; f.split_res = true; f.stats = stats;
+    f.unsupported = Cfg::PL >= 2 ? "snvc_f16x3_conv3d_forward: no kernel" : "snvc_f16_conv3d_forward: no kernel";
+    ((f.launch[call_of[EPI]] = launch_f16<Cfg, EPI>), ...);
+    return f;
+}
+
+// a 16x16x32 form: pad_steps k-steps of read-ahead behind a class; its launchers are added with on()
+constexpr F16Form q16_form(Q16Layout q, int TD, int TH, int pad_steps, int cls_mode, int grid, bool split_res, bool stats, const char *unsupported) {
+    F16Form f{};
+    f.q16 = q; f.MI = q.NH / 2; f.KCG = 1; f.TD = TD; f.TH = TH;
+    f.chunk_frags = q.PASSES * q.NSEG * q.NQ * q.NH * q.NPL;
+    f.pad_frags = pad_steps * q.NH * q.NPL;
+    f.cls_mode = cls_mode; f.grid = grid; f.split_res = split_res; f.stats = stats; f.unsupported = unsupported;
+    return f;
+}
+template <class C>      // flat tap segments: 5^3 one of all 125 taps, 7^3 two of 172 slots
+constexpr F16Form q16s_form(F16Call c, const char *unsupported) {
+    return q16_form({C::K3, C::KSEG, C::NQ, C::NH, C::SPLIT ? 2 : 1, C::PASSES}, C::TD, C::TH, C::PF, C::DILW == 2 ? CLS_SUBGRID : CLS_ONE, GRID_TILES, true,
+                    false, unsupported).on(c, launch_q16s<C>);
+}
+
+// The records stand in the order in which the dispatch switches used to name their kernels, and an EPI list names its launchers last to
+// first: the compiler emits kernels in the order (and a pack's in the reverse of the order) of first use, and this order keeps the code
+// object byte for byte what it was (profiles/f16_host_plan/device_code_identity.txt).
+// fp16 storage (snvc_f16_conv3d_*)
+constexpr const char *kQ16C8 = "snvc_f16_conv3d_forward: the 16x16x32 form writes C8 tensors";
+constexpr F16Form FORM_K7QN   = q16s_form<Q16SCfg<7, 1, 1, 1>>(TO_C8, kQ16C8);
+constexpr F16Form FORM_K5QN   = q16s_form<Q16SCfg<5, 1, 1, 1>>(TO_C8, kQ16C8);
+constexpr F16Form FORM_K5D2QN = q16s_form<Q16SCfg<5, 2, 1, 1>>(TO_C8, kQ16C8);
+constexpr F16Form FORM_K7Q    = q16s_form<Q16SCfg<7, 1, 1, 2>>(TO_C8, kQ16C8);
+constexpr F16Form FORM_K5Q    = q16s_form<Q16SCfg<5, 1, 1, 2>>(TO_C8, kQ16C8);
+constexpr F16Form FORM_K5D2Q  = q16s_form<Q16SCfg<5, 2, 1, 2>>(TO_C8, kQ16C8);
+constexpr F16Form FORM_K1     = f16_form<F16K1, 0>(CLS_ONE);
+constexpr F16Form FORM_K3     = f16_form<F16K3, 0>(CLS_ONE);
+constexpr F16Form FORM_K3H    = f16_form<F16K3H, 1>(CLS_ONE);              // the one-channel fp32 plane
+constexpr F16Form FORM_K3S2   = f16_form<F16K3S2, 0>(CLS_ONE);
+constexpr F16Form FORM_K5     = f16_form<F16K5, 0>(CLS_ONE);
+constexpr F16Form FORM_K5D2   = f16_form<F16K5D2, 0>(CLS_SUBGRID);
+constexpr F16Form FORM_K7     = f16_form<F16K7, 0>(CLS_ONE);
+constexpr F16Form FORM_DC     = f16_form<F16DC, 0>(CLS_TRANSPOSED);
+constexpr F16Form FORM_K1N    = f16_form<F16K1N, 0>(CLS_ONE);
+constexpr F16Form FORM_K3N    = f16_form<F16K3H, 0>(CLS_ONE);
+constexpr F16Form FORM_K3S2N  = f16_form<F16K3S2N, 0>(CLS_ONE);
+constexpr F16Form FORM_K5N    = f16_form<F16K5N, 0>(CLS_ONE);
+constexpr F16Form FORM_K5D2N  = f16_form<F16K5D2N, 0>(CLS_SUBGRID);
+constexpr F16Form FORM_K7N    = f16_form<F16K7N, 0>(CLS_ONE);
+constexpr F16Form FORM_DCN    = f16_form<F16DCN, 0>(CLS_TRANSPOSED);
+// split mode (snvc_f16x3_conv3d_*); true: the statistics epilogue
+constexpr F16Form FORM_K3X    = f16_form<F16K3X, 0, 3, 2>(CLS_ONE, true);
+constexpr F16Form FORM_K3X2   = f16_form<F16K3X2, 0, 2>(CLS_ONE, true);
+constexpr F16Form FORM_K3XS   = f16_form<F16K3XS, 0, 3, 2>(CLS_ONE, true);
+constexpr F16Form FORM_K3X2S  = f16_form<F16K3X2S, 0, 2>(CLS_ONE, true);
+constexpr F16Form FORM_K3XT   = f16_form<F16K3XT, 0, 3, 2>(CLS_ONE, true);
+constexpr F16Form FORM_K3S2X  = f16_form<F16K3S2X, 0, 2>(CLS_ONE, true);
+constexpr F16Form FORM_K3S2XT = f16_form<F16K3S2XT, 0, 2>(CLS_ONE, true);
+constexpr F16Form FORM_DCX    = f16_form<F16DCX, 0, 2, 4>(CLS_TRANSPOSED, true);
+constexpr F16Form FORM_DCXT   = f16_form<F16DCXT, 0, 2, 4>(CLS_TRANSPOSED, true);
+constexpr F16Form FORM_DCXN   = f16_form<F16DCXN, 0, 2, 4>(CLS_TRANSPOSED, true);
+constexpr F16Form FORM_K1X    = f16_form<F16K1X, 0, 2>(CLS_ONE);
+constexpr F16Form FORM_K5X    = f16_form<F16K5X, 0, 2>(CLS_ONE);
+constexpr F16Form FORM_K5D2X  = f16_form<F16K5D2X, 0, 2>(CLS_SUBGRID);
+constexpr F16Form FORM_K7X    = f16_form<F16K7X, 0, 2>(CLS_ONE);
+constexpr F16Form FORM_K3XH   = f16_form<F16K3X, 1>(CLS_ONE);              // the one-channel occupancy head
+constexpr const char *kQ16Split = "snvc_f16x3_conv3d_forward: the 16x16x32 form writes a split C8 tensor, no side head";
+constexpr F16Form FORM_K5XQ   = q16s_form<Q16SCfg<5, 1>>(TO_C8, kQ16Split);
+constexpr F16Form FORM_K5D2XQ = q16s_form<Q16SCfg<5, 2>>(TO_C8, kQ16Split);
+constexpr F16Form FORM_K7XQ   = q16s_form<Q16SCfg<7, 1>>(TO_C8, kQ16Split);
+// [cb (64 channels)][chunk][quad][co half (4)][hi | lo][lane][8]; a whole chunk of padding: the last chunk's phase H never reads ahead, but
+// stays in bounds if it did
+constexpr F16Form FORM_K3S2XQ =
+    q16_form({27, 1, X3S2Cfg::NQ, 4, 2, 1}, X3S2Cfg::TD, X3S2Cfg::TH, X3S2Cfg::NQ, CLS_ONE, GRID_PERSISTENT, false, false,
+             "snvc_f16x3_conv3d_forward: the stride-2 16x16x32 form writes a split C8 tensor, no residual / head")
+        .on(TO_C8, launch_x3s2q);
+// four taps x one channel group per MFMA, [cb][chunk][quad][co half][hi | lo][lane][8]: one segment of all 27 taps
+constexpr F16Form FORM_K3XQ =
+    q16_form({27, 1, X3QCfg::NQ, 2, 2, 1}, X3QCfg::TD, X3QCfg::TH, X3QCfg::PF, CLS_ONE, GRID_JOBS, false, true,
+             "snvc_f16x3_conv3d_forward: the 16x16x32 form has no split residual, no side head beside a float32 result")
+        .on(TO_SRC_HEAD, launch_x3q_src<3>).on(TO_SRC, launch_x3q_src<0>).on(TO_F32, launch_x3q<2>).on(TO_HEAD, launch_x3q<3>).on(TO_C8, launch_x3q<0>);
+
+struct F16Plan {
+    const F16Form *form;
+    int nchunks, cblocks;
+    int64_t block_halves;      // packed halves of one class (without padding)
+    int64_t class_stride() const { return block_halves + (int64_t)form->pad_frags * 64 * 8; }
+};
+
+// the form of a non-transposed layer with more than one output channel; NULL: none for this (ksize, stride, dilation)
+const F16Form *plain_form(int key, int Cout, int algo) {
+    const bool narrow = Cout == 32;      // one 32-channel block: the MI = 1 forms
+    if (algo & SNVC_ALGO_X3_Q16) {       // 16x16x32 form, two blocks per workgroup (one for Cout = 32 * odd)
+        const bool two = Cout % 64 == 0;
+        if (key == 711) return two ? &FORM_K7Q : &FORM_K7QN;
+        if (key == 512) return two ? &FORM_K5D2Q : &FORM_K5D2QN;
+        if (key == 511) return two ? &FORM_K5Q : &FORM_K5QN;
+    }
+    switch (key) {
+        case 111: return narrow ? &FORM_K1N : &FORM_K1;
+        case 311: return narrow ? &FORM_K3N : &FORM_K3;
+        case 321: return narrow ? &FORM_K3S2N : &FORM_K3S2;
+        case 511: return narrow ? &FORM_K5N : &FORM_K5;
+        case 512: return narrow ? &FORM_K5D2N : &FORM_K5D2;
+        case 711: return narrow ? &FORM_K7N : &FORM_K7;
+        default: return nullptr;
+    }
+}
+
+const F16Form *split_form(int key, int Cout, int algo) {
+    const bool q16 = algo & SNVC_ALGO_X3_Q16;      // the 16x16x32 forms
+    switch (key) {
+        case 111: return &FORM_K1X;
+        case 321: return q16 ? &FORM_K3S2XQ : (algo & SNVC_ALGO_X3_SMALL) ? &FORM_K3S2XT : &FORM_K3S2X;
+        case 511: return q16 ? &FORM_K5XQ : &FORM_K5X;
+        case 512: return q16 ? &FORM_K5D2XQ : &FORM_K5D2X;
+        case 711: return q16 ? &FORM_K7XQ : &FORM_K7X;
+        case 311:
+            if (q16) return &FORM_K3XQ;
+            if (algo & SNVC_ALGO_X3_SMALL) return &FORM_K3XT;
+            if (algo & SNVC_ALGO_X3_NARROW) return &FORM_K3X;
+            if (algo & SNVC_ALGO_X3_SERIAL) return Cout == 32 ? &FORM_K3XS : &FORM_K3X2S;
+            return Cout == 32 ? &FORM_K3X : &FORM_K3X2;
+        default: return nullptr;
+    }
+}
+
+int make_f16_plan(const snvc_conv3d_desc &d, F16Plan &p, bool split = false) {
+#define SNVC_F16_WHO(msg) (split ? "snvc_f16x3_conv3d: " msg : "snvc_f16_conv3d: " msg)
+    if (d.N < 0 || d.Cin <= 0 || d.Cout <= 0 || d.Din <= 0 || d.Hin <= 0 || d.Win <= 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16_conv3d: sizes must be positive");
+    if (d.Cin % 8 != 0) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: Cin must be a multiple of 8 (C8 layout)");
+    if (!split && d.Cout != 1 && d.Cout % 32 != 0)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: Cout must be a multiple of 32, or 1 (fp32 plane output)");
+    const F16Form *f;
+    if (d.transposed) {
+        if (d.ksize != 3 || d.stride != 2 || d.pad != 1 || d.dilation != 1 || (split && d.Cout % 32 != 0))
+            return fail(SNVC_ERR_UNSUPPORTED, split ? "snvc_f16x3_conv3d: transposed layers: k3,s2,p1,op1 with Cout % 32 == 0"
+                                                    : "snvc_f16_conv3d: transposed conv supports k3,s2,p1,op1 only");
+        if (d.Dout != 2 * d.Din || d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win)
+            return fail(SNVC_ERR_INVALID_ARGUMENT, SNVC_F16_WHO("transposed output must be 2x the input"));
+        if (d.Cout == 1) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d: transposed conv to one channel");
+        if (split) f = d.Cout % 64 == 0 ? ((d.algo & SNVC_ALGO_X3_SMALL) ? &FORM_DCXT : &FORM_DCX) : &FORM_DCXN;
+        else f = d.Cout == 32 ? &FORM_DCN : &FORM_DC;
+    } else {
+        if (d.pad != d.dilation * (d.ksize - 1) / 2) return fail(SNVC_ERR_UNSUPPORTED, SNVC_F16_WHO("pad must equal dilation*(ksize-1)/2"));
+        const int eff = d.dilation * (d.ksize - 1) + 1;
+        if (d.Dout != (d.Din + 2 * d.pad - eff) / d.stride + 1 || d.Hout != (d.Hin + 2 * d.pad - eff) / d.stride + 1 ||
+            d.Wout != (d.Win + 2 * d.pad - eff) / d.stride + 1)
+            return fail(SNVC_ERR_INVALID_ARGUMENT, SNVC_F16_WHO("output size does not match the convolution arithmetic"));
+        const int key = d.ksize * 100 + d.stride * 10 + d.dilation;
+        if (d.Cout == 1) {
+            if (key != 311) return fail(SNVC_ERR_UNSUPPORTED, SNVC_F16_WHO("one-channel output is built for k3/s1 only"));
+            f = split ? &FORM_K3XH : &FORM_K3H;
+        } else {
+            if (split && key == 321 && d.Cout % 64 != 0) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: stride-2 layers need Cout % 64 == 0");
+            if (split && key != 321 && d.Cout % 32 != 0) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d: Cout % 32 == 0");
+            f = split ? split_form(key, d.Cout, d.algo) : plain_form(key, d.Cout, d.algo);
+            if (!f) return fail(SNVC_ERR_UNSUPPORTED, SNVC_F16_WHO("(ksize,stride,dilation) not in {(1,1,1),(3,1,1),(3,2,1),(5,1,1),(5,1,2),(7,1,1)}"));
+        }
+    }
+    p.form = f;
+    p.nchunks = ceil_div(d.Cin / 8, f->KCG);
+    p.cblocks = ceil_div(d.Cout, 32 * f->MI);
+    p.block_halves = (int64_t)p.cblocks * p.nchunks * f->chunk_frags * 64 * 8;
+    if (p.cblocks > 65535 || d.N > 65535) return fail(SNVC_ERR_UNSUPPORTED, SNVC_F16_WHO("too many channel blocks or samples"));
+    return SNVC_OK;
+#undef SNVC_F16_WHO
+}
+
+// The launch geometry of a planned layer: fills a's class, sub-grid, pad and tile fields, and returns the counts and the grid that the
+// forward calls check and launch with -- and that the statistics workspace is sized by.
+F16Geom f16_geometry(const snvc_conv3d_desc &d, const F16Plan &p, F16Args &a) {
+    const F16Form &f = *p.form;
+    const bool transposed = f.cls_mode == CLS_TRANSPOSED, subgrid = f.cls_mode == CLS_SUBGRID;      // (depth, height) parity classes share ONE packed weight block
+    a.N = d.N; a.cls_mode = f.cls_mode; a.cls_wstride = p.class_stride();
+    a.isd = a.ish = 1; a.iod = a.ioh = 0; a.offd = a.offh = a.offw = 0;
+    if (transposed) {
+        a.nd = d.Din; a.nh = d.Hin; a.nw = d.Win;
+        a.osd = a.osh = a.osw = 2;
+        a.pad_d = a.pad_h = a.pad_w = 0;
+    } else if (subgrid) {
+        a.nd = (d.Dout + 1) / 2; a.nh = (d.Hout + 1) / 2; a.nw = d.Wout;     // the largest class; the kernel trims the others
+        a.osd = a.osh = 2; a.osw = 1;
+        a.isd = a.ish = 2;
+        a.pad_d = a.pad_h = d.pad / 2; a.pad_w = d.pad;
+    } else {
+        a.nd = d.Dout; a.nh = d.Hout; a.nw = d.Wout;
+        a.osd = a.osh = a.osw = 1;
+        a.pad_d = a.pad_h = a.pad_w = d.pad;
+    }
+    a.tiles_d = ceil_div(a.nd, f.TD); a.tiles_h = ceil_div(a.nh, f.TH); a.tiles_w = ceil_div(a.nw, 32);
+    F16Geom g{};
+    g.classes = transposed ? 8 : (subgrid ? 4 : 1);
+    g.ntiles = (int64_t)a.tiles_d * a.tiles_h * a.tiles_w;
+    const int64_t gx = transposed ? 2 * g.ntiles : g.ntiles, gz = transposed ? 4 : g.classes;
+    g.grid = dim3((unsigned)gx, (unsigned)p.cblocks, (unsigned)(d.N * gz));
+    g.stats_slots = gz * gx * 4;
+    if (f.grid == GRID_JOBS) {           // channel block fastest: a slot per tile and wave
+        g.jobs = g.ntiles * p.cblocks;
+        g.grid = dim3((unsigned)g.jobs, 1, (unsigned)d.N);
+        g.stats_slots = g.ntiles * 4;
+    } else if (f.grid == GRID_PERSISTENT) {
+        g.jobs = g.ntiles * p.cblocks * d.N;
+    }
+    return g;
+}
+
+// the one call site of pack_q16s_weights_kernel: total halves of [cb][chunk] blocks in layout q (NT = 4 NQ tap slots per segment)
+void pack_q16(const Q16Layout &q, const float *w, void *packed, int Cout, int Cin, float wmul, int64_t total, hipStream_t st) {
+    pack_q16s_weights_kernel<<<(unsigned)ceil_div<int64_t>(total, 256), 256, 0, st>>>(w, reinterpret_cast<_Float16 *>(packed), Cout, Cin, q.K3, q.NSEG, 4 * q.NQ,
+                                                                                    q.NQ, Cin / 8, q.NH, q.NPL, q.PASSES, wmul, total);
 }
 
 }  // namespace
@@ -2350,12 +2470,14 @@ void launch_f16(const F16Args &a, dim3 grid, hipStream_t st) {
 
 extern "C" {
 
-int64_t snvc_f16_conv3d_packed_weight_bytes(const snvc_conv3d_desc *d) {
-    using namespace snvc;
-    F16Plan p;
-    if (!d || make_f16_plan(*d, p) != SNVC_OK) return -1;
-    return 2 * f16_class_stride(p) * (d->transposed ? 8 : 1);
+static int64_t f16_packed_bytes(const snvc_conv3d_desc *d, bool split) {
+    snvc::F16Plan p;
+    if (!d || snvc::make_f16_plan(*d, p, split) != SNVC_OK) return -1;
+    return 2 * p.class_stride() * (d->transposed ? 8 : 1);
 }
+
+int64_t snvc_f16_conv3d_packed_weight_bytes(const snvc_conv3d_desc *d) { return f16_packed_bytes(d, false); }
+int64_t snvc_f16x3_conv3d_packed_weight_bytes(const snvc_conv3d_desc *d) { return f16_packed_bytes(d, true); }
 
 static int f16_pack_common(const snvc_conv3d_desc *d, const float *weight, void *packed, bool split, float wmul, void *stream,
                            const char *who) {
@@ -2365,47 +2487,26 @@ static int f16_pack_common(const snvc_conv3d_desc *d, const float *weight, void 
     int rc = make_f16_plan(*d, p, split);
     if (rc) return rc;
     if (!weight || !packed) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16_conv3d_pack_weights: null pointer");
+    const F16Form &f = *p.form;
     const int classes = d->transposed ? 8 : 1;
-    const int64_t bytes = 2 * f16_class_stride(p) * classes;
-    if (hipMemsetAsync(packed, 0, (size_t)bytes, as_stream(stream)) != hipSuccess)   // the ring's read-ahead padding
+    if (hipMemsetAsync(packed, 0, (size_t)(2 * p.class_stride() * classes), as_stream(stream)) != hipSuccess)   // the ring's read-ahead padding
         return fail(SNVC_ERR_HIP, "snvc_f16_conv3d_pack_weights: hipMemsetAsync failed");
-    if (p.kind == FK5XQ || p.kind == FK5D2XQ || p.kind == FK7XQ || p.kind == FK5D2Q || p.kind == FK7Q || p.kind == FK5D2QN || p.kind == FK7QN ||
-        p.kind == FK5Q || p.kind == FK5QN) {
-        const int ks = d->ksize, k3 = ks * ks * ks;
-        const int fseg = q16s_flat_segments(ks);      // 5^3: one segment of all 125 taps; 7^3: two of 172 slots
-        const int nseg = fseg, nq = ((k3 + fseg - 1) / fseg + 3) / 4, nt = 4 * nq;
-        const bool sp_ = p.PL >= 2;
-        const int nh_ = sp_ ? 2 : 2 * p.MI;
-        pack_q16s_weights_kernel<<<(unsigned)ceil_div<int64_t>(p.block_halves, 256), 256, 0, as_stream(stream)>>>(
-            weight, reinterpret_cast<_Float16 *>(packed), d->Cout, d->Cin, k3, nseg, nt, nq, p.nchunks, nh_, sp_ ? 2 : 1, sp_ ? 2 : 1, wmul,
-            p.block_halves);
-        return check_launch(who);
-    }
-    if (p.kind == FK3S2XQ) {    // [cb (64 channels)][chunk][quad][co half (4)][hi | lo][lane][8]
-        pack_q16s_weights_kernel<<<(unsigned)ceil_div<int64_t>(p.block_halves, 256), 256, 0, as_stream(stream)>>>(
-            weight, reinterpret_cast<_Float16 *>(packed), d->Cout, d->Cin, 27, 1, 4 * X3S2Cfg::NQ, X3S2Cfg::NQ, p.nchunks, 4, 2, 1, wmul, p.block_halves);
-        return check_launch(who);
-    }
-    if (p.kind == FK3XQ) {      // [cb][chunk][quad][co half][hi | lo][lane][8]: one segment of all 27 taps
-        pack_q16s_weights_kernel<<<(unsigned)ceil_div<int64_t>(p.block_halves, 256), 256, 0, as_stream(stream)>>>(
-            weight, reinterpret_cast<_Float16 *>(packed), d->Cout, d->Cin, 27, 1, 4 * X3QCfg::NQ, X3QCfg::NQ, p.nchunks, 2, 2, 1, wmul, p.block_halves);
+    if (f.q16.NQ) {
+        pack_q16(f.q16, weight, packed, d->Cout, d->Cin, wmul, p.block_halves, as_stream(stream));
         return check_launch(who);
     }
     for (int c = 0; c < classes; ++c) {
-        PackArgs a;
+        PackArgs a = f.pack;
         a.w = weight;
-        a.out = reinterpret_cast<_Float16 *>(packed) + c * f16_class_stride(p);
+        a.out = reinterpret_cast<_Float16 *>(packed) + c * p.class_stride();
         a.Cout = d->Cout; a.Cin = d->Cin; a.K = d->ksize;
         a.transposed = d->transposed; a.pd = (c >> 2) & 1; a.ph = (c >> 1) & 1; a.pw = c & 1;
-        a.KD = p.KD; a.KH = p.KH; a.KW = p.KW; a.KCG = p.KCG; a.MODE = p.MODE; a.MI = p.MI; a.SEGS = p.SEGS;
-        a.TSEG = p.TSEG; a.NPS = p.NPS; a.NS = p.NS; a.unroll_d = p.unroll_d;
         a.nchunks = p.nchunks; a.cblocks = p.cblocks; a.total = p.block_halves;
-        a.PL = p.PL; a.PASSES = p.PASSES; a.wmul = wmul;
-        a.dyn = p.dyn;
-        if (p.dyn) {        // compact per class: 2 * pairs k-steps per chunk
+        a.wmul = wmul;
+        if (a.dyn) {        // compact per class: 2 * pairs k-steps per chunk
             const int T = (1 + a.pd) * (1 + a.ph) * (1 + a.pw);
             a.NS = 2 * (T > 1 ? T / 2 : 1);
-            a.total = (int64_t)p.cblocks * p.nchunks * a.NS * p.MI * 2 * 64 * 8;
+            a.total = (int64_t)p.cblocks * p.nchunks * a.NS * a.MI * 2 * 64 * 8;
         }
         pack_f16_weights_kernel<<<(unsigned)ceil_div<int64_t>(a.total, 256), 256, 0, as_stream(stream)>>>(a);
     }
@@ -2414,13 +2515,6 @@ static int f16_pack_common(const snvc_conv3d_desc *d, const float *weight, void 
 
 int snvc_f16_conv3d_pack_weights(const snvc_conv3d_desc *d, const float *weight, void *packed, void *stream) {
     return f16_pack_common(d, weight, packed, false, 1.0f, stream, "snvc_f16_conv3d_pack_weights");
-}
-
-int64_t snvc_f16x3_conv3d_packed_weight_bytes(const snvc_conv3d_desc *d) {
-    using namespace snvc;
-    F16Plan p;
-    if (!d || make_f16_plan(*d, p, true) != SNVC_OK) return -1;
-    return 2 * f16_class_stride(p) * (d->transposed ? 8 : 1);
 }
 
 int snvc_f16x3_conv3d_pack_weights(const snvc_conv3d_desc *d, const float *weight, void *packed, float wmul, void *stream) {
@@ -2458,6 +2552,7 @@ int snvc_f16_conv3d_forward(const snvc_conv3d_desc *d, const void *x, const void
 
     F16Args a{};
     a.x = reinterpret_cast<const _Float16 *>(x);
+    a.wp = reinterpret_cast<const _Float16 *>(packed_weight);
     a.scale = scale; a.bias = bias;
     a.res = resflags ? reinterpret_cast<const _Float16 *>(residual) : nullptr;
     a.y = reinterpret_cast<_Float16 *>(y); a.y_f32 = y_f32;
@@ -2471,246 +2566,127 @@ int snvc_f16_conv3d_forward(const snvc_conv3d_desc *d, const void *x, const void
     a.y_bs = d->y_batch_stride ? d->y_batch_stride : (int64_t)d->Cout * out_sp;
     a.r_bs = d->res_batch_stride ? d->res_batch_stride : (int64_t)d->Cout * out_sp;
     a.yf_bs = out_sp;
-    hipStream_t st = as_stream(stream);
-    const bool subgrid = p.kind == FK5D2 || p.kind == FK5D2N || p.kind == FK5D2Q || p.kind == FK5D2QN;      // (depth, height) parity classes share ONE packed weight block
-    const int classes = d->transposed ? 8 : (subgrid ? 4 : 1);
-    a.wp = reinterpret_cast<const _Float16 *>(packed_weight);
-    a.N = d->N; a.cls_mode = d->transposed ? 1 : (subgrid ? 2 : 0); a.cls_wstride = f16_class_stride(p);
-    a.isd = a.ish = 1; a.iod = a.ioh = 0; a.offd = a.offh = a.offw = 0;
-    if (d->transposed) {
-        a.nd = d->Din; a.nh = d->Hin; a.nw = d->Win;
-        a.osd = a.osh = a.osw = 2;
-        a.pad_d = a.pad_h = a.pad_w = 0;
-    } else if (subgrid) {
-        a.nd = (d->Dout + 1) / 2; a.nh = (d->Hout + 1) / 2; a.nw = d->Wout;     // the largest class; the kernel trims the others
-        a.osd = a.osh = 2; a.osw = 1;
-        a.isd = a.ish = 2;
-        a.pad_d = a.pad_h = d->pad / 2; a.pad_w = d->pad;
-    } else {
-        a.nd = d->Dout; a.nh = d->Hout; a.nw = d->Wout;
-        a.osd = a.osh = a.osw = 1;
-        a.pad_d = a.pad_h = a.pad_w = d->pad;
-    }
-    a.tiles_d = ceil_div(a.nd, p.TD); a.tiles_h = ceil_div(a.nh, p.TH); a.tiles_w = ceil_div(a.nw, 32);
-    const int64_t ntiles = (int64_t)a.tiles_d * a.tiles_h * a.tiles_w;
-    if (ntiles >= ((int64_t)1 << 30) || (int64_t)d->N * classes > 65535)
+    const F16Geom g = f16_geometry(*d, p, a);
+    if (g.ntiles >= ((int64_t)1 << 30) || (int64_t)d->N * g.classes > 65535)
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d_forward: too many tiles or samples");
-    dim3 grid((unsigned)(d->transposed ? 2 * ntiles : ntiles), (unsigned)p.cblocks, (unsigned)(d->N * (d->transposed ? 4 : classes)));
-    switch (p.kind) {
-        case FK7QN: case FK5D2QN: case FK5QN: {
-            using C7 = Q16SCfg<7, 1, 1, 1>; using C5D = Q16SCfg<5, 2, 1, 1>; using C5 = Q16SCfg<5, 1, 1, 1>;
-            if (p.kind == FK7QN) launch_lds<conv3d_q16s_kernel<C7>>(grid, 256, C7::LDS_BYTES, st, a);
-            else if (p.kind == FK5QN) launch_lds<conv3d_q16s_kernel<C5>>(grid, 256, C5::LDS_BYTES, st, a);
-            else launch_lds<conv3d_q16s_kernel<C5D>>(grid, 256, C5D::LDS_BYTES, st, a);
-            break;
-        }
-        case FK7Q: case FK5D2Q: case FK5Q: {
-            if (plane) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d_forward: the 16x16x32 form writes C8 tensors");
-            using C7 = Q16SCfg<7, 1, 1, 2>; using C5D = Q16SCfg<5, 2, 1, 2>; using C5 = Q16SCfg<5, 1, 1, 2>;
-            if (p.kind == FK7Q) launch_lds<conv3d_q16s_kernel<C7>>(grid, 256, C7::LDS_BYTES, st, a);
-            else if (p.kind == FK5Q) launch_lds<conv3d_q16s_kernel<C5>>(grid, 256, C5::LDS_BYTES, st, a);
-            else launch_lds<conv3d_q16s_kernel<C5D>>(grid, 256, C5D::LDS_BYTES, st, a);
-            break;
-        }
-        case FK1: launch_f16<F16K1, 0>(a, grid, st); break;
-        case FK3: launch_f16<F16K3, 0>(a, grid, st); break;
-        case FK3H: launch_f16<F16K3H, 1>(a, grid, st); break;
-        case FK3S2: launch_f16<F16K3S2, 0>(a, grid, st); break;
-        case FK5: launch_f16<F16K5, 0>(a, grid, st); break;
-        case FK5D2: launch_f16<F16K5D2, 0>(a, grid, st); break;
-        case FK7: launch_f16<F16K7, 0>(a, grid, st); break;
-        case FDC: launch_f16<F16DC, 0>(a, grid, st); break;
-        case FK1N: launch_f16<F16K1N, 0>(a, grid, st); break;
-        case FK3N: launch_f16<F16K3H, 0>(a, grid, st); break;
-        case FK3S2N: launch_f16<F16K3S2N, 0>(a, grid, st); break;
-        case FK5N: launch_f16<F16K5N, 0>(a, grid, st); break;
-        case FK5D2N: launch_f16<F16K5D2N, 0>(a, grid, st); break;
-        case FK7N: launch_f16<F16K7N, 0>(a, grid, st); break;
-        case FDCN: launch_f16<F16DCN, 0>(a, grid, st); break;
-        default: return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16_conv3d_forward: no kernel");
-    }
+    const F16Launch launch = p.form->launch[plane ? TO_PLANE : TO_C8];
+    if (!launch) return fail(SNVC_ERR_UNSUPPORTED, p.form->unsupported);
+    launch(a, g, as_stream(stream));
     return check_launch("snvc_f16_conv3d_forward");
 }
 
-static int f16x3_forward(const snvc_conv3d_desc *d, const void *x_hi, const void *x_lo, const void *packed_weight,
-                         const float *scale, const float *bias, const void *res_hi, const void *res_lo, void *y_hi,
-                         void *y_lo, float *y_f32, const float *head, float *y_head, float head_mul, float res_mul,
-                         int *overflow, const void *tail_w, float *t_out, float tail_mul, void *stream, double *stats = nullptr,
-                         int64_t *stats_slots = nullptr, const float *x_mul = nullptr, const snvc::F16SrcArgs *src = nullptr) {
+// One call of a split layer: what the five entry points below set, everything else null or zero.
+struct F16x3Call {
+    const void *x_hi = nullptr, *x_lo = nullptr, *packed_weight = nullptr;
+    const float *scale = nullptr, *bias = nullptr;
+    const void *res_hi = nullptr, *res_lo = nullptr;      // the split residual of ADD_PRE / ADD_POST
+    const float *res_f32 = nullptr;                       // a float32 result's float32 NCDHW residual (added after the activation, no flag)
+    void *y_hi = nullptr, *y_lo = nullptr;
+    float *y_f32 = nullptr;
+    const float *head = nullptr;
+    float *y_head = nullptr;
+    float head_mul = 0.0f, res_mul = 0.0f;
+    int *overflow = nullptr;
+    const void *tail_w = nullptr;                         // EPI 4: the result is contracted with a one-channel transposed layer's taps, not stored
+    float *t_out = nullptr;
+    float tail_mul = 0.0f;
+    double *stats = nullptr;                              // the statistics epilogue's workspace; stats_slots: its slots per sample (out)
+    int64_t *stats_slots = nullptr;
+    const float *x_mul = nullptr;
+    const snvc::F16SrcArgs *src = nullptr;                // the fused sheared first layer: the image's producer
+    void *stream = nullptr;
+};
+
+static int f16x3_forward(const snvc_conv3d_desc *d, const F16x3Call &c) {
     using namespace snvc;
     F16Plan p;
     if (!d) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: null desc");
     int rc = make_f16_plan(*d, p, true);
     if (rc) return rc;
     if (d->N == 0) return SNVC_OK;
-    const bool tail = tail_w != nullptr;          // EPI 4: the result is contracted with a one-channel transposed layer's taps, not stored
-    if (tail && (!t_out || !d->transposed || p.cblocks != 1 || d->Cout != 32 * p.MI || (reinterpret_cast<uintptr_t>(tail_w) & 15)))
+    const F16Form &f = *p.form;
+    const bool tail = c.tail_w != nullptr;
+    if (tail && (!c.t_out || !f.launch[TO_TAIL] || p.cblocks != 1 || d->Cout != 32 * f.MI || (reinterpret_cast<uintptr_t>(c.tail_w) & 15)))
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_deconv3d_tail_forward: a transposed split layer whose 32 or 64 output channels sit in one block");
     const bool plane = d->Cout == 1;              // the occupancy head: y_f32 is then the fp32 plane [N][1][D][H][W] (Sigmoid honoured)
-    const bool to_f32 = y_f32 != nullptr;
+    const bool to_f32 = c.y_f32 != nullptr;
     if (plane && !to_f32) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: a one-channel layer writes y_f32");
-    if ((!src && (!x_hi || !x_lo)) || !packed_weight || (!tail && !to_f32 && (!y_hi || !y_lo)))
+    if ((!c.src && (!c.x_hi || !c.x_lo)) || !c.packed_weight || (!tail && !to_f32 && (!c.y_hi || !c.y_lo)))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: null pointer");
-    if ((scale == nullptr) != (bias == nullptr))
+    if ((c.scale == nullptr) != (c.bias == nullptr))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: scale and bias must both be given or both be NULL");
-    int resflags = d->flags & (SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST);
-    // r6: a float32 result (y_f32) takes a float32 NCDHW residual of its own shape and batch stride: res_hi = that tensor, res_lo = NULL,
-    // ADD_POST only (the data gradients of the training step add a skip connection's gradient this way)
-    const float *res_f32 = nullptr;
-    if (resflags == SNVC_EPI_ADD_POST && to_f32 && !plane && res_hi && !res_lo && !tail_w) {
-        if (d->res_batch_stride && d->res_batch_stride != (d->y_batch_stride ? d->y_batch_stride : (int64_t)d->Cout * d->Dout * d->Hout * d->Wout))
-            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: a float32 residual shares the result's batch stride");
-        res_f32 = reinterpret_cast<const float *>(res_hi);
-        res_hi = nullptr;
-        resflags = 0;
-    }
-    if (resflags && (!res_hi || !res_lo || plane))
+    // r6: a float32 result takes a float32 NCDHW residual of its own shape and batch stride, added after the activation: it stands for
+    // ADD_POST (the data gradients of the training step add a skip connection's gradient this way)
+    const int flags = c.res_f32 ? (d->flags & ~SNVC_EPI_ADD_POST) : d->flags;
+    const int resflags = flags & (SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST);
+    if (c.res_f32 && !plane && d->res_batch_stride && d->res_batch_stride != (d->y_batch_stride ? d->y_batch_stride : (int64_t)d->Cout * d->Dout * d->Hout * d->Wout))
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: a float32 residual shares the result's batch stride");
+    if ((resflags && (!c.res_hi || !c.res_lo)) || ((resflags || c.res_f32) && plane))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: residual flag without a split residual");
     if (resflags == (SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: ADD_PRE and ADD_POST are exclusive");
     if (d->flags & ~(SNVC_EPI_RELU | SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST | (plane ? SNVC_EPI_SIGMOID : 0)))
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: RELU / ADD_PRE / ADD_POST only (SIGMOID with the one-channel output)");
-    if ((head != nullptr) != (y_head != nullptr))
+    if ((c.head != nullptr) != (c.y_head != nullptr))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: head and y_head go together");
-    if (head && ((p.kind != FK3X && p.kind != FK3XS && p.kind != FK3XT && p.kind != FK3XQ) || d->Cout != 32 || to_f32))
+    if (c.head && (!f.launch[TO_HEAD] || d->Cout != 32 || to_f32))
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: the side head is built for 32-channel stride-1 layers with a split output");
     const int64_t in_sp = (int64_t)d->Din * d->Hin * d->Win, out_sp = (int64_t)d->Dout * d->Hout * d->Wout;
     if ((int64_t)(d->Cin / 8 + 2) * in_sp >= ((int64_t)1 << 31) || out_sp >= ((int64_t)1 << 31))
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: one sample must stay below 2^31 pieces");
-    if ((reinterpret_cast<uintptr_t>(x_hi) | reinterpret_cast<uintptr_t>(x_lo) | reinterpret_cast<uintptr_t>(y_hi) |
-         reinterpret_cast<uintptr_t>(y_lo) | reinterpret_cast<uintptr_t>(res_hi) | reinterpret_cast<uintptr_t>(res_lo) |
-         reinterpret_cast<uintptr_t>(packed_weight) | reinterpret_cast<uintptr_t>(scale) | reinterpret_cast<uintptr_t>(bias) |
-         reinterpret_cast<uintptr_t>(head)) & 15)
+    if ((reinterpret_cast<uintptr_t>(c.x_hi) | reinterpret_cast<uintptr_t>(c.x_lo) | reinterpret_cast<uintptr_t>(c.y_hi) |
+         reinterpret_cast<uintptr_t>(c.y_lo) | reinterpret_cast<uintptr_t>(c.res_hi) | reinterpret_cast<uintptr_t>(c.res_lo) |
+         reinterpret_cast<uintptr_t>(c.packed_weight) | reinterpret_cast<uintptr_t>(c.scale) | reinterpret_cast<uintptr_t>(c.bias) |
+         reinterpret_cast<uintptr_t>(c.head)) & 15)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: C8 tensors and the per-channel vectors must be 16-byte aligned");
-    if ((d->x_batch_stride | (res_f32 ? 0 : d->res_batch_stride)) % 8 || (!to_f32 && d->y_batch_stride % 8))
+    if ((d->x_batch_stride | (c.res_f32 ? 0 : d->res_batch_stride)) % 8 || (!to_f32 && d->y_batch_stride % 8))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward: batch strides must be multiples of 8 elements");
-    F16Args a{};
-    a.x = reinterpret_cast<const _Float16 *>(x_hi); a.x_lo = reinterpret_cast<const _Float16 *>(x_lo);
-    a.scale = scale; a.bias = bias;
-    a.res = resflags ? reinterpret_cast<const _Float16 *>(res_hi) : nullptr;
-    a.res_lo = resflags ? reinterpret_cast<const _Float16 *>(res_lo) : nullptr;
-    a.y = reinterpret_cast<_Float16 *>(y_hi); a.y_lo = reinterpret_cast<_Float16 *>(y_lo); a.y_f32 = y_f32;
-    a.head = head; a.y_head = y_head; a.head_mul = head_mul; a.res_mul = res_mul; a.overflow = overflow;
-    a.res_f32 = res_f32;
-    a.stats = stats;
-    a.x_mul = to_f32 ? x_mul : nullptr;
-    a.tail_w = reinterpret_cast<const _Float16 *>(tail_w); a.t_out = t_out; a.tail_mul = tail_mul;
+    F16SrcArgs b{};             // an F16Args for every form; the fused source's fields behind it
+    if (c.src) b = *c.src;
+    F16Args &a = b;
+    a = F16Args{};
+    a.x = reinterpret_cast<const _Float16 *>(c.x_hi); a.x_lo = reinterpret_cast<const _Float16 *>(c.x_lo);
+    a.wp = reinterpret_cast<const _Float16 *>(c.packed_weight);
+    a.scale = c.scale; a.bias = c.bias;
+    a.res = resflags ? reinterpret_cast<const _Float16 *>(c.res_hi) : nullptr;
+    a.res_lo = resflags ? reinterpret_cast<const _Float16 *>(c.res_lo) : nullptr;
+    a.y = reinterpret_cast<_Float16 *>(c.y_hi); a.y_lo = reinterpret_cast<_Float16 *>(c.y_lo); a.y_f32 = c.y_f32;
+    a.head = c.head; a.y_head = c.y_head; a.head_mul = c.head_mul; a.res_mul = c.res_mul; a.overflow = c.overflow;
+    a.res_f32 = c.res_f32;
+    a.stats = c.stats;
+    a.x_mul = to_f32 ? c.x_mul : nullptr;
+    a.tail_w = reinterpret_cast<const _Float16 *>(c.tail_w); a.t_out = c.t_out; a.tail_mul = c.tail_mul;
     a.t_bs = (int64_t)27 * 8 * d->Din * d->Hin * d->Win;
     a.CGin = d->Cin / 8; a.Cout = d->Cout;
     a.Din = d->Din; a.Hin = d->Hin; a.Win = d->Win;
     a.Dout = d->Dout; a.Hout = d->Hout; a.Wout = d->Wout;
-    a.nchunks = p.nchunks; a.flags = res_f32 ? (d->flags & ~SNVC_EPI_ADD_POST) : d->flags;
+    a.nchunks = p.nchunks; a.flags = flags;
     a.x_bs = d->x_batch_stride ? d->x_batch_stride : 2 * (int64_t)d->Cin * in_sp;
     a.y_bs = d->y_batch_stride ? d->y_batch_stride : 2 * (int64_t)d->Cout * out_sp;
     a.r_bs = d->res_batch_stride ? d->res_batch_stride : 2 * (int64_t)d->Cout * out_sp;
     a.yf_bs = plane ? out_sp : (d->y_batch_stride ? d->y_batch_stride : (int64_t)d->Cout * out_sp);
-    a.wp = reinterpret_cast<const _Float16 *>(packed_weight);
-    const bool subgrid = p.kind == FK5D2X || p.kind == FK5D2XQ;        // (depth, height) parity classes share ONE packed weight block
-    const int classes = d->transposed ? 8 : (subgrid ? 4 : 1);
-    a.N = d->N; a.cls_mode = d->transposed ? 1 : (subgrid ? 2 : 0); a.cls_wstride = f16_class_stride(p);
-    a.isd = a.ish = 1; a.iod = a.ioh = 0; a.offd = a.offh = a.offw = 0;
-    if (d->transposed) {
-        a.nd = d->Din; a.nh = d->Hin; a.nw = d->Win;
-        a.osd = a.osh = a.osw = 2;
-        a.pad_d = a.pad_h = a.pad_w = 0;
-    } else if (subgrid) {
-        a.nd = (d->Dout + 1) / 2; a.nh = (d->Hout + 1) / 2; a.nw = d->Wout;     // the largest class; the kernel trims the others
-        a.osd = a.osh = 2; a.osw = 1;
-        a.isd = a.ish = 2;
-        a.pad_d = a.pad_h = d->pad / 2; a.pad_w = d->pad;
-    } else {
-        a.nd = d->Dout; a.nh = d->Hout; a.nw = d->Wout;
-        a.osd = a.osh = a.osw = 1;
-        a.pad_d = a.pad_h = a.pad_w = d->pad;
-    }
-    a.tiles_d = ceil_div(a.nd, p.TD); a.tiles_h = ceil_div(a.nh, p.TH); a.tiles_w = ceil_div(a.nw, 32);
-    const int64_t ntiles = (int64_t)a.tiles_d * a.tiles_h * a.tiles_w;
-    if (ntiles >= ((int64_t)1 << 30) || (int64_t)d->N * classes > 65535)
+    const F16Geom g = f16_geometry(*d, p, a);
+    if (g.ntiles >= ((int64_t)1 << 30) || (int64_t)d->N * g.classes > 65535)
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles or samples");
-    dim3 grid((unsigned)(d->transposed ? 2 * ntiles : ntiles), (unsigned)p.cblocks, (unsigned)(d->N * (d->transposed ? 4 : classes)));
-    hipStream_t st = as_stream(stream);
-    if (stats_slots) {          // the statistics epilogue (r6): only the forms that write float32 through the shared epilogue, 256 threads
-        const bool form_ok = to_f32 && !plane && !tail && (p.kind == FK3XQ || p.kind == FK3X || p.kind == FK3X2 || p.kind == FK3XS || p.kind == FK3X2S || p.kind == FK3XT ||
-                                                            p.kind == FK3S2X || p.kind == FK3S2XT || p.kind == FDCX || p.kind == FDCXT || p.kind == FDCXN);
-        if (!form_ok) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward_stats: this layer's kernel form has no statistics epilogue");
-        *stats_slots = p.kind == FK3XQ ? ntiles * 4 : (int64_t)(grid.z / d->N) * grid.x * 4;
-        if (!stats) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward_stats: null workspace");
+    hipStream_t st = as_stream(c.stream);
+    if (c.stats_slots) {        // the statistics epilogue (r6): only the forms that write float32 through the shared epilogue, 256 threads
+        if (!(to_f32 && !plane && !tail && f.stats))
+            return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward_stats: this layer's kernel form has no statistics epilogue");
+        *c.stats_slots = g.stats_slots;
+        if (!c.stats) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward_stats: null workspace");
         // whole tiles outside a smaller parity class return early: their slots must read as zero (one class: every workgroup writes its slots)
-        if (classes > 1) {
-            const hipError_t e = hipMemsetAsync(stats, 0, (size_t)d->N * *stats_slots * ((d->Cout + 31) / 32) * 64 * sizeof(double), st);
+        if (g.classes > 1) {
+            const hipError_t e = hipMemsetAsync(c.stats, 0, (size_t)d->N * g.stats_slots * ((d->Cout + 31) / 32) * 64 * sizeof(double), st);
             if (e != hipSuccess) return fail(SNVC_ERR_HIP, "snvc_f16x3_conv3d_forward_stats: hipMemsetAsync failed");
         }
     }
-    if (src && p.kind != FK3XQ)
+    if (c.src && !f.launch[TO_SRC])
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a 3x3x3 stride-1 layer on the 16x16x32 form (SNVC_ALGO_X3_Q16)");
-#define SNVC_X3_LAUNCH(CFG) do { if (to_f32) launch_f16<CFG, 2>(a, grid, st); else launch_f16<CFG, 0>(a, grid, st); } while (0)
-    switch (p.kind) {
-        case FK3X:
-            if (to_f32) launch_f16<F16K3X, 2>(a, grid, st);
-            else if (head) launch_f16<F16K3X, 3>(a, grid, st);
-            else launch_f16<F16K3X, 0>(a, grid, st);
-            break;
-        case FK3X2: SNVC_X3_LAUNCH(F16K3X2); break;
-        case FK3XS:
-            if (to_f32) launch_f16<F16K3XS, 2>(a, grid, st);
-            else if (head) launch_f16<F16K3XS, 3>(a, grid, st);
-            else launch_f16<F16K3XS, 0>(a, grid, st);
-            break;
-        case FK3X2S: SNVC_X3_LAUNCH(F16K3X2S); break;
-        case FK3XT:
-            if (to_f32) launch_f16<F16K3XT, 2>(a, grid, st);
-            else if (head) launch_f16<F16K3XT, 3>(a, grid, st);
-            else launch_f16<F16K3XT, 0>(a, grid, st);
-            break;
-        case FK3S2X: SNVC_X3_LAUNCH(F16K3S2X); break;
-        case FK3S2XT: SNVC_X3_LAUNCH(F16K3S2XT); break;
-        case FDCX: if (tail) launch_f16<F16DCX, 4>(a, grid, st); else SNVC_X3_LAUNCH(F16DCX); break;
-        case FDCXT: if (tail) launch_f16<F16DCXT, 4>(a, grid, st); else SNVC_X3_LAUNCH(F16DCXT); break;
-        case FDCXN: if (tail) launch_f16<F16DCXN, 4>(a, grid, st); else SNVC_X3_LAUNCH(F16DCXN); break;
-        case FK1X: SNVC_X3_LAUNCH(F16K1X); break;
-        case FK5X: SNVC_X3_LAUNCH(F16K5X); break;
-        case FK5D2X: SNVC_X3_LAUNCH(F16K5D2X); break;
-        case FK7X: SNVC_X3_LAUNCH(F16K7X); break;
-        case FK3XH: launch_f16<F16K3X, 1>(a, grid, st); break;
-        case FK5XQ: case FK5D2XQ: case FK7XQ: {
-            if (to_f32 || head) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: the 16x16x32 form writes a split C8 tensor, no side head");
-            using C5 = Q16SCfg<5, 1>; using C5D = Q16SCfg<5, 2>; using C7 = Q16SCfg<7, 1>;
-            if (p.kind == FK5XQ) launch_lds<conv3d_q16s_kernel<C5>>(grid, 256, C5::LDS_BYTES, st, a);
-            else if (p.kind == FK5D2XQ) launch_lds<conv3d_q16s_kernel<C5D>>(grid, 256, C5D::LDS_BYTES, st, a);
-            else launch_lds<conv3d_q16s_kernel<C7>>(grid, 256, C7::LDS_BYTES, st, a);
-            break;
-        }
-        case FK3S2XQ: {
-            if (to_f32 || resflags || head) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: the stride-2 16x16x32 form writes a split C8 tensor, no residual / head");
-            // persistent: one workgroup per CU (144 KB of LDS each), a multiple of 8 so that a workgroup's jobs b, b + G, ... stay on its XCD
-            const int64_t total = ntiles * p.cblocks * d->N;
-            if (total >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles");
-            int g = device_cu_count();
-            if (g <= 0) g = 256;
-            if (total < g) g = total >= 8 ? (int)(total & ~(int64_t)7) : (int)total;
-            launch_lds<conv3d_x3s2q_kernel>(dim3((unsigned)g), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)total);
-            break;
-        }
-        case FK3XQ: {
-            if (resflags || (to_f32 && head)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: the 16x16x32 form has no split residual, no side head beside a float32 result");
-            if (ntiles * p.cblocks >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles");
-            grid = dim3((unsigned)(ntiles * p.cblocks), 1, (unsigned)d->N);      // (tile, channel block) jobs, channel block fastest
-            if (src) {      // the fused sheared first layer: the image is formed in the launch
-                if (to_f32) return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a split C8 output");
-                F16SrcArgs b = *src;
-                static_cast<F16Args &>(b) = a;
-                if (head) launch_lds<conv3d_x3q_kernel<3, 1>>(grid, 256, X3QCfg::LDS_BYTES, st, b);
-                else launch_lds<conv3d_x3q_kernel<0, 1>>(grid, 256, X3QCfg::LDS_BYTES, st, b);
-                break;
-            }
-            if (to_f32) launch_lds<conv3d_x3q_kernel<2>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
-            else if (head) launch_lds<conv3d_x3q_kernel<3>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
-            else launch_lds<conv3d_x3q_kernel<0>>(grid, 256, X3QCfg::LDS_BYTES, st, a);
-            break;
-        }
-        default: return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: no kernel");
-    }
-#undef SNVC_X3_LAUNCH
+    const F16Call call = tail ? TO_TAIL : plane ? TO_PLANE : to_f32 ? TO_F32 : c.head ? (c.src ? TO_SRC_HEAD : TO_HEAD) : (c.src ? TO_SRC : TO_C8);
+    if (!f.launch[call] || (resflags && !f.split_res)) return fail(SNVC_ERR_UNSUPPORTED, f.unsupported);
+    if (g.jobs >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles");
+    if (c.src && to_f32) return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a split C8 output");
+    f.launch[call](b, g, st);
     return check_launch("snvc_f16x3_conv3d_forward");
 }
 
@@ -2718,8 +2694,16 @@ int snvc_f16x3_conv3d_forward(const snvc_conv3d_desc *d, const void *x_hi, const
                               const float *scale, const float *bias, const void *res_hi, const void *res_lo, void *y_hi,
                               void *y_lo, float *y_f32, const float *head, float *y_head, float head_mul, float res_mul,
                               int *overflow, void *stream) {
-    return f16x3_forward(d, x_hi, x_lo, packed_weight, scale, bias, res_hi, res_lo, y_hi, y_lo, y_f32, head, y_head, head_mul, res_mul,
-                         overflow, nullptr, nullptr, 0.0f, stream);
+    F16x3Call c;
+    c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias;
+    c.res_hi = res_hi; c.res_lo = res_lo; c.y_hi = y_hi; c.y_lo = y_lo; c.y_f32 = y_f32;
+    c.head = head; c.y_head = y_head; c.head_mul = head_mul; c.res_mul = res_mul; c.overflow = overflow; c.stream = stream;
+    // r6: with y_f32 and ADD_POST alone, res_hi without res_lo is the float32 residual (include/snvc_hip.h)
+    if (d && (d->flags & (SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST)) == SNVC_EPI_ADD_POST && y_f32 && d->Cout != 1 && res_hi && !res_lo) {
+        c.res_f32 = static_cast<const float *>(res_hi);
+        c.res_hi = nullptr;
+    }
+    return f16x3_forward(d, c);
 }
 
 int snvc_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias, void *y_hi,
@@ -2744,21 +2728,10 @@ int snvc_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packe
     F16SrcArgs s{};
     s.gi = gi; s.p_il = p_il; s.v_scale = v_scale; s.v_bias = v_bias; s.gi_bs = 6 * CG * H * pitch * 8;
     s.v_pitch = (int)pitch; s.v_lp = (int)lp; s.v_q = q; s.v_m0 = m0; s.v_off = off; s.v_off2 = off2; s.v_flags = v_flags;
-    return f16x3_forward(d, nullptr, nullptr, packed_weight, scale, bias, nullptr, nullptr, y_hi, y_lo, nullptr, head, y_head, head_mul, 1.0f,
-                         overflow, nullptr, nullptr, 0.0f, stream, nullptr, nullptr, nullptr, &s);
-}
-
-// slots per sample of the statistics epilogue = (z classes) * gridDim.x * 4 waves, as f16x3_forward lays its grid out
-static int64_t f16x3_stats_slots(const snvc_conv3d_desc &d, const snvc::F16Plan &p) {
-    using namespace snvc;
-    const bool subgrid = p.kind == FK5D2X || p.kind == FK5D2XQ;
-    int nd, nh, nw;
-    if (d.transposed) { nd = d.Din; nh = d.Hin; nw = d.Win; }
-    else if (subgrid) { nd = (d.Dout + 1) / 2; nh = (d.Hout + 1) / 2; nw = d.Wout; }
-    else { nd = d.Dout; nh = d.Hout; nw = d.Wout; }
-    const int64_t ntiles = (int64_t)ceil_div(nd, p.TD) * ceil_div(nh, p.TH) * ceil_div(nw, 32);
-    if (p.kind == FK3XQ) return ntiles * 4;              // (tile, channel block) jobs on gridDim.x: a slot per tile and wave
-    return (d.transposed ? 4 * 2 * ntiles : (subgrid ? 4 : 1) * ntiles) * 4;
+    F16x3Call c;
+    c.packed_weight = packed_weight; c.scale = scale; c.bias = bias; c.y_hi = y_hi; c.y_lo = y_lo;
+    c.head = head; c.y_head = y_head; c.head_mul = head_mul; c.res_mul = 1.0f; c.overflow = overflow; c.src = &s; c.stream = stream;
+    return f16x3_forward(d, c);
 }
 
 int64_t snvc_f16x3_conv3d_stats_workspace_bytes(const snvc_conv3d_desc *d) {
@@ -2766,7 +2739,8 @@ int64_t snvc_f16x3_conv3d_stats_workspace_bytes(const snvc_conv3d_desc *d) {
     F16Plan p;
     if (!d || d->N < 0 || make_f16_plan(*d, p, true)) return -1;
     const int64_t groups = (d->Cout + 31) / 32;
-    const int64_t slots = f16x3_stats_slots(*d, p);
+    F16Args a{};
+    const int64_t slots = f16_geometry(*d, p, a).stats_slots;      // of the grid that f16x3_forward launches
     return (d->N * slots * groups * 64 + conv_stats_fold_scratch_doubles(d->N, (int)groups, slots) + d->N * (int64_t)d->Cout * 2) * (int64_t)sizeof(double);
 }
 
@@ -2776,10 +2750,10 @@ int snvc_f16x3_conv3d_forward_f32(const snvc_conv3d_desc *d, const void *x_hi, c
     using namespace snvc;
     if (!d || !y_f32) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward_f32: null pointer");
     if (d->flags & (SNVC_EPI_ADD_PRE | SNVC_EPI_ADD_POST)) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv3d_forward_f32: the residual is res_f32 (added after the activation), no flag");
-    snvc_conv3d_desc dd = *d;
-    if (res_f32) dd.flags |= SNVC_EPI_ADD_POST;
-    return f16x3_forward(&dd, x_hi, x_lo, packed_weight, scale, bias, res_f32, nullptr, nullptr, nullptr, y_f32, nullptr, nullptr, out_mul, 1.0f,
-                         nullptr, nullptr, nullptr, 0.0f, stream, nullptr, nullptr, x_mul);
+    F16x3Call c;
+    c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias; c.x_mul = x_mul;
+    c.res_f32 = res_f32; c.y_f32 = y_f32; c.head_mul = out_mul; c.res_mul = 1.0f; c.stream = stream;
+    return f16x3_forward(d, c);
 }
 
 int snvc_f16x3_conv3d_forward_stats(const snvc_conv3d_desc *d, const void *x_hi, const void *x_lo, const void *packed_weight,
@@ -2792,8 +2766,10 @@ int snvc_f16x3_conv3d_forward_stats(const snvc_conv3d_desc *d, const void *x_hi,
     if (d->N <= 0 || d->flags || d->Cout % 32) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward_stats: whole 32-channel groups, no epilogue flags");
     double *stats = static_cast<double *>(workspace);
     int64_t slots = 0;
-    int rc = f16x3_forward(d, x_hi, x_lo, packed_weight, scale, bias, nullptr, nullptr, nullptr, nullptr, y_f32, nullptr, nullptr, head_mul, 1.0f,
-                           nullptr, nullptr, nullptr, 0.0f, stream, stats, &slots, x_mul);
+    F16x3Call c;
+    c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias; c.x_mul = x_mul;
+    c.y_f32 = y_f32; c.head_mul = head_mul; c.res_mul = 1.0f; c.stats = stats; c.stats_slots = &slots; c.stream = stream;
+    int rc = f16x3_forward(d, c);
     if (rc) return rc;
     const int groups = d->Cout / 32;
     double *scratch = stats + d->N * slots * groups * 64;
@@ -2834,9 +2810,8 @@ int snvc_f16x3_conv2d_pack_weights(const float *weight, int cout, int cin, int k
         return fail(SNVC_ERR_HIP, "snvc_f16x3_conv2d_pack_weights: hipMemsetAsync failed");
     const int nq = x2q_nq(kh, kw);
     const int64_t total = (int64_t)(cout / 32) * (cin / 8) * nq * 4 * 64 * 8;
-    // [cb][chunk][quad][co half][hi | lo][lane][8] over the (kh, kw) raster: the 3x3x3 form's packer with K3 = kh * kw taps
-    pack_q16s_weights_kernel<<<(unsigned)ceil_div<int64_t>(total, 256), 256, 0, as_stream(stream)>>>(
-        weight, reinterpret_cast<_Float16 *>(packed), cout, cin, kh * kw, 1, 4 * nq, nq, cin / 8, 2, 2, 1, wmul, total);
+    // [cb][chunk][quad][co half][hi | lo][lane][8] over the (kh, kw) raster: the 3x3x3 form's layout with K3 = kh * kw taps
+    pack_q16({kh * kw, 1, nq, 2, 2, 1}, weight, packed, cout, cin, wmul, total, as_stream(stream));
     return check_launch("snvc_f16x3_conv2d_pack_weights");
 }
 
@@ -2846,16 +2821,6 @@ struct snvc_il_out {
     int64_t bs, pitch, lp, cls0, classes;
     int mode;
 };
-
-static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
-                                float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
-                                const float *x_mul_dev, int flags, void *stream, const snvc_il_out *il);
-
-int snvc_f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
-                              float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
-                              const float *x_mul_dev, int flags, void *stream) {
-    return f16x3_conv2d_forward(x_hi, x_lo, packed_weight, scale, bias, y, N, Cin, Cout, H, W, kh, kw, out_mul, x_mul_dev, flags, stream, nullptr);
-}
 
 static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
                                 float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
@@ -2912,31 +2877,15 @@ static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *
     return check_launch("snvc_f16x3_conv2d_forward");
 }
 
+int snvc_f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
+                              float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
+                              const float *x_mul_dev, int flags, void *stream) {
+    return f16x3_conv2d_forward(x_hi, x_lo, packed_weight, scale, bias, y, N, Cin, Cout, H, W, kh, kw, out_mul, x_mul_dev, flags, stream, nullptr);
+}
+
 // The sheared first layer's whole 2D prep in ONE host call (five launches: scale, Rq -> G, Rq' -> G'): behind the step's one host
 // sync the GPU is empty, and five Python-level launches of 5-20 us kernels starve it (measured: +0.08-0.14 ms per step against
 // the same kernels queued by a host that runs ahead).
-extern "C" int snvc_sheared_upsample_split(const float *, void *, void *, const float *, int64_t, int64_t, int64_t, int64_t, int, int64_t, int, void *);
-static int sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
-                           const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
-                           void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, void *stream, float *gi, int64_t pitch,
-                           int64_t lp);
-
-int snvc_sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
-                         const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
-                         void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, void *stream) {
-    return sheared_prep_x3(right, N, C, H, W, q, WU, off, WU2, off2, packed_g, packed_col, Cout3, out_mul_g, out_mul_col, rq_split, rq2_split,
-                           scratch8, mul_dev, g, gcol, stream, nullptr, 0, 0);
-}
-
-int snvc_fused_sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2,
-                               int off2, const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col,
-                               void *rq_split, void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, float *gi,
-                               int64_t pitch, int64_t lp, void *stream) {
-    if (!gi || Cout3 != 3 * C) return snvc::fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_sheared_prep_x3: gi is NULL or Cout3 != 3 * C");
-    return sheared_prep_x3(right, N, C, H, W, q, WU, off, WU2, off2, packed_g, packed_col, Cout3, out_mul_g, out_mul_col, rq_split, rq2_split,
-                           scratch8, mul_dev, g, gcol, stream, gi, pitch, lp);
-}
-
 static int sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
                            const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
                            void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, void *stream, float *gi, int64_t pitch,
@@ -2962,6 +2911,22 @@ static int sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, 
                                 stream, gi ? &il_col : nullptr);
 }
 
+int snvc_sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
+                         const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
+                         void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, void *stream) {
+    return sheared_prep_x3(right, N, C, H, W, q, WU, off, WU2, off2, packed_g, packed_col, Cout3, out_mul_g, out_mul_col, rq_split, rq2_split,
+                           scratch8, mul_dev, g, gcol, stream, nullptr, 0, 0);
+}
+
+int snvc_fused_sheared_prep_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2,
+                               int off2, const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col,
+                               void *rq_split, void *rq2_split, void *scratch8, float *mul_dev, float *g, float *gcol, float *gi,
+                               int64_t pitch, int64_t lp, void *stream) {
+    if (!gi || Cout3 != 3 * C) return snvc::fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_sheared_prep_x3: gi is NULL or Cout3 != 3 * C");
+    return sheared_prep_x3(right, N, C, H, W, q, WU, off, WU2, off2, packed_g, packed_col, Cout3, out_mul_g, out_mul_col, rq_split, rq2_split,
+                           scratch8, mul_dev, g, gcol, stream, gi, pitch, lp);
+}
+
 int snvc_fused_abi_version(void) { return 1; }
 
 int64_t snvc_fused_il_index(int mode, int64_t oc, int64_t C, int64_t H, int64_t pitch, int64_t lp, int64_t cls0, int64_t h, int64_t x) {
@@ -2970,7 +2935,6 @@ int64_t snvc_fused_il_index(int mode, int64_t oc, int64_t C, int64_t H, int64_t 
     return snvc::il_index<int64_t>(mode, oc, C, H, pitch, lp, cls0, h, x);
 }
 
-extern "C" int snvc_f16x3_from_ncdhw(const float *, void *, void *, int64_t, int64_t, int64_t, int64_t, int64_t, float, const float *, void *);
 int snvc_fused_planes_from_f32(const float *x, int64_t N, int64_t C, int64_t H, int64_t W, const void *packed, int64_t cout, float out_mul,
                                float *y, float *p_il, void *ws_split, void *scratch8, float *mul_dev, void *stream) {
     using namespace snvc;
@@ -2989,7 +2953,6 @@ int snvc_fused_planes_from_f32(const float *x, int64_t N, int64_t C, int64_t H, 
 // n_layers depth-1 split layers of ONE fp32 [N][C][H][W] input in one host call: its scale, its split pair (ws: N*2*C*H*W halves), then
 // the layers (same kernel size, their own packed weights / output channels / results).  The left half's depth-class planes (one
 // 3x3 layer) and the any-shift path's P / Q layers (two 3x3 layers of the right feature) go through here.
-extern "C" int snvc_f16x3_from_ncdhw(const float *, void *, void *, int64_t, int64_t, int64_t, int64_t, int64_t, float, const float *, void *);
 int snvc_f16x3_conv2d_from_f32(const float *x, int64_t N, int64_t C, int64_t H, int64_t W, int kh, int kw, int n_layers,
                                const void *const *packed, const int64_t *cout, const float *out_mul, float *const *y, void *ws_split,
                                void *scratch8, float *mul_dev, void *stream) {
@@ -3027,8 +2990,10 @@ int snvc_f16x3_deconv3d_tail_forward(const snvc_conv3d_desc *d, const void *x_hi
                                      const void *tail_packed, float *t_out, float tail_mul, int *overflow, void *stream) {
     using namespace snvc;
     if (!tail_packed || !t_out) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_deconv3d_tail_forward: null pointer");
-    return f16x3_forward(d, x_hi, x_lo, packed_weight, scale, bias, res_hi, res_lo, nullptr, nullptr, nullptr, nullptr, nullptr, 1.0f, res_mul,
-                         overflow, tail_packed, t_out, tail_mul, stream);
+    F16x3Call c;
+    c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias; c.res_hi = res_hi; c.res_lo = res_lo;
+    c.head_mul = 1.0f; c.res_mul = res_mul; c.overflow = overflow; c.tail_w = tail_packed; c.t_out = t_out; c.tail_mul = tail_mul; c.stream = stream;
+    return f16x3_forward(d, c);
 }
 
 int snvc_deconv_tail_gather(const float *t, const float *bias, const float *residual, float *y, int64_t n, int64_t nd, int64_t nh,

@@ -66,6 +66,23 @@ def test_argument_validation_needs_no_gpu(L):
     assert L.snvc_conv3d_packed_weight_count(ctypes.byref(d)) == -1 and "transposed" in err()
 
 
+def test_f16_forward_entry_points_refuse_null_arguments_as_recorded(L):
+    """A null descriptor, null pointers and an empty batch on the five split entry points and on snvc_f16_conv3d_forward: the status
+    and text recorded in tests/golden/f16_plan_table.json (tests/golden/make_golden_f16_plan.py), before anything is launched."""
+    import json
+
+    import f16_plan_cases as C
+    from snvc_amd import _fused
+    with open(os.path.join(ROOT, "tests", "golden", "f16_plan_table.json")) as f:
+        want = json.load(f)["null_calls"]
+    got = C.null_calls(L, _fused.lib())
+    assert len(got) == 24 and {g[0] for g in got} == {
+        "snvc_f16_conv3d_forward", "snvc_f16x3_conv3d_forward", "snvc_f16x3_conv3d_forward_f32", "snvc_f16x3_conv3d_forward_stats",
+        "snvc_f16x3_deconv3d_tail_forward", "snvc_fused_first_conv3d_forward"}
+    assert got == want
+    assert all(g[2] != 0 and g[3] for g in got if g[1] != "empty batch")
+
+
 def test_no_cpu_fallback():
     from snvc_amd import ops
     from snvc_amd.extension.build_cost_volume import build_cost_volume
