@@ -1,0 +1,86 @@
+"""ctypes binding of the kernel-form queries of ``libsnvc_hip.so`` (``include/snvc_forms.h``): which form the cost-volume and
+gather launchers take for a shape.  Host code only -- nothing is launched and no device is needed.
+
+Kept apart from ``_lib.SIGNATURES`` (the table of ``include/snvc_hip.h``): this header versions itself through
+``snvc_forms_abi_version()``.  The symbols are resolved on ``_lib.lib()``'s handle at first use, so importing this module
+loads nothing.
+"""
+import ctypes
+import re
+from typing import Tuple
+
+from . import _lib
+
+_ABI = 1   # snvc_forms_abi_version() this binding was written against
+
+c_i64 = ctypes.c_int64
+c_p = ctypes.c_void_p
+c_int = ctypes.c_int
+c_f = ctypes.c_float
+
+INFO = 8                                   # SNVC_FORMS_INFO
+ALIGNED_IN, ALIGNED_OUT, ALIGNED_ALL = 1, 2, 3
+GATHER_F32, GATHER_C8, GATHER_SPLIT = 0, 1, 2
+
+# name -> (restype, argtypes); kept next to the header so the symbol test can walk it
+SIGNATURES = {
+    "snvc_forms_abi_version": (c_int, []),
+    "snvc_cost_volume_forward_form": (c_int, [c_i64] * 6 + [c_int, c_int, c_int, c_p]),
+    "snvc_cost_volume_backward_form": (c_int, [c_i64] * 6 + [c_int, c_int, c_p]),
+    "snvc_voxel_gather_forward_form": (c_int, [c_int] + [c_i64] * 5 + [c_f, c_f, c_int, c_p]),
+    "snvc_voxel_gather_backward_form": (c_int, [c_i64] * 5 + [c_int, c_p]),
+}
+
+# info slot names per query (the header's comments)
+CV_FWD_INFO = ("RB", "hblocks", "dsplit", "dchunk", "grid_x", "grid_y", "threads", "lds")
+CV_BWD_INFO = ("", "", "", "", "grid_x", "", "threads", "")
+GATHER_FWD_INFO = ("run", "nruns", "pow2", "slices", "grid_x", "grid_yz", "threads", "lds")
+GATHER_BWD_INFO = ("vchunk", "nvchunks", "passes", "max_pieces", "grid_x", "grid_y", "threads", "lds")
+
+_bound = None
+
+
+def lib() -> ctypes.CDLL:
+    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
+    global _bound
+    if _bound is None:
+        handle = _lib.lib()
+        for name, (res, args) in SIGNATURES.items():
+            fn = getattr(handle, name)  # AttributeError if the .so is stale
+            fn.restype = res
+            fn.argtypes = args
+        if handle.snvc_forms_abi_version() != _ABI:
+            raise RuntimeError("libsnvc_hip.so form-query ABI version mismatch; rebuild it")
+        _bound = handle
+    return _bound
+
+
+def enum_names(header_text: str, prefix: str) -> dict:
+    """{name without the prefix: value} of the ``SNVC_<prefix>_<NAME> = <int>`` enumerators of include/snvc_forms.h."""
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"\bSNVC_%s_(\w+)\s*=\s*(\d+)" % prefix, header_text)}
+
+
+def _query(fn, names, *args) -> Tuple[int, dict, str]:
+    info = (c_i64 * INFO)()
+    rc = fn(*args, ctypes.cast(info, c_p))
+    text = _lib.lib().snvc_last_error_string().decode("utf-8", "replace") if rc < 0 else ""
+    return rc, {n: int(v) for n, v in zip(names, info) if n}, text
+
+
+def cost_volume_forward(n, c, hi, wi, d, downsample, dtype, right_only=False, aligned=ALIGNED_ALL):
+    """(form id, or 0 for no launch, or -status; info; error text) of snvc_cost_volume_forward[_right] for these sizes."""
+    return _query(lib().snvc_cost_volume_forward_form, CV_FWD_INFO, n, c, hi, wi, d, downsample, dtype, int(right_only), aligned)
+
+
+def cost_volume_backward(n, c, h, w, d, downsample, dtype, right_only=False):
+    return _query(lib().snvc_cost_volume_backward_form, CV_BWD_INFO, n, c, h, w, d, downsample, dtype, int(right_only))
+
+
+def voxel_gather_forward(kind, n, f, hf, wf, v, resolution, aligned=ALIGNED_ALL):
+    """``resolution`` as the ops take it: (rows, columns) of the crop."""
+    return _query(lib().snvc_voxel_gather_forward_form, GATHER_FWD_INFO, kind, n, f, hf, wf, v, float(resolution[1]), float(resolution[0]),
+                  aligned)
+
+
+def voxel_gather_backward(n, f, hf, wf, v, deterministic=True):
+    return _query(lib().snvc_voxel_gather_backward_form, GATHER_BWD_INFO, n, f, hf, wf, v, int(deterministic))

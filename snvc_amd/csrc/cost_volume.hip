@@ -13,6 +13,7 @@
 // Every product / sum is rounded on its own (fp contract off), in the order the reference
 // writes them, which makes the results bit-identical to oracle/cost_volume_ref.c.
 #include "common.hpp"
+#include "snvc_forms.h"
 
 namespace snvc {
 namespace {
@@ -410,20 +411,29 @@ depth_class_sums_kernel(const float *__restrict__ g, float *__restrict__ out, in
     op[2 * HW4] = gp[(int64_t)(D - 1) * HW4];
 }
 
-template <typename T>
-int launch_forward(const void *left, const void *right, const void *shift, void *out, int64_t N,
-                   int64_t C, int64_t Hi, int64_t Wi, int64_t D, int64_t ds, hipStream_t st) {
+// What the forward launcher does with a shape, decided from what the host can see: sizes, element size, which entry point, and
+// whether left / right / out are 16-byte aligned.  launch_forward launches exactly this; snvc_cost_volume_forward_form
+// (include/snvc_forms.h) exports it, so a test can ask which kernel its shape reaches.
+struct FwdPlan {
+    int form = 0;                 // snvc_cost_volume_forward_form_id; 0 = nothing to launch
+    int RB = 0, hblocks = 0, dsplit = 0, dchunk = 0, threads = 0;
+    int64_t gx = 0, gy = 0, lds = 0;
+};
+
+int plan_forward(size_t elem, bool right_only, bool aligned16, int64_t N, int64_t C, int64_t Hi, int64_t Wi, int64_t D, int64_t ds,
+                 FwdPlan &p) {
+    p = FwdPlan();
     const int64_t H = Hi / ds, W = Wi / ds;
     const int64_t planes = N * 2 * C * D;
     if (planes == 0 || H * W == 0) return SNVC_OK;  // BuildCostVolume_cuda.cu:235-238
-    const unsigned gy = (unsigned)(planes < 65535 ? planes : 65535);
-    const bool fast = sizeof(T) == 4 && ds == 1 && (W % 4) == 0 &&
-                      ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right) |
-                        reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    if (!left && !(fast && W / 4 <= 512 && N * C * H < ((int64_t)1 << 30)))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward_right: needs fp32, downsample 1, W % 4 == 0, W <= 2048");
+    const bool fast = elem == 4 && ds == 1 && (W % 4) == 0 && aligned16;
     const int64_t W4 = W / 4;
-    if (fast && W4 <= 512 && N * C * H < ((int64_t)1 << 30)) {
+    const bool rows = fast && W4 <= 512 && N * C * H < ((int64_t)1 << 30);
+    if (right_only && !rows)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward_right: needs fp32, downsample 1, W % 4 == 0, W <= 2048");
+    p.threads = 256;
+    p.gy = planes < 65535 ? planes : 65535;
+    if (rows) {
         // rows per workgroup: prefer RB*W*4 bytes to be a multiple of 128 (every workgroup then writes
         // whole cache lines per plane), with RB*W/4 threads <= 512
         int RB = 0;
@@ -435,34 +445,56 @@ int launch_forward(const void *left, const void *right, const void *shift, void 
             if (RB < 1) RB = 1;
         }
         if (RB > H) RB = (int)H;
-        const int threads = (int)ceil_div<int64_t>(RB * W4, 64) * 64;
-        const int hblocks = (int)ceil_div<int64_t>(H, RB);
+        p.RB = RB;
+        p.threads = (int)ceil_div<int64_t>(RB * W4, 64) * 64;
+        p.hblocks = (int)ceil_div<int64_t>(H, RB);
         // enough workgroups to fill the chip without shortening the per-thread plane walk too much
         int dsplit = 1;
-        while (N * C * hblocks * dsplit < 2048 && D / (dsplit * 2) >= 8) dsplit *= 2;
-        const int dchunk = (int)ceil_div<int64_t>(D, dsplit);
-        dim3 grid((unsigned)(N * C * hblocks), (unsigned)ceil_div<int64_t>(D, dchunk));
-        const size_t lds = (size_t)(RB + 1) * W * sizeof(float);
-        if (left)
-            cost_volume_fwd_rows<true><<<grid, threads, lds, st>>>((const float *)left, (const float *)right,
-                                                                   (const float *)shift, (float *)out, (int)C, (int)D,
-                                                                   (int)H, (int)W, RB, hblocks, dchunk);
-        else
-            cost_volume_fwd_rows<false><<<grid, threads, lds, st>>>(nullptr, (const float *)right, (const float *)shift,
-                                                                    (float *)out, (int)C, (int)D, (int)H, (int)W, RB,
-                                                                    hblocks, dchunk);
+        while (N * C * p.hblocks * dsplit < 2048 && D / (dsplit * 2) >= 8) dsplit *= 2;
+        p.dchunk = (int)ceil_div<int64_t>(D, dsplit);
+        p.gx = N * C * p.hblocks;
+        p.gy = ceil_div<int64_t>(D, p.dchunk);
+        p.dsplit = dsplit;
+        p.lds = (int64_t)(RB + 1) * W * (int64_t)sizeof(float);
+        p.form = right_only ? SNVC_CVF_ROWS_RIGHT : SNVC_CVF_ROWS;
     } else if (fast) {
-        dim3 grid((unsigned)ceil_div<int64_t>(H * W / 4, 256), gy);
+        p.gx = ceil_div<int64_t>(H * W / 4, 256);
+        p.form = SNVC_CVF_F32X4;
+    } else if (elem == 8 && ds == 1 && (W % 2) == 0 && aligned16) {
+        p.gx = ceil_div<int64_t>(H * W / 2, 256);
+        p.form = SNVC_CVF_F64X2;
+    } else {
+        p.gx = ceil_div<int64_t>(H * W, 256);
+        p.form = elem == 4 ? SNVC_CVF_GENERIC_F32 : SNVC_CVF_GENERIC_F64;
+    }
+    return SNVC_OK;
+}
+
+template <typename T>
+int launch_forward(const void *left, const void *right, const void *shift, void *out, int64_t N,
+                   int64_t C, int64_t Hi, int64_t Wi, int64_t D, int64_t ds, hipStream_t st) {
+    const int64_t H = Hi / ds, W = Wi / ds;
+    const int64_t planes = N * 2 * C * D;
+    FwdPlan p;
+    const int rc = plan_forward(sizeof(T), !left, aligned(16, left, right, out), N, C, Hi, Wi, D, ds, p);
+    if (rc || p.form == 0) return rc;
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gy);
+    if (p.form == SNVC_CVF_ROWS) {
+        cost_volume_fwd_rows<true><<<grid, p.threads, (size_t)p.lds, st>>>((const float *)left, (const float *)right,
+                                                                            (const float *)shift, (float *)out, (int)C, (int)D,
+                                                                            (int)H, (int)W, p.RB, p.hblocks, p.dchunk);
+    } else if (p.form == SNVC_CVF_ROWS_RIGHT) {
+        cost_volume_fwd_rows<false><<<grid, p.threads, (size_t)p.lds, st>>>(nullptr, (const float *)right, (const float *)shift,
+                                                                             (float *)out, (int)C, (int)D, (int)H, (int)W, p.RB,
+                                                                             p.hblocks, p.dchunk);
+    } else if (p.form == SNVC_CVF_F32X4) {
         cost_volume_fwd_f32x4<<<grid, 256, 0, st>>>((const float *)left, (const float *)right,
                                                     (const float *)shift, (float *)out, (int)C,
                                                     (int)D, (int)H, (int)W, planes);
-    } else if (sizeof(T) == 8 && ds == 1 && (W % 2) == 0 &&
-               ((reinterpret_cast<uintptr_t>(left) | reinterpret_cast<uintptr_t>(right) | reinterpret_cast<uintptr_t>(out)) & 15) == 0) {
-        dim3 grid((unsigned)ceil_div<int64_t>(H * W / 2, 256), gy);
+    } else if (p.form == SNVC_CVF_F64X2) {
         cost_volume_fwd_f64x2<<<grid, 256, 0, st>>>((const double *)left, (const double *)right, (const double *)shift, (double *)out,
                                                     (int)C, (int)D, (int)H, (int)W, planes);
     } else {
-        dim3 grid((unsigned)ceil_div<int64_t>(H * W, 256), gy);
         cost_volume_fwd_generic<T><<<grid, 256, 0, st>>>((const T *)left, (const T *)right,
                                                          (const T *)shift, (T *)out, (int)C, (int)D,
                                                          (int)H, (int)W, (int)ds, planes);
@@ -470,23 +502,77 @@ int launch_forward(const void *left, const void *right, const void *shift, void 
     return check_launch("snvc_cost_volume_forward");
 }
 
+// The backward's decision, as plan_forward: no form depends on alignment.  H, W: the volume's.
+struct BwdPlan {
+    int form = 0;                 // snvc_cost_volume_backward_form_id; 0 = nothing to launch
+    int64_t total = 0, blocks = 0;
+};
+
+int plan_backward(size_t elem, bool right_only, int64_t N, int64_t C, int64_t H, int64_t W, int64_t D, int64_t ds, BwdPlan &p) {
+    p = BwdPlan();
+    p.total = N * C * H * ds * W * ds;
+    if (p.total == 0) return SNVC_OK;
+    p.blocks = ceil_div<int64_t>(p.total, 256);
+    if (right_only) {
+        if (W < 2 || H * W >= ((int64_t)1 << 31) || p.blocks >= ((int64_t)1 << 31))
+            return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward_right: needs 2 <= W and a plane below 2^31 elements");
+        p.form = SNVC_CVB_ROWS_RIGHT;
+    } else if (elem == 4 && ds == 1 && W >= 2 && p.blocks < ((int64_t)1 << 31)) {
+        p.form = SNVC_CVB_ROWS;
+    } else {
+        p.form = elem == 4 ? SNVC_CVB_GATHER_F32 : SNVC_CVB_GATHER_F64;
+    }
+    return SNVC_OK;
+}
+
 template <typename T>
 int launch_backward(const void *grad, const void *shift, void *gl, void *gr, int64_t N, int64_t C,
                     int64_t H, int64_t W, int64_t D, int64_t ds, hipStream_t st) {
-    const int64_t total = N * C * H * ds * W * ds;
-    if (total == 0) return SNVC_OK;
-    const int64_t blocks = ceil_div<int64_t>(total, 256);
+    BwdPlan p;
+    const int rc = plan_backward(sizeof(T), false, N, C, H, W, D, ds, p);
+    if (rc || p.form == 0) return rc;
     if constexpr (sizeof(T) == 4) {
-        if (ds == 1 && W >= 2 && blocks < ((int64_t)1 << 31)) {
-            cost_volume_bwd_rows_f32<true><<<dim3((unsigned)blocks), 256, 0, st>>>((const float *)grad, (const float *)shift, (float *)gl,
-                                                                          (float *)gr, (int)C, (int)D, (int)H, (int)W, total);
+        if (p.form == SNVC_CVB_ROWS) {
+            cost_volume_bwd_rows_f32<true><<<dim3((unsigned)p.blocks), 256, 0, st>>>((const float *)grad, (const float *)shift, (float *)gl,
+                                                                          (float *)gr, (int)C, (int)D, (int)H, (int)W, p.total);
             return check_launch("snvc_cost_volume_backward");
         }
     }
-    cost_volume_bwd_gather<T><<<dim3((unsigned)blocks), 256, 0, st>>>(
+    cost_volume_bwd_gather<T><<<dim3((unsigned)p.blocks), 256, 0, st>>>(
         (const T *)grad, (const T *)shift, (T *)gl, (T *)gr, (int)C, (int)D, (int)H, (int)W, (int)ds,
-        total);
+        p.total);
     return check_launch("snvc_cost_volume_backward");
+}
+
+// The size checks of the four entry points, in their order; the form queries run the same ones.
+int forward_size_checks(int64_t N, int64_t C, int64_t Hi, int64_t Wi, int64_t D, int64_t downsample) {
+    if (N < 0 || C < 0 || Hi < 0 || Wi < 0 || D < 0 || downsample < 1)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_forward: negative size or downsample < 1");
+    if (Hi % downsample || Wi % downsample)
+        return fail(SNVC_ERR_INVALID_ARGUMENT,
+                    "snvc_cost_volume_forward: H and W must be multiples of downsample");
+    if (Hi * Wi >= (int64_t)1 << 31)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward: feature plane exceeds 2^31 elements");
+    return SNVC_OK;
+}
+
+int forward_right_size_checks(int64_t N, int64_t C, int64_t Hi, int64_t Wi, int64_t D, int64_t downsample) {
+    if (N < 0 || C < 0 || Hi < 0 || Wi < 0 || D < 0 || downsample != 1)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward_right: downsample must be 1 and sizes non-negative");
+    return SNVC_OK;
+}
+
+int backward_size_checks(int64_t N, int64_t C, int64_t H, int64_t W, int64_t D, int64_t downsample) {
+    if (N < 0 || C < 0 || H < 0 || W < 0 || D < 0 || downsample < 1)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_backward: negative size or downsample < 1");
+    if (H * downsample * W * downsample >= (int64_t)1 << 31)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward: feature plane exceeds 2^31 elements");
+    return SNVC_OK;
+}
+
+int backward_right_size_checks(int64_t N, int64_t C, int64_t H, int64_t W, int64_t D) {
+    if (N < 0 || C < 0 || H < 0 || W < 0 || D < 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_backward_right: negative size");
+    return SNVC_OK;
 }
 
 }  // namespace
@@ -498,13 +584,7 @@ int snvc_cost_volume_forward(const void *left, const void *right, const void *sh
                              int64_t N, int64_t C, int64_t Hi, int64_t Wi, int64_t D,
                              int64_t downsample, int dtype, void *stream) {
     using namespace snvc;
-    if (N < 0 || C < 0 || Hi < 0 || Wi < 0 || D < 0 || downsample < 1)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_forward: negative size or downsample < 1");
-    if (Hi % downsample || Wi % downsample)
-        return fail(SNVC_ERR_INVALID_ARGUMENT,
-                    "snvc_cost_volume_forward: H and W must be multiples of downsample");
-    if (Hi * Wi >= (int64_t)1 << 31)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward: feature plane exceeds 2^31 elements");
+    if (const int rc = forward_size_checks(N, C, Hi, Wi, D, downsample)) return rc;
     if (N * 2 * C * D * (Hi / downsample) * (Wi / downsample) > 0 && (!left || !right || !shift || !out))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_forward: null pointer");
     if (dtype == SNVC_F32)
@@ -517,8 +597,7 @@ int snvc_cost_volume_forward(const void *left, const void *right, const void *sh
 int snvc_cost_volume_forward_right(const float *right, const float *shift, float *out, int64_t N, int64_t C,
                                    int64_t Hi, int64_t Wi, int64_t D, int64_t downsample, void *stream) {
     using namespace snvc;
-    if (N < 0 || C < 0 || Hi < 0 || Wi < 0 || D < 0 || downsample != 1)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward_right: downsample must be 1 and sizes non-negative");
+    if (const int rc = forward_right_size_checks(N, C, Hi, Wi, D, downsample)) return rc;
     if (N * C * D * Hi * Wi == 0) return SNVC_OK;
     if (!right || !shift || !out) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_forward_right: null pointer");
     return launch_forward<float>(nullptr, right, shift, out, N, C, Hi, Wi, D, 1, as_stream(stream));
@@ -527,15 +606,14 @@ int snvc_cost_volume_forward_right(const float *right, const float *shift, float
 int snvc_cost_volume_backward_right(const float *grad_right_half, const float *shift, float *grad_right, int64_t N, int64_t C,
                                     int64_t H, int64_t W, int64_t D, void *stream) {
     using namespace snvc;
-    if (N < 0 || C < 0 || H < 0 || W < 0 || D < 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_backward_right: negative size");
-    const int64_t total = N * C * H * W;
-    if (total == 0) return SNVC_OK;
-    if (W < 2 || H * W >= ((int64_t)1 << 31) || ceil_div<int64_t>(total, 256) >= ((int64_t)1 << 31))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward_right: needs 2 <= W and a plane below 2^31 elements");
+    if (const int rc = backward_right_size_checks(N, C, H, W, D)) return rc;
+    BwdPlan p;
+    const int rc = plan_backward(sizeof(float), true, N, C, H, W, D, 1, p);
+    if (rc || p.form == 0) return rc;
     if (!grad_right || (D > 0 && (!grad_right_half || !shift)))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_backward_right: null pointer");
-    cost_volume_bwd_rows_f32<false><<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, as_stream(stream)>>>(
-        grad_right_half, shift, nullptr, grad_right, (int)C, (int)D, (int)H, (int)W, total);
+    cost_volume_bwd_rows_f32<false><<<dim3((unsigned)p.blocks), 256, 0, as_stream(stream)>>>(
+        grad_right_half, shift, nullptr, grad_right, (int)C, (int)D, (int)H, (int)W, p.total);
     return check_launch("snvc_cost_volume_backward_right");
 }
 
@@ -555,10 +633,7 @@ int snvc_cost_volume_backward(const void *grad, const void *shift, void *grad_le
                               int64_t N, int64_t C, int64_t H, int64_t W, int64_t D,
                               int64_t downsample, int dtype, void *stream) {
     using namespace snvc;
-    if (N < 0 || C < 0 || H < 0 || W < 0 || D < 0 || downsample < 1)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_backward: negative size or downsample < 1");
-    if (H * downsample * W * downsample >= (int64_t)1 << 31)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward: feature plane exceeds 2^31 elements");
+    if (const int rc = backward_size_checks(N, C, H, W, D, downsample)) return rc;
     if (N * C * H * W > 0 && (!grad_left || !grad_right || (D > 0 && (!grad || !shift))))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_backward: null pointer");
     if (dtype == SNVC_F32)
@@ -566,6 +641,47 @@ int snvc_cost_volume_backward(const void *grad, const void *shift, void *grad_le
     if (dtype == SNVC_F64)
         return launch_backward<double>(grad, shift, grad_left, grad_right, N, C, H, W, D, downsample, as_stream(stream));
     return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward: dtype must be f32 or f64");
+}
+
+int snvc_forms_abi_version(void) { return 1; }
+
+int snvc_cost_volume_forward_form(int64_t N, int64_t C, int64_t Hi, int64_t Wi, int64_t D, int64_t downsample, int dtype, int right_only,
+                                  int aligned, int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_forward_form: info is NULL");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    if (const int rc = right_only ? forward_right_size_checks(N, C, Hi, Wi, D, downsample) : forward_size_checks(N, C, Hi, Wi, D, downsample))
+        return -rc;
+    if (right_only && N * C * D * Hi * Wi == 0) return 0;
+    if (right_only && dtype != SNVC_F32)
+        return -fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward_right: fp32 only");
+    if (dtype != SNVC_F32 && dtype != SNVC_F64)
+        return -fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_forward: dtype must be f32 or f64 (AT_DISPATCH_FLOATING_TYPES)");
+    FwdPlan p;
+    if (const int rc = plan_forward(dtype == SNVC_F32 ? 4 : 8, right_only != 0, (aligned & SNVC_FORMS_ALIGNED_ALL) == SNVC_FORMS_ALIGNED_ALL, N, C, Hi, Wi, D,
+                                    downsample, p))
+        return -rc;
+    if (p.form == 0) return 0;
+    const int64_t v[SNVC_FORMS_INFO] = {p.RB, p.hblocks, p.dsplit, p.dchunk, p.gx, p.gy, p.threads, p.lds};
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = v[i];
+    return p.form;
+}
+
+int snvc_cost_volume_backward_form(int64_t N, int64_t C, int64_t H, int64_t W, int64_t D, int64_t downsample, int dtype, int right_only,
+                                   int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_cost_volume_backward_form: info is NULL");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    if (right_only && (downsample != 1 || dtype != SNVC_F32))
+        return -fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward_right: fp32 and downsample 1 only");
+    if (const int rc = right_only ? backward_right_size_checks(N, C, H, W, D) : backward_size_checks(N, C, H, W, D, downsample)) return -rc;
+    if (dtype != SNVC_F32 && dtype != SNVC_F64) return -fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward: dtype must be f32 or f64");
+    BwdPlan p;
+    if (const int rc = plan_backward(dtype == SNVC_F32 ? 4 : 8, right_only != 0, N, C, H, W, D, downsample, p)) return -rc;
+    if (p.form == 0) return 0;
+    info[4] = p.blocks;
+    info[6] = 256;
+    return p.form;
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 // sw = n*e, se = n*w, out-of-range taps contribute 0 -- with every operation rounded on its
 // own (fp contract off), so it is bit-identical to oracle/numpy_ref.py:sample_2d_feat.
 #include "common.hpp"
+#include "snvc_forms.h"
 
 #include <cmath>
 
@@ -361,31 +362,122 @@ inline bool pow2_res(float x, float &inv) {
     return true;
 }
 
-template <int CS, int OUT, int BS>
-int launch_gather_lds(const float *ws, const float *l_pts, const float *r_pts, void *out, int64_t N, int64_t F, int64_t Hf,
-                      int64_t Wf, int64_t V, int64_t run, float res_x, float res_y, hipStream_t st, const float *mul_dev = nullptr,
-                      int64_t lo_off = 0, int64_t out_bs = -1) {
-    if (out_bs < 0) out_bs = 2 * F * V;        // dense C8: [N][2F/8][V][8] halves (unused by the fp32 form)
-    const int plane = (int)(Hf * Wf);
-    const size_t lds = (size_t)plane * CS * 4 + (CS / 4) * 16;     // the slice + the zero slot
-    const int nruns = (int)ceil_div<int64_t>(V, run);
-    const dim3 grid((unsigned)(8 * ceil_div(nruns, 8) * (int)(F / CS)), 1, (unsigned)N);
-    float ix = 0.0f, iy = 0.0f;
-    if (pow2_res(res_x, ix) && pow2_res(res_y, iy))
-        launch_lds<voxel_gather_fwd_lds<CS, OUT, BS, true>>(grid, BS, lds, st, ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V, run, nruns,
-                                                            ix, iy, mul_dev, lo_off, out_bs);
-    else
-        launch_lds<voxel_gather_fwd_lds<CS, OUT, BS, false>>(grid, BS, lds, st, ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V, run, nruns,
-                                                             res_x, res_y, mul_dev, lo_off, out_bs);
-    return 0;
-}
-
 // voxels per workgroup: enough workgroups to fill the chip twice over, runs as long as that allows (the refill of the
 // slice is amortised over the run), whole 4096-voxel steps
 inline int64_t gather_run_length(int64_t V, int64_t slices, int64_t N) {
     const int64_t want = ceil_div<int64_t>(4 * (int64_t)device_cu_count(), slices * N);     // workgroups along the voxel axis
     int64_t run = ceil_div<int64_t>(ceil_div<int64_t>(V, want), 4096) * 4096;
     return run < 4096 ? 4096 : run;
+}
+
+// What a forward entry point does with a shape, decided from what the host can see (sizes, crop resolution, alignment, CU count):
+// the entry points launch exactly this, and snvc_voxel_gather_forward_form (include/snvc_forms.h) exports it.
+struct GatherPlan {
+    int form = 0;                 // snvc_voxel_gather_forward_form_id; 0 = nothing to launch
+    int64_t run = 0, nruns = 0, slices = 0, gx = 0, gyz = 0, threads = 0, lds = 0;
+    bool pow2 = false;
+    float rx = 0.0f, ry = 0.0f;   // what the LDS kernel gets as (res_x, res_y): the reciprocals when pow2
+};
+
+// the LDS-staged forms: CS channels per slice, BS threads
+void plan_lds(GatherPlan &p, int form, int CS, int BS, int64_t N, int64_t F, int64_t plane, int64_t V, float res_x, float res_y) {
+    p.form = form;
+    p.slices = F / CS;
+    p.run = gather_run_length(V, p.slices, N);
+    p.nruns = ceil_div<int64_t>(V, p.run);
+    p.gx = 8 * ceil_div<int64_t>(p.nruns, 8) * p.slices;
+    p.gyz = N;
+    p.threads = BS;
+    p.lds = plane * CS * 4 + (CS / 4) * 16;     // the slice + the zero slot
+    float ix = 0.0f, iy = 0.0f;
+    p.pow2 = pow2_res(res_x, ix) && pow2_res(res_y, iy);
+    p.rx = p.pow2 ? ix : res_x;
+    p.ry = p.pow2 ? iy : res_y;
+}
+
+int plan_plain(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, GatherPlan &p) {
+    p = GatherPlan();
+    if (N < 0 || F < 0 || Hf < 0 || Wf < 0 || V < 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward: negative size");
+    if (N == 0 || F == 0 || V == 0) return SNVC_OK;
+    if (Hf * Wf >= (int64_t)1 << 30 || N > 65535)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_forward: feature plane or batch too large");
+    p.form = SNVC_GF_PLAIN;
+    p.gx = ceil_div<int64_t>(V, 256);
+    p.gyz = N;
+    p.threads = 256;
+    return SNVC_OK;
+}
+
+// fp32 output (snvc_voxel_gather_forward_ws).  ws_ok: there is a workspace and it is 16-byte aligned; io16: both coordinate
+// arrays and the output are.
+int plan_f32(bool ws_ok, bool io16, int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, float res_x, float res_y, GatherPlan &p) {
+    const bool cl_ok = ws_ok && F > 0 && F % 4 == 0 && F <= 256 && N > 0 && V > 0 && N <= 65535 && Hf * Wf < ((int64_t)1 << 24);
+    if (!cl_ok) return plan_plain(N, F, Hf, Wf, V, p);
+    p = GatherPlan();
+    const int64_t plane = Hf * Wf;
+    const bool x4 = V % 4 == 0 && io16;
+    if (x4 && plane * 16 <= 72 * 1024 && V >= 4096) {     // LDS-staged 4-channel slices (two workgroups per CU)
+        plan_lds(p, SNVC_GF_LDS, 4, 512, N, F, plane, V, res_x, res_y);
+    } else {
+        p.form = x4 ? SNVC_GF_CL_X4 : SNVC_GF_CL;
+        p.gx = ceil_div<int64_t>(x4 ? V / 4 : V, 256);
+        p.gyz = N;
+        p.threads = 256;
+    }
+    return SNVC_OK;
+}
+
+// The size checks of snvc_voxel_gather_forward_f16 / _split, in their order.  empty: the call returns SNVC_OK without a launch.
+int c8_size_checks(bool split, int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, bool &empty) {
+    empty = false;
+    if (N < 0 || F <= 0 || F % 8 != 0 || F > 256 || Hf <= 0 || Wf <= 0 || V < 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, split ? "snvc_voxel_gather_forward_split: bad sizes (F % 8 == 0, F <= 256)"
+                                                     : "snvc_voxel_gather_forward_f16: bad sizes (F % 8 == 0, F <= 256)");
+    empty = N == 0 || V == 0;
+    if (!empty && (N > 65535 || Hf * Wf >= ((int64_t)1 << 24)))
+        return fail(SNVC_ERR_UNSUPPORTED, split ? "snvc_voxel_gather_forward_split: feature plane or batch too large"
+                                                : "snvc_voxel_gather_forward_f16: feature plane or batch too large");
+    return SNVC_OK;
+}
+
+// C8 half output (snvc_voxel_gather_forward_f16) or a split C8 pair (snvc_voxel_gather_forward_split).  out16: the workspace and
+// the output(s) are 16-byte aligned.
+int plan_c8(bool split, bool out16, int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, float res_x, float res_y, GatherPlan &p) {
+    p = GatherPlan();
+    bool empty = false;
+    if (const int rc = c8_size_checks(split, N, F, Hf, Wf, V, empty)) return rc;
+    if (empty) return SNVC_OK;
+    if (!out16)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, split ? "snvc_voxel_gather_forward_split: workspace and outputs must be 16-byte aligned"
+                                                     : "snvc_voxel_gather_forward_f16: workspace and output must be 16-byte aligned");
+    const int64_t plane = Hf * Wf;
+    if (plane * 32 <= 144 * 1024 && V >= 4096) {      // LDS-staged 8-channel groups (one workgroup per CU)
+        plan_lds(p, split ? SNVC_GF_LDS_SPLIT : SNVC_GF_LDS_C8, 8, 1024, N, F, plane, V, res_x, res_y);
+    } else if (split) {
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_forward_split: needs the LDS-staged form (Hf * Wf <= 4608, V >= 4096)");
+    } else {
+        p.form = SNVC_GF_CL_C8;
+        p.gx = ceil_div<int64_t>(V, 256);
+        p.gyz = N;
+        p.threads = 256;
+    }
+    return SNVC_OK;
+}
+
+template <int CS, int OUT, int BS>
+int launch_gather_lds(const GatherPlan &p, const float *ws, const float *l_pts, const float *r_pts, void *out, int64_t N, int64_t F,
+                      int64_t Hf, int64_t Wf, int64_t V, hipStream_t st, const float *mul_dev = nullptr, int64_t lo_off = 0,
+                      int64_t out_bs = -1) {
+    if (out_bs < 0) out_bs = 2 * F * V;        // dense C8: [N][2F/8][V][8] halves (unused by the fp32 form)
+    const dim3 grid((unsigned)p.gx, 1, (unsigned)N);
+    if (p.pow2)
+        launch_lds<voxel_gather_fwd_lds<CS, OUT, BS, true>>(grid, BS, (size_t)p.lds, st, ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V,
+                                                            p.run, (int)p.nruns, p.rx, p.ry, mul_dev, lo_off, out_bs);
+    else
+        launch_lds<voxel_gather_fwd_lds<CS, OUT, BS, false>>(grid, BS, (size_t)p.lds, st, ws, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V,
+                                                             p.run, (int)p.nruns, p.rx, p.ry, mul_dev, lo_off, out_bs);
+    return 0;
 }
 
 // aggregate="concat-atten" (snvc/models/vernier.py:341-344): the concatenated voxel features are multiplied by
@@ -524,6 +616,34 @@ voxel_gather_bwd_lds(const float *__restrict__ grad_out, const float *__restrict
 }
 
 }  // namespace
+
+// What snvc_voxel_gather_backward (the float-atomics adjoint) does with a shape; snvc_voxel_gather_backward_form
+// (voxel_gather_bwd.hip) exports it next to the sorted form's.  form 0: nothing to launch beyond the zero fill.
+int plan_gather_backward_atomics(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, int &form, int64_t info[SNVC_FORMS_INFO]) {
+    form = 0;
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    if (N < 0 || F < 0 || Hf < 0 || Wf < 0 || V < 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_backward: negative size");
+    if (Hf * Wf >= (int64_t)1 << 30 || N > 65535)
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_backward: feature plane or batch too large");
+    if (N == 0 || F == 0 || V == 0) return SNVC_OK;
+    constexpr int CPB = 2;
+    info[6] = 256;
+    if ((int64_t)CPB * Hf * Wf * 4 <= 64 * 1024 && 2 * N <= 65535) {
+        // ~64k voxels per workgroup: the flush (<= CPB*Hf*Wf atomics) is amortised over >= 8x as many LDS adds
+        form = SNVC_GB_LDS_ATOMICS;
+        info[0] = V < 65536 ? V : 65536;
+        info[1] = info[4] = ceil_div<int64_t>(V, info[0]);
+        info[5] = ceil_div<int64_t>(F, CPB);
+        info[7] = (int64_t)CPB * Hf * Wf * 4;
+    } else {
+        form = SNVC_GB_GLOBAL_ATOMICS;
+        info[4] = ceil_div<int64_t>(V, 256);
+        info[5] = N;
+    }
+    return SNVC_OK;
+}
+
 }  // namespace snvc
 
 extern "C" {
@@ -532,14 +652,12 @@ int snvc_voxel_gather_forward(const float *left, const float *right, const float
                               const float *r_pts, float *out, int64_t N, int64_t F, int64_t Hf,
                               int64_t Wf, int64_t V, float res_x, float res_y, void *stream) {
     using namespace snvc;
-    if (N < 0 || F < 0 || Hf < 0 || Wf < 0 || V < 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward: negative size");
-    if (N == 0 || F == 0 || V == 0) return SNVC_OK;
-    if (Hf * Wf >= (int64_t)1 << 30 || N > 65535)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_forward: feature plane or batch too large");
+    GatherPlan p;
+    const int rc = plan_plain(N, F, Hf, Wf, V, p);
+    if (rc || p.form == 0) return rc;
     if (!left || !right || !l_pts || !r_pts || !out)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward: null pointer");
-    dim3 grid((unsigned)ceil_div<int64_t>(V, 256), (unsigned)N);
+    dim3 grid((unsigned)p.gx, (unsigned)p.gyz);
     voxel_gather_fwd<<<grid, 256, 0, as_stream(stream)>>>(left, right, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V,
                                                           res_x, res_y);
     return check_launch("snvc_voxel_gather_forward");
@@ -554,26 +672,23 @@ int snvc_voxel_gather_forward_ws(const float *left, const float *right, const fl
                                  float *out, float *workspace, int64_t N, int64_t F, int64_t Hf, int64_t Wf,
                                  int64_t V, float res_x, float res_y, void *stream) {
     using namespace snvc;
-    const bool cl_ok = workspace && F > 0 && F % 4 == 0 && F <= 256 && N > 0 && V > 0 && N <= 65535 &&
-                       Hf * Wf < ((int64_t)1 << 24) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
-    if (!cl_ok) return snvc_voxel_gather_forward(left, right, l_pts, r_pts, out, N, F, Hf, Wf, V, res_x, res_y, stream);
+    GatherPlan p;
+    const int rc = plan_f32(workspace && aligned(16, workspace), aligned(16, l_pts, r_pts, out), N, F, Hf, Wf, V, res_x, res_y, p);
+    if (rc || p.form == 0 || p.form == SNVC_GF_PLAIN)
+        return snvc_voxel_gather_forward(left, right, l_pts, r_pts, out, N, F, Hf, Wf, V, res_x, res_y, stream);
     if (!left || !right || !l_pts || !r_pts || !out)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_ws: null pointer");
     const int plane = (int)(Hf * Wf);
     dim3 tg((unsigned)ceil_div(plane, 64), (unsigned)N, 2);
     features_to_channels_last<<<tg, 256, (size_t)64 * (F + 1) * sizeof(float), as_stream(stream)>>>(left, right, workspace,
                                                                                                     (int)F, plane);
-    const bool x4 = V % 4 == 0 &&
-        ((reinterpret_cast<uintptr_t>(l_pts) | reinterpret_cast<uintptr_t>(r_pts) | reinterpret_cast<uintptr_t>(out)) & 15) == 0;
-    if (x4 && (int64_t)plane * 16 <= 72 * 1024 && V >= 4096) {     // LDS-staged 4-channel slices (two workgroups per CU)
-        const int64_t run = gather_run_length(V, F / 4, N);
-        launch_gather_lds<4, false, 512>(workspace, l_pts, r_pts, out, N, F, Hf, Wf, V, run, res_x, res_y, as_stream(stream));
-    } else if (x4) {
-        dim3 grid((unsigned)ceil_div<int64_t>(V / 4, 256), (unsigned)N);
+    const dim3 grid((unsigned)p.gx, (unsigned)p.gyz);
+    if (p.form == SNVC_GF_LDS) {
+        launch_gather_lds<4, false, 512>(p, workspace, l_pts, r_pts, out, N, F, Hf, Wf, V, as_stream(stream));
+    } else if (p.form == SNVC_GF_CL_X4) {
         voxel_gather_fwd_cl_x4<<<grid, 256, 0, as_stream(stream)>>>(workspace, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf,
                                                                     V, res_x, res_y);
     } else {
-        dim3 grid((unsigned)ceil_div<int64_t>(V, 256), (unsigned)N);
         voxel_gather_fwd_cl<<<grid, 256, 0, as_stream(stream)>>>(workspace, l_pts, r_pts, out, (int)F, (int)Hf, (int)Wf, V,
                                                                  res_x, res_y);
     }
@@ -584,24 +699,21 @@ int snvc_voxel_gather_forward_f16(const float *left, const float *right, const f
                                   void *out, float *workspace, int64_t N, int64_t F, int64_t Hf, int64_t Wf,
                                   int64_t V, float res_x, float res_y, void *stream) {
     using namespace snvc;
-    if (N < 0 || F <= 0 || F % 8 != 0 || F > 256 || Hf <= 0 || Wf <= 0 || V < 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_f16: bad sizes (F % 8 == 0, F <= 256)");
-    if (N == 0 || V == 0) return SNVC_OK;
-    if (N > 65535 || Hf * Wf >= ((int64_t)1 << 24))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_forward_f16: feature plane or batch too large");
+    bool empty = false;
+    if (const int rc = c8_size_checks(false, N, F, Hf, Wf, V, empty)) return rc;
+    if (empty) return SNVC_OK;
     if (!left || !right || !l_pts || !r_pts || !out || !workspace)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_f16: null pointer");
-    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(out)) & 15)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_f16: workspace and output must be 16-byte aligned");
+    GatherPlan p;
+    if (const int rc = plan_c8(false, aligned(16, workspace, out), N, F, Hf, Wf, V, res_x, res_y, p)) return rc;
     const int plane = (int)(Hf * Wf);
     dim3 tg((unsigned)ceil_div(plane, 64), (unsigned)N, 2);
     features_to_channels_last<<<tg, 256, (size_t)64 * (F + 1) * sizeof(float), as_stream(stream)>>>(left, right, workspace,
                                                                                                     (int)F, plane);
-    if ((int64_t)plane * 32 <= 144 * 1024 && V >= 4096) {      // LDS-staged 8-channel groups (one workgroup per CU)
-        const int64_t run = gather_run_length(V, F / 8, N);
-        launch_gather_lds<8, 1, 1024>(workspace, l_pts, r_pts, out, N, F, Hf, Wf, V, run, res_x, res_y, as_stream(stream));
+    if (p.form == SNVC_GF_LDS_C8) {
+        launch_gather_lds<8, 1, 1024>(p, workspace, l_pts, r_pts, out, N, F, Hf, Wf, V, as_stream(stream));
     } else {
-        dim3 grid((unsigned)ceil_div<int64_t>(V, 256), (unsigned)N);
+        dim3 grid((unsigned)p.gx, (unsigned)p.gyz);
         voxel_gather_fwd_cl_c8<<<grid, 256, 0, as_stream(stream)>>>(workspace, l_pts, r_pts, reinterpret_cast<_Float16 *>(out),
                                                                     (int)F, (int)Hf, (int)Wf, V, res_x, res_y);
     }
@@ -612,24 +724,19 @@ int snvc_voxel_gather_forward_split(const float *left, const float *right, const
                                     void *out_lo, const float *mul_dev, float *workspace, int64_t N, int64_t F, int64_t Hf, int64_t Wf,
                                     int64_t V, int64_t out_batch_stride, float res_x, float res_y, void *stream) {
     using namespace snvc;
-    if (N < 0 || F <= 0 || F % 8 != 0 || F > 256 || Hf <= 0 || Wf <= 0 || V < 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_split: bad sizes (F % 8 == 0, F <= 256)");
-    if (N == 0 || V == 0) return SNVC_OK;
-    if (N > 65535 || Hf * Wf >= ((int64_t)1 << 24))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_forward_split: feature plane or batch too large");
+    bool empty = false;
+    if (const int rc = c8_size_checks(true, N, F, Hf, Wf, V, empty)) return rc;
+    if (empty) return SNVC_OK;
     if (!left || !right || !l_pts || !r_pts || !out_hi || !out_lo || !mul_dev || !workspace)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_split: null pointer");
-    if ((reinterpret_cast<uintptr_t>(workspace) | reinterpret_cast<uintptr_t>(out_hi) | reinterpret_cast<uintptr_t>(out_lo)) & 15)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_split: workspace and outputs must be 16-byte aligned");
+    GatherPlan p;
+    if (const int rc = plan_c8(true, aligned(16, workspace, out_hi, out_lo), N, F, Hf, Wf, V, res_x, res_y, p)) return rc;
     const int plane = (int)(Hf * Wf);
-    if (!((int64_t)plane * 32 <= 144 * 1024 && V >= 4096))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_forward_split: needs the LDS-staged form (Hf * Wf <= 4608, V >= 4096)");
     dim3 tg((unsigned)ceil_div(plane, 64), (unsigned)N, 2);
     features_to_channels_last<<<tg, 256, (size_t)64 * (F + 1) * sizeof(float), as_stream(stream)>>>(left, right, workspace,
                                                                                                     (int)F, plane);
-    const int64_t run = gather_run_length(V, F / 8, N);
     const int64_t lo_off = static_cast<const _Float16 *>(out_lo) - static_cast<const _Float16 *>(out_hi);
-    launch_gather_lds<8, 2, 1024>(workspace, l_pts, r_pts, out_hi, N, F, Hf, Wf, V, run, res_x, res_y, as_stream(stream), mul_dev, lo_off,
+    launch_gather_lds<8, 2, 1024>(p, workspace, l_pts, r_pts, out_hi, N, F, Hf, Wf, V, as_stream(stream), mul_dev, lo_off,
                                   out_batch_stride ? out_batch_stride : 4 * F * V);
     return check_launch("snvc_voxel_gather_forward_split");
 }
@@ -648,10 +755,9 @@ int snvc_voxel_gather_backward(const float *grad_out, const float *l_pts, const 
                                float *grad_left, float *grad_right, int64_t N, int64_t F, int64_t Hf,
                                int64_t Wf, int64_t V, float res_x, float res_y, void *stream) {
     using namespace snvc;
-    if (N < 0 || F < 0 || Hf < 0 || Wf < 0 || V < 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_backward: negative size");
-    if (Hf * Wf >= (int64_t)1 << 30 || N > 65535)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_backward: feature plane or batch too large");
+    int form = 0;
+    int64_t info[SNVC_FORMS_INFO];
+    if (const int rc = plan_gather_backward_atomics(N, F, Hf, Wf, V, form, info)) return rc;
     const size_t bytes = sizeof(float) * (size_t)(N * F * Hf * Wf);
     if (bytes) {
         if (!grad_left || !grad_right)
@@ -660,21 +766,34 @@ int snvc_voxel_gather_backward(const float *grad_out, const float *l_pts, const 
             hipMemsetAsync(grad_right, 0, bytes, as_stream(stream)) != hipSuccess)
             return fail(SNVC_ERR_HIP, "snvc_voxel_gather_backward: hipMemsetAsync failed");
     }
-    if (N == 0 || F == 0 || V == 0) return SNVC_OK;
-    constexpr int CPB = 2;
-    if ((int64_t)CPB * Hf * Wf * 4 <= 64 * 1024 && 2 * N <= 65535) {
-        // ~64k voxels per workgroup: the flush (<= CPB*Hf*Wf atomics) is amortised over >= 8x as many LDS adds
-        int64_t vchunk = 65536;
-        if (vchunk > V) vchunk = V;
-        dim3 grid((unsigned)ceil_div<int64_t>(V, vchunk), (unsigned)ceil_div<int64_t>(F, CPB), (unsigned)(2 * N));
-        voxel_gather_bwd_lds<CPB><<<grid, 256, (size_t)CPB * Hf * Wf * 4, as_stream(stream)>>>(
-            grad_out, l_pts, r_pts, grad_left, grad_right, (int)F, (int)Hf, (int)Wf, V, vchunk, res_x, res_y);
+    if (form == 0) return SNVC_OK;
+    if (form == SNVC_GB_LDS_ATOMICS) {
+        dim3 grid((unsigned)info[4], (unsigned)info[5], (unsigned)(2 * N));
+        voxel_gather_bwd_lds<2><<<grid, 256, (size_t)info[7], as_stream(stream)>>>(
+            grad_out, l_pts, r_pts, grad_left, grad_right, (int)F, (int)Hf, (int)Wf, V, info[0], res_x, res_y);
     } else {
-        dim3 grid((unsigned)ceil_div<int64_t>(V, 256), (unsigned)N);
+        dim3 grid((unsigned)info[4], (unsigned)info[5]);
         voxel_gather_bwd<<<grid, 256, 0, as_stream(stream)>>>(grad_out, l_pts, r_pts, grad_left, grad_right,
                                                               (int)F, (int)Hf, (int)Wf, V, res_x, res_y);
     }
     return check_launch("snvc_voxel_gather_backward");
+}
+
+int snvc_voxel_gather_forward_form(int kind, int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, float res_x, float res_y, int aligned,
+                                   int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_form: info is NULL");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    const bool in16 = (aligned & SNVC_FORMS_ALIGNED_IN) != 0, out16 = (aligned & SNVC_FORMS_ALIGNED_OUT) != 0;
+    GatherPlan p;
+    int rc;
+    if (kind == SNVC_GATHER_F32) rc = plan_f32(out16, in16 && out16, N, F, Hf, Wf, V, res_x, res_y, p);
+    else if (kind == SNVC_GATHER_C8 || kind == SNVC_GATHER_SPLIT) rc = plan_c8(kind == SNVC_GATHER_SPLIT, out16, N, F, Hf, Wf, V, res_x, res_y, p);
+    else rc = fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_forward_form: kind must be SNVC_GATHER_F32, _C8 or _SPLIT");
+    if (rc) return -rc;
+    const int64_t v[SNVC_FORMS_INFO] = {p.run, p.nruns, p.pow2 ? 1 : 0, p.slices, p.gx, p.gyz, p.threads, p.lds};
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = v[i];
+    return p.form;
 }
 
 }  // extern "C"

@@ -15,8 +15,12 @@
 #include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "snvc_forms.h"
 
 namespace snvc {
+
+int plan_gather_backward_atomics(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, int &form, int64_t info[SNVC_FORMS_INFO]);   // voxel_gather.hip
+
 namespace {
 
 #pragma clang fp contract(off)
@@ -170,12 +174,36 @@ struct BwdLayout {
 
 inline int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
-int bwd_layout(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, BwdLayout &L) {
+// The sizes of the sorted form, and its refusal: pure arithmetic (snvc_voxel_gather_backward_form asks it without a device).
+int bwd_sizes(int64_t N, int64_t Hf, int64_t Wf, int64_t V, BwdLayout &L) {
     L.M = 2 * N * V;
     const int64_t K = (Hf + 1) * (Wf + 1);
     L.nkeys = 2 * N * (K + 1);
     if (L.nkeys >= ((int64_t)1 << 31) || V >= ((int64_t)1 << 32) || L.M >= ((int64_t)1 << 31))
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_backward_det: too many voxels or pixels for 32-bit keys");
+    L.max_pieces = L.M / kPiece + L.nkeys;          // sum of ceil(len / kPiece) <= M / kPiece + (number of keys)
+    return SNVC_OK;
+}
+
+// The size checks of snvc_voxel_gather_backward_det, in its order, and what the call then does: nothing (an empty gradient),
+// a zero fill only (no voxel), or the sort and its passes.
+enum DetWork { DET_NOTHING, DET_ZERO_FILL, DET_SORT };
+
+int det_size_checks(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, DetWork &work) {
+    work = DET_NOTHING;
+    if (N < 0 || F < 0 || Hf < 0 || Wf < 0 || V < 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_backward_det: negative size");
+    if (N * F * Hf * Wf == 0) return SNVC_OK;
+    work = DET_ZERO_FILL;
+    if (V == 0) return SNVC_OK;
+    if (2 * N > 65535 || Hf * Wf >= ((int64_t)1 << 24))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_backward_det: batch or feature plane too large");
+    work = DET_SORT;
+    return SNVC_OK;
+}
+
+int bwd_layout(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, BwdLayout &L) {
+    if (const int rc = bwd_sizes(N, Hf, Wf, V, L)) return rc;
     size_t tmp = 0;
     if (hipcub::DeviceRadixSort::SortPairs(nullptr, tmp, (const unsigned *)nullptr, (unsigned *)nullptr, (const unsigned *)nullptr,
                                            (unsigned *)nullptr, (int)L.M, 0, 32) != hipSuccess)
@@ -184,7 +212,6 @@ int bwd_layout(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, BwdLayou
     if (hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, (const unsigned *)nullptr, (unsigned *)nullptr, (int)(L.nkeys + 1)) != hipSuccess)
         return fail(SNVC_ERR_HIP, "snvc_voxel_gather_backward_det: hipcub temp-storage query failed");
     L.tmp_bytes = (int64_t)(tmp > tmp2 ? tmp : tmp2);
-    L.max_pieces = L.M / kPiece + L.nkeys;          // sum of ceil(len / kPiece) <= M / kPiece + (number of keys)
     int64_t o = 0;
     L.off_keys_in = o; o += align256(L.M * 4);
     L.off_keys_out = o; o += align256(L.M * 4);
@@ -216,13 +243,13 @@ int snvc_voxel_gather_backward_det(const float *grad_out, const float *l_pts, co
                                    float *grad_right, void *workspace, int64_t N, int64_t F, int64_t Hf, int64_t Wf,
                                    int64_t V, float res_x, float res_y, void *stream) {
     using namespace snvc;
-    if (N < 0 || F < 0 || Hf < 0 || Wf < 0 || V < 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_backward_det: negative size");
+    DetWork work;
+    if (const int rc = det_size_checks(N, F, Hf, Wf, V, work)) return rc;
+    if (work == DET_NOTHING) return SNVC_OK;
     hipStream_t st = as_stream(stream);
     const int64_t plane = Hf * Wf;
-    if (N * F * plane == 0) return SNVC_OK;
     if (!grad_left || !grad_right) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_backward_det: null pointer");
-    if (V == 0) {
+    if (work == DET_ZERO_FILL) {
         if (hipMemsetAsync(grad_left, 0, sizeof(float) * N * F * plane, st) != hipSuccess ||
             hipMemsetAsync(grad_right, 0, sizeof(float) * N * F * plane, st) != hipSuccess)
             return fail(SNVC_ERR_HIP, "snvc_voxel_gather_backward_det: hipMemsetAsync failed");
@@ -230,8 +257,6 @@ int snvc_voxel_gather_backward_det(const float *grad_out, const float *l_pts, co
     }
     if (!grad_out || !l_pts || !r_pts || !workspace || (reinterpret_cast<uintptr_t>(workspace) & 255))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_backward_det: null pointer or workspace not 256-byte aligned");
-    if (2 * N > 65535 || plane >= ((int64_t)1 << 24))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_voxel_gather_backward_det: batch or feature plane too large");
     BwdLayout L;
     int rc = bwd_layout(N, F, Hf, Wf, V, L);
     if (rc) return rc;
@@ -263,6 +288,27 @@ int snvc_voxel_gather_backward_det(const float *grad_out, const float *l_pts, co
     gather_bwd_combine_kernel<<<dim3((unsigned)ceil_div<int64_t>(F * plane, 256), (unsigned)G), 256, 0, st>>>(P, slot0, grad_left, grad_right,
                                                                                                               (int)N, (int)F, (int)Hf, (int)Wf);
     return check_launch("snvc_voxel_gather_backward_det");
+}
+
+int snvc_voxel_gather_backward_form(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, int deterministic, int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_voxel_gather_backward_form: info is NULL");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    if (!deterministic) {
+        int form = 0;
+        const int rc = plan_gather_backward_atomics(N, F, Hf, Wf, V, form, info);
+        return rc ? -rc : form;
+    }
+    DetWork work;
+    if (const int rc = det_size_checks(N, F, Hf, Wf, V, work)) return -rc;
+    if (work != DET_SORT) return 0;
+    BwdLayout L;
+    if (const int rc = bwd_sizes(N, Hf, Wf, V, L)) return -rc;
+    info[2] = ceil_div<int64_t>(F, 64);
+    info[3] = info[4] = L.max_pieces;
+    info[5] = 1;
+    info[6] = 256;
+    return SNVC_GB_SORTED;
 }
 
 }  // extern "C"

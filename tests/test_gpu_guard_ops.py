@@ -6,6 +6,9 @@ the tensor's own minimum, a value inside the valid range) and every allocation o
 
 Second placement: 4 bytes off 256; 8 or 16 where the entry point refuses less ("transposed y / residual must be 8-byte aligned",
 ``snvc_depth_class_sums``, ``snvc_deconv_tail_gather`` and ``snvc_fc_eval_forward`` ask for 16): the least alignment its contract allows.
+The rows of tests/geometry_cases.py (``forms_*``: one guarded run per launcher form of the cost volume and the gather, the test
+functions of tests/test_gpu_geometry_forms.py run unchanged) carry their own second placement -- 16 bytes for the vector and LDS forms,
+4 for the scalar ones -- because each asserts, through the form query, that it still takes the form it is there for.
 
 ``loose``: the results of the two float-atomics forms -- the call ``voxel_gather_backward(..., deterministic=False)`` and the RoI-aware
 pool's backward -- differ in bits from run to run and are compared with the unguarded run at the tolerance of the op's existing test
@@ -44,6 +47,7 @@ def _table():
     import decode_cases as DEC
     import depth_cases as DC
     import fcmodel_cases as FC
+    import geometry_cases as GEO
     import roi_crop_cases as RC
     import test_gpu_epilogue as E
     import test_gpu_hrnet as HR
@@ -65,6 +69,8 @@ def _table():
           ("gather_bwd_edges", P, "test_voxel_gather_backward_deterministic", dict(case="edges"), 4, GATHER_ATOMICS),
           ("gather_bwd_coherent", P, "test_voxel_gather_backward_deterministic", dict(case="coherent"), 4, GATHER_ATOMICS),
           ("gather_zero_points_and_empties", P, "test_empty_and_ragged_inputs", {}, 4, {})]
+    t += [(f"forms_{c.name}", "test_gpu_geometry_forms", GEO.TEST_OF_ENTRY[c.entry], dict(c=c), c.place,
+           GATHER_ATOMICS if c.entry == "gather_bwd" and not c.det else {}) for c in GEO.GUARDED]
     # -------------------------------------------------------------------------------------------------- elementwise, epilogue
     big = dict(arena_bytes=512 << 20)
     for s in list(E.TINY) + [E.GROUPS, E.VEC_TAIL, E.SCALAR_TAIL]:
