@@ -56,7 +56,7 @@ class LazyCostVolume(torch.Tensor):
         """The paused step ``build_cost_volume`` started for ``model`` (GlobalStack.lazy_prefetch), once: None if there is none, it
         belongs to another model or stream, or the model's first-layer weights changed since.  (Whether the prep buffers the paused
         step queued are still ITS OWN is the step's business: it re-checks the model's prep epoch when resumed and starts over if another
-        call used them in between -- GlobalStack._forward_pair_steps.)"""
+        call used them in between -- GlobalStack._factored_pair_steps.)"""
         pre, self._prefetch = self._prefetch, None
         if pre is None:
             return None

@@ -13,6 +13,7 @@ blocks (``convbn_3d``, ``hourglass``) and the composition pattern of VernierScal
     v = v + hourglass(v)[0]                                      hg_conv3d
     cost = conv1x1x1(v)           C  -> 1                        classifier
 """
+import dataclasses
 import itertools
 import warnings
 import weakref
@@ -28,7 +29,26 @@ from .submodule import (_ROUTES, SCRATCH_ATTRS, WORKSPACE_ATTRS, X3_GROUP_NORM, 
                         _is_channel_head as _is_head_conv, _Plan, convbn_3d, folded_head_weights, hourglass, overflow_guard, plan_for,
                         sheared_geometry, sheared_kernels, x3_exponent, x3_norm_bound, EPI_RELU, SHEAR_CLASS_KDS)
 
-_PREP_EPOCH = itertools.count(1)      # stamps of the per-model first-layer prep buffers (see _forward_pair_steps)
+_PREP_EPOCH = itertools.count(1)      # stamps of the per-model first-layer prep buffers (see _factored_pair_steps)
+_X3_KEY = {ops.Conv3dLayer: "", ops.Conv2dLayerX3: "_x3"}      # plan-dict key suffix of a depth-1 layer kind (GlobalStack._layers)
+_ASK = object()                       # _conv2_tail: the caller has not resolved the split-mode state
+
+
+@dataclasses.dataclass
+class _Prep:
+    """What the first layer's small 2D launches of ONE step share (GlobalStack._left_planes, _sheared_inputs, _commuted_inputs) and what
+    its expand pass needs of them."""
+    plans: dict                       # _factored_plans(conv1, c): the layers of every weight fold
+    c: int                            # feature channels: `weight` is conv1's [Cout, 2 c, 3, 3, 3], left half first
+    weight: torch.Tensor
+    st: dict = None                   # this step's split-mode state (_x3_select), None: fp32 arithmetic
+    scale: torch.Tensor = None        # the folded eval BatchNorm (None: a GroupNorm layer, statistics per call)
+    bias: torch.Tensor = None
+    split_prep: bool = False          # the 2D layers in split mode too, results in `prep_ws` (False: fp32 MFMA, results from the allocator)
+    fuse: bool = False                # ... and channel-interleaved copies (`p_il`, G | G') for conv2's fused first layer
+    prep_ws: dict = None
+    planes: torch.Tensor = None       # [N, c, 3, H, W], filled by _left_planes
+    p_il: torch.Tensor = None
 
 
 def _factored_plans(conv: nn.Module, c: int) -> dict:
@@ -88,15 +108,24 @@ class GlobalStack(SplitModePolicy, nn.Module):
             buf = ws[key] = torch.empty(shape, dtype=dtype, device=device)
         return buf
 
-    # the sheared first layer's two small 2D chains on side streams: built and measured in r5 (tools/ab_step.py, interleaved legs):
-    # 2.185 ms/step against 2.130 on one stream -- the cross-stream event waits cost more than the chains' overlap buys.  Off.
-    prep_streams = False
+    # The two first-layer buffers.  They are the only places that say where the call's first-layer result is (last_first_layer()).
+    def _v1(self, shape, device):
+        """The fp32 first-layer result [N,C,D,H,W]."""
+        self.__dict__["_snvc_last_v1"] = "v1"
+        return self._buffer("v1", shape, device)
 
-    def _side_streams(self, device):
-        st = self.__dict__.setdefault("_snvc_streams", {})
-        if device not in st:
-            st[device] = (torch.cuda.Stream(device), torch.cuda.Stream(device))
-        return st[device]
+    def _v1s(self, shape, device, last="v1s", lazy=None):
+        """The split pair [N,2,C/8,D,H,W,8] of a first-layer result of fp32 ``shape``.  ``last="v1"``: the pair is a layout pass over the
+        fp32 result, which is in the workspace too.  ``lazy`` (the fused route, which never stores the pair): nothing is handed out;
+        ``lazy(pair buffer)`` fills it if somebody asks for the result."""
+        def pair():
+            return self._buffer("v1s", (shape[0], 2, shape[1] // 8) + tuple(shape[2:]) + (8,), device, torch.float16)
+        if lazy is not None:
+            self.__dict__.setdefault("_snvc_ws", {})[("v1s_lazy", (), None)] = lambda: lazy(pair())
+            self.__dict__["_snvc_last_v1"] = "v1s_lazy"
+            return None
+        self.__dict__["_snvc_last_v1"] = last
+        return pair()
 
     def last_first_layer(self) -> torch.Tensor:
         """The first layer's result of the most recent inference call as a float32 [N,C,D,H,W] tensor (a copy when the call ran
@@ -106,8 +135,12 @@ class GlobalStack(SplitModePolicy, nn.Module):
         if which == "v1s_lazy":      # the fused route never stored it: the expand pass on the operands the call left in the prep workspace
             return ops.from_split(ws[("v1s_lazy", (), None)](), self.__dict__["_snvc_x3"]["exp"]["v1"])
         for k, v in ws.items():
+            if k[0] == which == "v1s":
+                st = self.__dict__.get("_snvc_x3")      # None: a GroupNorm stack, whose sheared first layer takes the exponent from the norm's bound
+                return ops.from_split(v, st["exp"]["v1"] if st is not None else
+                                      x3_exponent(x3_norm_bound(self.conv1[0][1], plan_for(self.conv1[0][0], "_x3", v.device))))
             if k[0] == which:
-                return ops.from_split(v, self.__dict__["_snvc_x3"]["exp"]["v1"]) if which == "v1s" else v
+                return v
         raise RuntimeError("no first-layer result in the workspace")
 
     def release_workspace(self):
@@ -120,7 +153,7 @@ class GlobalStack(SplitModePolicy, nn.Module):
             self.release_workspace()
         return super().train(mode)
 
-    def __getstate__(self):          # copy.deepcopy / torch.save(model): workspace, packed split-mode layers, overflow flag, streams are scratch
+    def __getstate__(self):          # copy.deepcopy / torch.save(model): workspace, packed split-mode layers, overflow flag are scratch
         state = self.__dict__.copy()
         for name in SCRATCH_ATTRS:
             state.pop(name, None)
@@ -299,8 +332,7 @@ class GlobalStack(SplitModePolicy, nn.Module):
             norm1 = self.conv1[0][1]
             b1 = x3_norm_bound(norm1, plan_for(self.conv1[0][0], "_x3", v1.device))
             e1 = x3_exponent(b1)
-            n, c = v1.size(0), v1.size(1)
-            v1s = SplitT(ops.to_split(v1, e1, out=self._buffer("v1s", (n, 2, c // 8) + tuple(v1.shape[2:]) + (8,), v1.device, torch.float16)), e1, b1)
+            v1s = SplitT(ops.to_split(v1, e1, out=self._v1s(v1.shape, v1.device, last="v1")), e1, b1)
         _mark(timing, "conv2", 0)
         v2 = self.conv2.fused_x3(v1s, flag=guard.flag)
         _mark(timing, "conv2", 1)
@@ -327,7 +359,7 @@ class GlobalStack(SplitModePolicy, nn.Module):
         columns = three 3 x 3 layers P_kw[u] = sum_{kd, kh} w[kd, kh, kw] Rq[row + kh - 1][u - kd] added 4 elements apart:
         G[u] = P_-1[u - 4] + P_0[u] + P_+1[u + 4], and G' (the last column: no kw = +1 taps) = P_-1[u - 4] + P_0[u].  One depth-1 3 x 3
         layer with 3 (kw) x 3 (depth class) x Cout output channels, folded in fp64 like sheared_kernels."""
-        if "sheared4" not in plans:
+        def fold():
             w = wr.detach().double()                                        # [Cout, C, kd, kh, kw]
             cout, c = w.shape[0], w.shape[1]
             k = torch.zeros((3, 3, cout, c, 3, 3), dtype=torch.float64, device=w.device)      # [kw][cls][co][c][kh][1 - kd]
@@ -335,8 +367,8 @@ class GlobalStack(SplitModePolicy, nn.Module):
                 for kd in kds:
                     for kw in (-1, 0, 1):
                         k[kw + 1, cls, :, :, :, 1 - kd] += w[:, :, kd + 1, :, kw + 1]
-            plans["sheared4"] = ops.Conv3dLayer(k.reshape(9 * cout, c, 3, 3).float().contiguous(), 3, 1, 1, 1, False, planar=True)
-        return plans["sheared4"]
+            return [k.reshape(9 * cout, c, 3, 3)]
+        return GlobalStack._layers(plans, "sheared4", ops.Conv3dLayer, fold)[0]
 
     def _sheared4_inputs(self, plans, wr, rq_src, q_up, m0, d, w):
         """(g, gcol, off, off_col) of the four-phase sheared layer: ``rq_src`` upsampled by ``q_up`` (1 or 2) is Rq."""
@@ -380,35 +412,22 @@ class GlobalStack(SplitModePolicy, nn.Module):
             _, wu4, _, _ = self._sheared_geometry4(m0, d, w)
             if 4 * ((wu4 + 3) // 4 * 4 + 16 + d) > 150 * 1024:
                 return None
-        st = self._x3_select(left.device, arithmetic)
+        st = self._x3_select(left.device, arithmetic)         # this route's one look at the split-mode state
         left_s = left[:, :, ::ds, ::ds].contiguous()
         right_r = right[:, :, ::ds, :].contiguous()          # rows ds*h; every input column
-        wt = conv.weight
         plans = _factored_plans(conv, c)
         scale, bias = _folded_bn(bn, plans["plan"])
-        planes = self._left_planes_layer(plans, wt.detach()[:, :c])(left_s.unsqueeze(2)).view(n, c, 3, h, w)
-        if phases == 2:
-            lay_g, lay_col = self._sheared_layers(plans, wt.detach()[:, c:], 2)
-            off, wu, off_col, wu_col = sheared_geometry(2, m0, d, w)
-            g = lay_g(ops.sheared_upsample(right_r, 1, wu, off).unsqueeze(2)).squeeze(2)
-            gcol = lay_col(ops.sheared_upsample(right_r, 1, wu_col, off_col).unsqueeze(2)).squeeze(2)
+        prep = _Prep(plans, c, conv.weight, st, scale, bias)  # the 2D layers on the fp32 kernels
+        self._left_planes(prep, left_s)
+        if phases == 2:      # the 3 x 7 layers of q = 2 with the feature itself in the upsampled image's place
+            g, gcol, off, off_col, _ = self._sheared_inputs(prep, right_r, 2, m0, d, w, up=1)
         else:
-            g, gcol, off, off_col = self._sheared4_inputs(plans, wt.detach()[:, c:], right_r, q_up, m0, d, w)
-        shape = (n, c, d, h, w)
-        try:
-            if st is not None:
-                v1s = self._buffer("v1s", (n, 2, c // 8, d, h, w, 8), left.device, torch.float16)
-                ops.sheared_expand_split(g, gcol, planes, *self._x3_v1_affine(st, scale, bias), v1s, phases, m0, off, off_col, ops.EPI_RELU,
-                                         st["flag"])
-                _ROUTES["ds_sheared_first_conv"] += 1
-                self.__dict__["_snvc_last_v1"] = "v1s"
-                return self._tail_x3(st, v1s, None)
-            v = self._buffer("v1", shape, left.device)
-            ops.sheared_expand(g, gcol, planes, scale, bias, v, phases, m0, off, off_col, ops.EPI_RELU)
-        except ops.Unsupported:
-            return None
-        _ROUTES["ds_sheared_first_conv"] += 1
-        return self._conv2_tail(v, shape, None, arithmetic)
+            g, gcol, off, off_col = self._sheared4_inputs(plans, conv.weight.detach()[:, c:], right_r, q_up, m0, d, w)
+        planes = prep.planes
+        return self._finish_first_layer(
+            prep, (n, c, d, h, w), left.device, None, arithmetic, "ds_sheared_first_conv",
+            lambda v1s, sc, bi: ops.sheared_expand_split(g, gcol, planes, sc, bi, v1s, phases, m0, off, off_col, ops.EPI_RELU, st["flag"]),
+            lambda v: ops.sheared_expand(g, gcol, planes, scale, bias, v, phases, m0, off, off_col, ops.EPI_RELU))
 
     def _gn_sheared_first_layer(self, left, right, shift, arithmetic=None):
         """``GlobalStack(gn=True)`` on uniformly spaced disparity planes WITHOUT the 1.47 GB volume (r6): with one
@@ -428,16 +447,13 @@ class GlobalStack(SplitModePolicy, nn.Module):
         if structure is None or not self._sheared_fits(structure[0], structure[1], d, w, True):
             return None
         q, m0 = structure
-        wt = conv.weight
-        plans = _factored_plans(conv, c)
-        planes = self._left_planes_layer(plans, wt.detach()[:, :c])(left.unsqueeze(2)).view(n, c, 3, h, w)
-        lay_g, lay_col = self._sheared_layers(plans, wt.detach()[:, c:], q)
-        off, wu, off_col, wu_col = sheared_geometry(q, m0, d, w)
-        g = lay_g(ops.sheared_upsample(right, q, wu, off).unsqueeze(2)).squeeze(2)
-        gcol = lay_col(ops.sheared_upsample(right, q, wu_col, off_col).unsqueeze(2)).squeeze(2)
+        prep = _Prep(_factored_plans(conv, c), c, conv.weight)      # the 2D layers on the fp32 kernels; no folded norm
+        self._left_planes(prep, left)
+        g, gcol, off, off_col, _ = self._sheared_inputs(prep, right, q, m0, d, w)
+        planes = prep.planes
         b1 = x3_norm_bound(norm, plan_for(conv, "_x3", left.device))
         e1 = x3_exponent(b1)
-        v1s = self._buffer("v1s", (n, 2, c // 8, d, h, w, 8), left.device, torch.float16)
+        v1s = self._v1s((n, c, d, h, w), left.device)
         gam = norm.weight.detach() if norm.weight is not None else None
         bet = norm.bias.detach() if norm.bias is not None else None
         try:
@@ -449,21 +465,18 @@ class GlobalStack(SplitModePolicy, nn.Module):
         except ops.Unsupported:
             return None
         _ROUTES["gn_sheared_first_conv"] += 1
-        self.__dict__["_snvc_last_v1"] = "v1s"
         return self._gn_tail_x3(SplitT(v1s, e1, b1), None, arithmetic)
 
-    def _conv2_tail(self, v1, shape, timing=None, arithmetic=None):
+    def _conv2_tail(self, v1, shape, timing=None, arithmetic=None, st=_ASK):
+        """Everything behind an fp32 first-layer result ``v1`` (from ``_v1``).  ``st``: the split-mode state the caller resolved for
+        this step (None: fp32 arithmetic); left out, it is asked for here."""
         gn_cost = self._gn_tail_x3(v1, timing, arithmetic)
         if gn_cost is not None:
-            self.__dict__["_snvc_last_v1"] = "v1"
             return gn_cost
-        st = self._x3_select(v1.device, arithmetic) if (v1.is_cuda and v1.dtype == torch.float32) else None
+        if st is _ASK:
+            st = self._x3_select(v1.device, arithmetic) if (v1.is_cuda and v1.dtype == torch.float32) else None
         if st is not None:      # split mode from an fp32 first-layer result: one layout pass (the sheared path writes the pair itself)
-            n, c = v1.size(0), v1.size(1)
-            v1s = ops.to_split(v1, st["exp"]["v1"], out=self._buffer("v1s", (n, 2, c // 8) + tuple(v1.shape[2:]) + (8,), v1.device, torch.float16))
-            self.__dict__["_snvc_last_v1"] = "v1"       # the fp32 first-layer result is in the workspace too
-            return self._tail_x3(st, v1s, timing)
-        self.__dict__["_snvc_last_v1"] = "v1"
+            return self._tail_x3(st, ops.to_split(v1, st["exp"]["v1"], out=self._v1s(v1.shape, v1.device, last="v1")), timing)
         _mark(timing, "conv2", 0)
         v, hv = self.conv2.fused(v1, out=self._buffer("v2", shape, v1.device), side_head=self.classifier)
         _mark(timing, "conv2", 1)
@@ -513,11 +526,10 @@ class GlobalStack(SplitModePolicy, nn.Module):
         conv, bn = self.conv1[0][0], self.conv1[0][1]
         if (self.training or torch.is_grad_enabled() or not isinstance(bn, nn.BatchNorm3d) or bn.training or left.device != conv.weight.device
                 or left.shape[1] * 2 != conv.in_channels or left.shape[3] % 4 != 0 or shift.size(1) < 4 or shift.dtype != torch.float32
-                or left.size(0) == 0):
-            return None
-        gen = self._forward_pair_steps(left, right, shift, 1, pause=True)
-        if next(gen, None) is None:        # the path taken has no pause point (it ran to its end): nothing to resume
-            return None
+                or left.size(0) == 0 or left.dtype != torch.float32):
+            return None                    # forward_pair would not reach the factored step, the one route with a pause point
+        gen = self._factored_pair_steps(left, right, shift, pause=True)
+        next(gen)
         return gen
 
     def _checked(self, fn, arithmetic, *args, **kw):
@@ -537,41 +549,35 @@ class GlobalStack(SplitModePolicy, nn.Module):
             return self._tail(self.conv2(self.conv1(volume)))
         n, c2 = volume.size(0), volume.size(1)
         shape = (n, c2 // 2) + tuple(volume.shape[2:])
-        gguard = self._gn_qualifies(volume.device, arithmetic) if (volume.dtype == torch.float32 and c2 % 16 == 0) else None
-        if gguard is not None:      # GroupNorm stack (r5): the volume split once, conv1 and everything behind it in split mode
+        splittable = volume.dtype == torch.float32 and c2 % 16 == 0
+        gguard = self._gn_qualifies(volume.device, arithmetic) if splittable else None
+        st = self._x3_select(volume.device, arithmetic) if splittable and gguard is None else None
+        if gguard is not None or st is not None:      # the volume split once, conv1 and everything behind it in split mode
             mul = ops.split_scale_for(*(scale_from if scale_from is not None else (volume,)))
-            vs = ops.to_split(volume, mul_dev=mul, out=self._buffer("vol_s", (n, 2, c2 // 8) + tuple(volume.shape[2:]) + (8,), volume.device,
-                                                                      torch.float16))
+            vs = SplitT(ops.to_split(volume, mul_dev=mul, out=self._buffer("vol_s", (n, 2, c2 // 8) + tuple(volume.shape[2:]) + (8,),
+                                                                             volume.device, torch.float16)), 0, None, mul)
+        if gguard is not None:      # GroupNorm stack (r5)
             _mark(timing, "conv1", 0)
-            v1s = self.conv1.fused_x3(SplitT(vs, 0, None, mul), flag=gguard.flag)
+            v1s = self.conv1.fused_x3(vs, flag=gguard.flag)
             _mark(timing, "conv1", 1)
             return self._gn_tail_x3(v1s, timing, arithmetic)
-        st = self._x3_select(volume.device, arithmetic) if (volume.dtype == torch.float32 and c2 % 16 == 0) else None
         if st is not None:
-            mul = ops.split_scale_for(*(scale_from if scale_from is not None else (volume,)))
-            vs = ops.to_split(volume, mul_dev=mul, out=self._buffer("vol_s", (n, 2, c2 // 8) + tuple(volume.shape[2:]) + (8,), volume.device,
-                                                                      torch.float16))
-            v1s = self._buffer("v1s", (n, 2, c2 // 16) + tuple(volume.shape[2:]) + (8,), volume.device, torch.float16)
+            v1s = self._v1s(shape, volume.device)
             _mark(timing, "conv1", 0)
-            self.conv1.fused_x3(SplitT(vs, 0, None, mul), out=v1s, out_exp=st["exp"]["v1"], flag=st["flag"])
+            self.conv1.fused_x3(vs, out=v1s, out_exp=st["exp"]["v1"], flag=st["flag"])
             _mark(timing, "conv1", 1)
-            self.__dict__["_snvc_last_v1"] = "v1s"
             return self._tail_x3(st, v1s, timing)
         _mark(timing, "conv1", 0)
-        v = self.conv1.fused(volume, out=self._buffer("v1", shape, volume.device))
+        v = self.conv1.fused(volume, out=self._v1(shape, volume.device))
         _mark(timing, "conv1", 1)
-        return self._conv2_tail(v, shape, timing, arithmetic)
+        return self._conv2_tail(v, shape, timing, arithmetic, st if splittable else _ASK)
 
     @staticmethod
     def _shift_structure(shift):
         """One device -> host round trip (it replaces the `assert torch.all(shift >= 0)` sync of the reference's wrapper):
         (all shifts >= 0, (q, m0) or None).  (q, m0): every row of ``shift`` is (m0 + d) / q for d = 0..D-1 with q in {1, 2}
         -- uniformly spaced whole- or half-pixel disparity planes -- exactly, in fp32."""
-        return GlobalStack._shift_structure_end(ops.shift_structure_begin(shift.detach()), shift.size(1))
-
-    @staticmethod
-    def _shift_structure_end(ticket, d):
-        return ops.shift_spacing_result(ticket, d)     # one launch (r3 first form: 12 torch kernels, 60 us)
+        return ops.shift_spacing_result(ops.shift_structure_begin(shift.detach()), shift.size(1))     # one launch (r3: 12 torch kernels, 60 us)
 
     @staticmethod
     def _sheared_fits(q, m0, d, w, training):
@@ -590,42 +596,36 @@ class GlobalStack(SplitModePolicy, nn.Module):
             return False
         return True
 
-    def _sheared_layers(self, plans, wr, q):
+    # ------------------------------------------------------------------------------- the first layer's weight folds and their layers
+    @staticmethod
+    def _layers(cache, key, kind, fold):
+        """``cache[key]``: the depth-1 "same" layers of one weight fold, built once per weight.  ``fold()`` returns the folded
+        [Cout', C, 3, kw] kernels; ``kind`` is what runs them: fp32 ``ops.Conv3dLayer`` or split-mode ``ops.Conv2dLayerX3``."""
+        if key not in cache:
+            def layer(k):
+                k, kw = k.float().contiguous(), k.shape[3]
+                return kind(k) if kind is ops.Conv2dLayerX3 else kind(k, kw, 1, kw // 2, 1, False, planar=True, ksize_h=3 if kw != 3 else 0)
+            cache[key] = tuple(layer(k) for k in fold())
+        return cache[key]
+
+    def _sheared_layers(self, plans, w, c, q, kind=ops.Conv3dLayer):
         """The depth-1 3 x 7 layers that compute G and G' (csrc/sheared_conv.hip): K[kh][t] = sum over (kd, kw) with
-        q*kw - kd = t of the right-half weights, folded in fp64; G' is the kernel without its kw = +1 taps."""
-        cache = plans.setdefault("sheared", {})
-        if q not in cache:
-            k = sheared_kernels(wr, q)                                     # [all | last column][depth class][Cout,C,3,7]
-            cout, c = k.shape[2], k.shape[3]
-            cache[q] = tuple(ops.Conv3dLayer(k[i].reshape(3 * cout, c, 3, 7).float().contiguous(), 7, 1, 3, 1, False, planar=True,
-                                             ksize_h=3) for i in range(2))
-        return cache[q]
-
-    def _sheared_layers_x3(self, plans, wr, q):
-        """``_sheared_layers`` as split-mode depth-1 layers (ops.Conv2dLayerX3): same folded 3 x 7 kernels."""
-        cache = plans.setdefault("sheared_x3", {})
-        if q not in cache:
-            k = sheared_kernels(wr, q)                                     # [all | last column][depth class][Cout,C,3,7]
-            cout, c = k.shape[2], k.shape[3]
-            cache[q] = tuple(ops.Conv2dLayerX3(k[i].reshape(3 * cout, c, 3, 7).float().contiguous()) for i in range(2))
-        return cache[q]
+        q*kw - kd = t of the right-half weights ``w[:, c:]``, folded in fp64; G' is the kernel without its kw = +1 taps."""
+        def fold():
+            k = sheared_kernels(w.detach()[:, c:], q)                      # [all | last column][depth class][Cout,C,3,7]
+            return [k[i].reshape(3 * k.shape[2], k.shape[3], 3, 7) for i in range(2)]
+        return self._layers(plans.setdefault("sheared" + _X3_KEY[kind], {}), q, kind, fold)
 
     @staticmethod
-    def _left_planes_weight(wl):
-        """[3 * Cout, C, 3, 3]: channel co*3 + cls = the kd taps depth class cls sees, summed in fp64."""
-        w = wl.detach().double()                                           # [Cout, C, kd, kh, kw]
-        k = torch.stack([w[:, :, 1:].sum(2), w.sum(2), w[:, :, :2].sum(2)], dim=1)          # [Cout, 3, C, kh, kw]
-        return k.reshape(-1, w.shape[1], 3, 3).float().contiguous()
-
-    @staticmethod
-    def _left_planes_layer(plans, wl):
+    def _left_planes_layer(plans, w, c, kind=ops.Conv3dLayer):
         """The three depth-class planes of the LEFT half of conv1(volume) as ONE depth-1 3x3 convolution of the left feature
         with 3*Cout output channels (channel co*3 + cls = the kd taps that class sees, summed in fp64): [N,3C,1,H,W] is
         the [N,C,3,H,W] tensor snvc_conv3d_forward_ex takes.  (r1-r2 ran the 3D kernel on the feature stacked 3 deep: a
         one-tile-deep launch whose time is one workgroup's whole channel loop, 50 us.)"""
-        if "left2d" not in plans:
-            plans["left2d"] = ops.Conv3dLayer(GlobalStack._left_planes_weight(wl), 3, 1, 1, 1, False, planar=True)
-        return plans["left2d"]
+        def fold():
+            wl = w.detach()[:, :c].double()                                 # [Cout, C, kd, kh, kw]
+            return [torch.stack([wl[:, :, 1:].sum(2), wl.sum(2), wl[:, :, :2].sum(2)], dim=1).reshape(-1, c, 3, 3)]      # [Cout, 3, C, kh, kw]
+        return GlobalStack._layers(plans, "left2d" + _X3_KEY[kind], kind, fold)[0]
 
     @staticmethod
     def _commuted_weights(wr):
@@ -638,51 +638,111 @@ class GlobalStack(SplitModePolicy, nn.Module):
         ke = torch.zeros((3, 3, cout, c, 3, 3), dtype=w.dtype, device=w.device)
         for kw in range(3):
             ke[:, kw, :, :, :, 1] = wk[..., kw]
-        return tuple(t.reshape(-1, c, 3, 3).contiguous() for t in (wk, kq, ke))
+        return tuple(t.reshape(-1, c, 3, 3) for t in (wk, kq, ke))
 
     @staticmethod
-    def _commuted_layers_x3(plans, wr):
-        if "commuted_x3" not in plans:
-            plans["commuted_x3"] = tuple(ops.Conv2dLayerX3(t.float()) for t in GlobalStack._commuted_weights(wr))
-        return plans["commuted_x3"]
-
-    @staticmethod
-    def _commuted_layers(plans, wr):
+    def _commuted_layers(plans, w, c, kind=ops.Conv3dLayer):
         """The depth-1 layers of the warp-after-convolution form of the first layer (csrc/sheared_conv.hip, any shift array):
         P_kd = conv2d(right, W[:, :, kd]); Q_kd = the kw = +1 taps alone (on the centre column); E[kd][kw] = the (c, kh)
         contraction with the kw taps, applied to the image's first column."""
-        if "commuted" not in plans:
-            w = wr.detach()                                                   # [Cout, C, kd, kh, kw]
-            cout, c = w.shape[0], w.shape[1]
-            wk = w.permute(2, 0, 1, 3, 4).contiguous()                        # [kd, Cout, C, kh, kw]
-            kq = torch.zeros_like(wk)
-            kq[..., 1] = wk[..., 2]
-            ke = torch.zeros((3, 3, cout, c, 3, 3), dtype=w.dtype, device=w.device)
-            for kw in range(3):
-                ke[:, kw, :, :, :, 1] = wk[..., kw]
-            mk = lambda t: ops.Conv3dLayer(t.reshape(-1, c, 3, 3).contiguous(), 3, 1, 1, 1, False, planar=True)   # noqa: E731
-            plans["commuted"] = (mk(wk), mk(kq), mk(ke))
-        return plans["commuted"]
+        return GlobalStack._layers(plans, "commuted" + _X3_KEY[kind], kind, lambda: GlobalStack._commuted_weights(w.detach()[:, c:]))
 
+    # ------------------------------------------------------------------------------------ the first layer's small 2D launches
+    def _left_planes(self, prep, left):
+        """Fills ``prep.planes`` ([N,C,3,H,W]: first / interior / last depth class of the left half) and, for the fused first layer,
+        ``prep.p_il``: the same planes channel-interleaved, a second output of the same launch."""
+        if prep.split_prep:     # one host call: the left feature's scale, its split pair, the 3x3 layer with 3 * Cout output channels
+            lx = self._left_planes_layer(prep.plans, prep.weight, prep.c, ops.Conv2dLayerX3)
+            if prep.fuse:
+                planes, prep.p_il = ops.planes_x3_il(left, lx, prep.prep_ws.setdefault("planes_il", {}))
+            else:
+                planes = ops.conv2d_x3_from_f32(left, [lx], prep.prep_ws.setdefault("planes", {}))[0]
+        else:
+            planes = self._left_planes_layer(prep.plans, prep.weight, prep.c)(left.unsqueeze(2))   # [N,3C,1,H,W] ...
+        prep.planes = planes.view(left.size(0), prep.c, 3, left.size(2), left.size(3))              # ... = [N,C,3,H,W]
+
+    # (the two chains below on two side streams, joined by events before the expand pass, were built and measured in r5 with interleaved
+    # legs: 2.185 ms/step against 2.130 on one stream -- the cross-stream event waits cost more than the chains' overlap buys.  Removed.)
+    def _sheared_inputs(self, prep, right, q, m0, d, w, up=None):
+        """(G, G', off, off_col, il) of the sheared layer with q phases on D = ``d`` planes and rows of ``w``: the depth-1 3 x 7 layers on
+        ``right`` upsampled by ``up`` (q unless the caller's feature already is the upsampled image).  ``il`` (fused first layer only):
+        (G | G' channel-interleaved, pitch, lp)."""
+        off, wu, off_col, wu_col = sheared_geometry(q, m0, d, w)
+        if prep.split_prep:
+            # r5: G and G' (depth-1 3 x 7 layers, 7.8 + 2.5 GFLOP: 84 + 31 us on the fp32 matrix pipe) in split mode like the layers behind
+            # them: Rq is written as a split pair scaled by the right feature's own maximum (one launch, no host round trip)
+            lx_g, lx_col = self._sheared_layers(prep.plans, prep.weight, prep.c, q, ops.Conv2dLayerX3)
+            # one host call for the five launches (behind the step's host sync the GPU is empty: five Python-level launches of
+            # 5-20 us kernels starve it); G / G' live in a per-model workspace until this call's expand pass has read them
+            il = None
+            if prep.fuse and q in (1, 2):      # G | G' also channel-interleaved, zero around the rows: what conv2's launch reads
+                pitch, lp = ops.fused_il_geometry(q, m0, d, w, wu, off, wu_col, off_col)
+                g, gcol, gi = ops.sheared_prep_x3_il(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep.prep_ws.setdefault("sheared_il", {}),
+                                                     pitch, lp)
+                il = (gi, pitch, lp)
+            else:
+                g, gcol = ops.sheared_prep_x3(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep.prep_ws.setdefault("sheared", {}))
+            _ROUTES["sheared_prep_x3"] += 1
+            return g, gcol, off, off_col, il
+        lay_g, lay_col = self._sheared_layers(prep.plans, prep.weight, prep.c, q)
+        up = q if up is None else up
+        g = lay_g(ops.sheared_upsample(right, up, wu, off).unsqueeze(2)).squeeze(2)                 # [N,3C,H,WU]
+        gcol = lay_col(ops.sheared_upsample(right, up, wu_col, off_col).unsqueeze(2)).squeeze(2)    # [N,3C,H,WU2]
+        return g, gcol, off, off_col, None
+
+    def _commuted_inputs(self, prep, right):
+        """(P, Q, E) of any other shift array: three 2D convolutions of the right feature (P, Q) and of its first columns (E)."""
+        if prep.split_prep and (9 * prep.weight.shape[0]) % 32 == 0:
+            # the three depth-1 3x3 layers in split mode: P and Q share the right feature's split pair (one host call), E runs on its
+            # first four columns (another)
+            lx_p, lx_q, lx_e = self._commuted_layers(prep.plans, prep.weight, prep.c, ops.Conv2dLayerX3)
+            p_, q_ = ops.conv2d_x3_from_f32(right, [lx_p, lx_q], prep.prep_ws.setdefault("commuted", {}))
+            e_ = ops.conv2d_x3_from_f32(right[:, :, :, :4], [lx_e], prep.prep_ws.setdefault("commuted_e", {}))[0]
+            _ROUTES["commuted_prep_x3"] += 1
+        else:
+            lay_p, lay_q, lay_e = self._commuted_layers(prep.plans, prep.weight, prep.c)
+            r5 = right.unsqueeze(2)
+            p_, q_ = lay_p(r5).squeeze(2), lay_q(r5).squeeze(2)
+            e_ = lay_e(right[:, :, :, :4].contiguous().unsqueeze(2)).squeeze(2)
+        return p_, q_, e_
+
+    def _finish_first_layer(self, prep, shape, device, timing, arithmetic, route, expand_split, expand):
+        """The expand pass of a first layer of fp32 ``shape`` [N,C,D,H,W] and everything behind it.  Split mode: ``expand_split(v1s, scale,
+        bias)`` writes the (hi, lo) pair conv2 reads (same bytes as the fp32 tensor, no layout pass); otherwise, or when that launcher
+        says ``Unsupported``, ``expand(v)`` writes the fp32 tensor.  Counts ``route``.  None: both said ``Unsupported`` (a limit
+        _sheared_fits does not mirror, rows that do not fit the LDS): the caller's next route gives the same answer."""
+        st = prep.st
+        if st is not None and prep.c % 8 == 0:
+            v1s = self._v1s(shape, device)
+            try:
+                expand_split(v1s, *self._x3_v1_affine(st, prep.scale, prep.bias))
+            except ops.Unsupported:
+                pass
+            else:
+                _mark(timing, "conv1", 1)
+                _ROUTES[route] += 1
+                return self._tail_x3(st, v1s, timing)
+        v = self._v1(shape, device)
+        try:
+            expand(v)
+        except ops.Unsupported:
+            return None
+        _mark(timing, "conv1", 1)
+        _ROUTES[route] += 1
+        return self._conv2_tail(v, shape, timing, arithmetic, st)
+
+    # -------------------------------------------------------------------------------------------------------- forward_pair
     def forward_pair(self, left, right, shift, downsample=1, factored=True, timing=None, shift_checked=False, sheared=True,
                      fused_bn=True, spacing="unknown", commuted=True, arithmetic=None):
         return self._checked(self._forward_pair_unchecked, arithmetic, left, right, shift, downsample, factored, timing, shift_checked,
                              sheared, fused_bn, spacing, commuted)
     forward_pair.__doc__ = "see _forward_pair_unchecked"
 
-    def _forward_pair_unchecked(self, *args, **kw):
-        """``_forward_pair_steps`` run to its end."""
-        return _run(self._forward_pair_steps(*args, **kw))
-
-    def _forward_pair_steps(self, left, right, shift, downsample=1, factored=True, timing=None, shift_checked=False, sheared=True,
-                            fused_bn=True, spacing="unknown", commuted=True, arithmetic=None, pause=False):
-        """A GENERATOR: with ``pause`` it yields once, right after the step's host sync (the shift array's sign / spacing check) with
-        the left half's planes and the speculative first-layer prep already queued -- ``build_cost_volume`` runs it up to there for
-        the model that consumed the last lazy volume (the reference's `assert` fires at build time as before, and the GPU is
-        not left idle while the host waits), ``GlobalStack.forward`` resumes it.  Without ``pause`` it runs straight through
-        (``_forward_pair_unchecked``).  The generator's return value is the cost tensor.
-
-        cost-volume build + 3D CNN forward: the unit BASELINE.json's metric counts.
+    def _forward_pair_unchecked(self, left, right, shift, downsample=1, factored=True, timing=None, shift_checked=False, sheared=True,
+                                fused_bn=True, spacing="unknown", commuted=True, arithmetic=None):
+        """cost-volume build + 3D CNN forward: the unit BASELINE.json's metric counts.  This function only picks the route, in this
+        order: training (_train_pair), the downsample 2 / 4 sheared layer, the GroupNorm sheared layer, the materialised volume
+        (_materialised_pair), the factored inference step (_factored_pair_steps).
 
         ``factored=True`` (inference, eval BatchNorm, downsample 1) uses the structure of the CONCAT
         volume: its left half repeats the left feature on every disparity plane
@@ -705,64 +765,90 @@ class GlobalStack(SplitModePolicy, nn.Module):
         current stream around the cost-volume launch and the first 3D convolution (the dominant kernel); used by
         bench.py for the roofline figures."""
         conv, bn = self.conv1[0][0], self.conv1[0][1]
-        training_graph = torch.is_grad_enabled() and (left.requires_grad or right.requires_grad or conv.weight.requires_grad)
-        if (training_graph and factored and timing is None and downsample == 1 and left.dtype == torch.float32
-                and left.size(3) % 4 == 0 and (left.size(2) * left.size(3)) % 4 == 0 and shift.size(1) >= 2):
-            # training (cfg4): the same factoring with a backward pass (half the first layer's dgrad / wgrad, no 1.5 GB volume)
-            structure = None
-            if sheared and left.size(0) > 0 and shift.size(1) >= 4 and shift.dtype == torch.float32 and left.size(1) <= 32:
-                nonneg, structure = self._shift_structure(shift)
-                assert nonneg
-            else:
-                assert torch.all(shift >= 0.)
-            plan = plan_for(conv, "", left.device)
-            if structure is not None and not self._sheared_fits(structure[0], structure[1], shift.size(1), left.size(3), True):
-                structure = None           # rows the sheared kernels do not cover (csrc/sheared_conv.hip's LDS limits): general path
-            if (structure is not None and isinstance(bn, nn.BatchNorm3d) and bn.training and left.size(3) % 8 == 0
-                    and left.size(3) <= 512 and fused_bn):
-                # ... with train-mode BatchNorm + ReLU folded around it: neither the raw result nor its gradient is ever stored
-                v = _ShearedFirstConvBNFn.apply(left, right, conv.weight, bn.weight, bn.bias, conv, bn, plan, structure[0], structure[1],
-                                                shift.size(1))
-                return self._tail(self.conv2(v))
-            if structure is not None:      # uniformly spaced planes: the sheared 2D form, forward and backward
-                v = _ShearedFirstConvFn.apply(left, right, conv.weight, bn.weight, bn.bias, conv, bn, EPI_RELU, plan, structure[0],
-                                              structure[1], shift.size(1))
-                return self._tail(self.conv2(v))
-            v = _FactoredFirstConvFn.apply(left, right, shift, conv.weight, bn.weight, bn.bias, conv, bn, EPI_RELU, plan, commuted)
-            return self._tail(self.conv2(v))
-        usable = (factored and downsample == 1 and not torch.is_grad_enabled() and isinstance(bn, nn.BatchNorm3d)
-                  and not bn.training and left.dtype == torch.float32 and left.size(3) % 4 == 0 and shift.size(1) >= 2)
-        if (downsample in (2, 4) and factored and sheared and timing is None and not torch.is_grad_enabled() and isinstance(bn, nn.BatchNorm3d)
-                and not bn.training and left.is_cuda and left.dtype == torch.float32 and left.size(2) % downsample == 0
-                and left.size(3) % downsample == 0 and shift.size(1) >= 4 and shift.dtype == torch.float32 and left.size(0) > 0
-                and left.size(1) % 8 == 0 and left.size(1) * 2 == conv.in_channels and left.shape == right.shape):
+        n, c, h, w = left.shape
+        d = shift.size(1)
+        grad = torch.is_grad_enabled()
+        if (grad and (left.requires_grad or right.requires_grad or conv.weight.requires_grad) and factored and timing is None
+                and downsample == 1 and left.dtype == torch.float32 and w % 4 == 0 and (h * w) % 4 == 0 and d >= 2):
+            return self._train_pair(left, right, shift, sheared, fused_bn, commuted)
+        # The inference gates.  Every route asks for `infer`; eval-mode BatchNorm is what folds into a scale and a bias.
+        infer = factored and not grad and left.dtype == torch.float32
+        bn_eval = isinstance(bn, nn.BatchNorm3d) and not bn.training
+        # The two special sheared layers have no general form behind them, so they also ask up front for what the factored step checks on
+        # its way or leaves to its fallbacks (a device, a float32 array of D >= 4 for the spacing kernel, a sample, split-pair channels),
+        # and they take no `timing`: their launches are not the brackets' launches.
+        special = (infer and sheared and timing is None and left.is_cuda and d >= 4 and shift.dtype == torch.float32 and n > 0
+                   and c % 8 == 0 and c * 2 == conv.in_channels)
+        # left.shape == right.shape: only this route strides both features itself, in front of every launcher that would compare them
+        if special and bn_eval and downsample in (2, 4) and h % downsample == 0 and w % downsample == 0 and left.shape == right.shape:
             cost = self._ds_sheared_first_layer(left, right, shift, downsample, arithmetic)      # r6; None: the materialised route below
             if cost is not None:
                 return cost
-        if (not usable and factored and sheared and downsample == 1 and timing is None and not torch.is_grad_enabled() and not self.training
-                and isinstance(bn, nn.GroupNorm) and bn.num_groups == conv.out_channels and left.is_cuda and left.dtype == torch.float32
-                and left.size(3) % 8 == 0 and left.size(3) <= 512 and shift.size(1) >= 4 and shift.dtype == torch.float32
-                and left.size(0) > 0 and left.size(1) % 8 == 0 and left.size(1) * 2 == conv.in_channels):
+        # W % 8, W <= 512: the statistics pass's row limits.  The downsample route asks them of its subsampled rows (inside); the factored
+        # step's expand kernels need W % 4 alone (below, _sheared_fits)
+        if (special and downsample == 1 and not self.training and isinstance(bn, nn.GroupNorm) and bn.num_groups == conv.out_channels
+                and w % 8 == 0 and w <= 512):
             cost = self._gn_sheared_first_layer(left, right, shift, arithmetic)       # r6; None: the paths below
             if cost is not None:
                 return cost
-        if not usable:
-            if timing is None:
-                vol = _BuildCostVolume.apply(left, right, shift, downsample)      # the eager volume
-                if torch.is_grad_enabled() or not vol.is_cuda:
-                    return self.forward(vol)
-                return self._forward_volume(vol, None, arithmetic, scale_from=(left, right) if downsample == 1 else None)
-            assert torch.all(shift >= 0.)        # the wrapper's own check (a sync) stays outside the event pair
-            _mark(timing, "volume", 0)
-            vol = ops.cost_volume_forward(left, right, shift, downsample)
-            _mark(timing, "volume", 1)
-            if torch.is_grad_enabled():
-                _mark(timing, "conv1", 0)
-                v = self.conv1(vol)
-                _mark(timing, "conv1", 1)
-                del vol
-                return self._tail(self.conv2(v))
-            return self._forward_volume(vol, timing, arithmetic, scale_from=(left, right))
+        if not (infer and bn_eval and downsample == 1 and w % 4 == 0 and d >= 2):
+            return self._materialised_pair(left, right, shift, downsample, timing, arithmetic)
+        return _run(self._factored_pair_steps(left, right, shift, timing, shift_checked, sheared, spacing, commuted, arithmetic))
+
+    def _train_pair(self, left, right, shift, sheared, fused_bn, commuted):
+        """Training (cfg4): the same factoring with a backward pass (half the first layer's dgrad / wgrad, no 1.5 GB volume)."""
+        conv, bn = self.conv1[0][0], self.conv1[0][1]
+        structure = None
+        if sheared and left.size(0) > 0 and shift.size(1) >= 4 and shift.dtype == torch.float32 and left.size(1) <= 32:
+            nonneg, structure = self._shift_structure(shift)
+            assert nonneg
+        else:
+            assert torch.all(shift >= 0.)
+        plan = plan_for(conv, "", left.device)
+        if structure is not None and not self._sheared_fits(structure[0], structure[1], shift.size(1), left.size(3), True):
+            structure = None           # rows the sheared kernels do not cover (csrc/sheared_conv.hip's LDS limits): general path
+        if (structure is not None and isinstance(bn, nn.BatchNorm3d) and bn.training and left.size(3) % 8 == 0
+                and left.size(3) <= 512 and fused_bn):
+            # ... with train-mode BatchNorm + ReLU folded around it: neither the raw result nor its gradient is ever stored
+            v = _ShearedFirstConvBNFn.apply(left, right, conv.weight, bn.weight, bn.bias, conv, bn, plan, structure[0], structure[1],
+                                            shift.size(1))
+        elif structure is not None:      # uniformly spaced planes: the sheared 2D form, forward and backward
+            v = _ShearedFirstConvFn.apply(left, right, conv.weight, bn.weight, bn.bias, conv, bn, EPI_RELU, plan, structure[0],
+                                          structure[1], shift.size(1))
+        else:
+            v = _FactoredFirstConvFn.apply(left, right, shift, conv.weight, bn.weight, bn.bias, conv, bn, EPI_RELU, plan, commuted)
+        return self._tail(self.conv2(v))
+
+    def _materialised_pair(self, left, right, shift, downsample, timing, arithmetic):
+        """The whole concat volume, then the modules: what the reference does.  With ``timing`` the volume is built by the launcher itself,
+        so that the event pair holds that launch alone."""
+        if timing is None:
+            vol = _BuildCostVolume.apply(left, right, shift, downsample)      # the eager volume
+            if torch.is_grad_enabled() or not vol.is_cuda:
+                return self.forward(vol)
+            return self._forward_volume(vol, None, arithmetic, scale_from=(left, right) if downsample == 1 else None)
+        assert torch.all(shift >= 0.)        # the wrapper's own check (a sync) stays outside the event pair
+        _mark(timing, "volume", 0)
+        vol = ops.cost_volume_forward(left, right, shift, downsample)
+        _mark(timing, "volume", 1)
+        if torch.is_grad_enabled():
+            _mark(timing, "conv1", 0)
+            v = self.conv1(vol)
+            _mark(timing, "conv1", 1)
+            del vol
+            return self._tail(self.conv2(v))
+        return self._forward_volume(vol, timing, arithmetic, scale_from=(left, right))
+
+    def _factored_pair_steps(self, left, right, shift, timing=None, shift_checked=False, sheared=True, spacing="unknown", commuted=True,
+                             arithmetic=None, pause=False):
+        """The factored inference step (eval BatchNorm, downsample 1, float32 features with W % 4 == 0, D >= 2), as a GENERATOR: with
+        ``pause`` it yields once, right after the step's host sync (the shift array's sign / spacing check) with the left half's planes
+        and the speculative first-layer prep already queued -- ``build_cost_volume`` runs it up to there for the model that consumed
+        the last lazy volume (the reference's `assert` fires at build time as before, and the GPU is not left idle while the host
+        waits), ``GlobalStack.forward`` resumes it.  Without ``pause`` it runs straight through.  The generator's return value is the
+        cost tensor.  Behind the sync: the sheared layer, else warp-after-convolution, else the right half built."""
+        conv, bn = self.conv1[0][0], self.conv1[0][1]
+        c, d, w = left.size(1), shift.size(1), left.size(3)
         # The one device -> host sync of the step (the wrapper's `assert shift >= 0`, here also the shift array's spacing) is
         # STARTED first and awaited only after everything that does not need its answer has been queued: the left half's
         # planes, and -- speculatively, for the spacing the previous call saw -- the sheared layer's two small 2D convolutions.
@@ -772,116 +858,43 @@ class GlobalStack(SplitModePolicy, nn.Module):
         known = shift_checked and spacing != "unknown"       # build_cost_volume already looked (LazyCostVolume.spacing)
         if known and not sheared:
             spacing = None
-        if not known and left.size(0) > 0 and shift.size(1) >= 4 and shift.dtype == torch.float32:
+        if not known and left.size(0) > 0 and d >= 4 and shift.dtype == torch.float32:
             # (r5: also with sheared=False -- the sign check rides on the same launch instead of a blocking torch.all in front of
             # an empty queue: 93 us of idle GPU per step on the any-shift path)
             ticket = ops.shift_structure_begin(shift.detach())
         elif not shift_checked:                  # a LazyCostVolume was checked when build_cost_volume made it
             assert torch.all(shift >= 0.)
-        c = left.size(1)
-        w = conv.weight
         plans = _factored_plans(conv, c)
         scale, bias = _folded_bn(bn, plans["plan"])
+        # the step's one look at the split-mode state (a paused step looks again when it goes on): it cannot change before the tail, where
+        # guard.post() is, so everything below is handed it
+        st = self._x3_select(left.device, arithmetic)
         # the first layer's small 2D convolutions run in split mode whenever the stack behind them does (same arithmetic contract:
         # fp32 accuracy on the half pipe); `arithmetic="fp32"` keeps every layer on the fp32-MFMA kernels
-        split_prep = bool(self.split_prep and c % 8 == 0 and (3 * conv.out_channels) % 32 == 0 and right.is_contiguous()
-                          and (not left.is_contiguous() or left.data_ptr() % 16 == 0) and right.data_ptr() % 16 == 0      # the scale launch reads float4
-                          and self._x3_select(left.device, arithmetic) is not None)
-        prep_ws = self.__dict__.setdefault("_snvc_prep_ws", {})
+        split_prep = bool(st is not None and self.split_prep and c % 8 == 0 and (3 * conv.out_channels) % 32 == 0 and right.is_contiguous()
+                          and (not left.is_contiguous() or left.data_ptr() % 16 == 0) and right.data_ptr() % 16 == 0)     # the scale launch reads float4
+        # the fused first layer (fused_first) reads the planes and G | G' channel-interleaved
+        fuse = bool(split_prep and self.fused_first and sheared and conv.out_channels == c and left.size(0) > 0
+                    and st["layers"]["conv2"].fused_first_form(left.size(0), (d,) + tuple(left.shape[2:])))
         # r6: the prep results (planes, G / G', P / Q / E) live in per-model buffers that the NEXT call through here overwrites.  Every
         # call takes a new epoch; a step that was paused (build_cost_volume's speculative start) compares it when it is resumed
         # (a process-wide counter: invalidate_plans(model) drops the attribute, and a fresh count must not meet an old step's number)
         epoch = self.__dict__["_snvc_prep_epoch"] = next(_PREP_EPOCH)
-        if split_prep:      # one host call: the left feature's scale, its split pair, the 3x3 layer with 3 * Cout output channels
-            lx = plans.get("left2d_x3")
-            if lx is None:
-                lx = plans["left2d_x3"] = ops.Conv2dLayerX3(self._left_planes_weight(w.detach()[:, :c]))
-            # the fused first layer (fused_first) reads the planes channel-interleaved: a second output of the same launch
-            st_f = self._x3_select(left.device, arithmetic)
-            fuse = bool(self.fused_first and sheared and conv.out_channels == c and isinstance(bn, nn.BatchNorm3d) and left.size(0) > 0
-                        and st_f["layers"]["conv2"].fused_first_form(left.size(0), (shift.size(1),) + tuple(left.shape[2:])))
-            if fuse:
-                planes, p_il = ops.planes_x3_il(left, lx, prep_ws.setdefault("planes_il", {}))
-            else:
-                planes = ops.conv2d_x3_from_f32(left, [lx], prep_ws.setdefault("planes", {}))[0]
-        else:
-            fuse = False
-            planes = self._left_planes_layer(plans, w.detach()[:, :c])(left.unsqueeze(2))   # [N,3C,1,H,W] ...
-        planes = planes.view(left.size(0), c, 3, left.size(2), left.size(3))                 # ... = [N,C,3,H,W]: first / interior / last
-        shape = (left.size(0), c, shift.size(1)) + tuple(left.shape[2:])
-
-        def sheared_inputs(q, m0):
-            off, wu, off_col, wu_col = sheared_geometry(q, m0, shift.size(1), left.size(3))
-            if split_prep:
-                # r5: G and G' (depth-1 3 x 7 layers, 7.8 + 2.5 GFLOP: 84 + 31 us on the fp32 matrix pipe) in split mode like the layers behind
-                # them: Rq is written as a split pair scaled by the right feature's own maximum (one launch, no host round trip)
-                lx_g, lx_col = self._sheared_layers_x3(plans, w.detach()[:, c:], q)
-                # one host call for the five launches (behind the step's host sync the GPU is empty: five Python-level launches of
-                # 5-20 us kernels starve it); G / G' live in a per-model workspace until this call's expand pass has read them
-                if fuse and q in (1, 2):      # G | G' also channel-interleaved, zero around the rows: what conv2's launch reads
-                    pitch, lp = ops.fused_il_geometry(q, m0, shift.size(1), left.size(3), wu, off, wu_col, off_col)
-                    g, gcol, gi = ops.sheared_prep_x3_il(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep_ws.setdefault("sheared_il", {}),
-                                                         pitch, lp)
-                    _ROUTES["sheared_prep_x3"] += 1
-                    return g, gcol, off, off_col, (gi, pitch, lp)
-                g, gcol = ops.sheared_prep_x3(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep_ws.setdefault("sheared", {}))
-                _ROUTES["sheared_prep_x3"] += 1
-                return g, gcol, off, off_col, None
-            lay_g, lay_col = self._sheared_layers(plans, w.detach()[:, c:], q)
-            if not self.prep_streams:
-                g = lay_g(ops.sheared_upsample(right, q, wu, off).unsqueeze(2)).squeeze(2)             # [N,3C,H,WU]
-                gcol = lay_col(ops.sheared_upsample(right, q, wu_col, off_col).unsqueeze(2)).squeeze(2)   # [N,3C,H,WU2]
-                return g, gcol, off, off_col, None
-            # r5: G and G' are two independent chains of small launches (an upsample + a depth-1 convolution of ~100 workgroups each:
-            # their time is one workgroup's latency, not throughput) beside the left half's planes already queued on this stream.
-            # They run on two side streams and join before the expand pass: three chains side by side instead of end to end.
-            cur = torch.cuda.current_stream(left.device)
-            s1, s2 = self._side_streams(left.device)
-            start = torch.cuda.Event()
-            start.record(cur)            # `right` (and everything else queued so far) is ready behind this point
-            out = []
-            for st_, lay, wu_, off_ in ((s1, lay_g, wu, off), (s2, lay_col, wu_col, off_col)):
-                with torch.cuda.stream(st_):
-                    st_.wait_event(start)
-                    t = lay(ops.sheared_upsample(right, q, wu_, off_).unsqueeze(2)).squeeze(2)
-                    t.record_stream(cur)     # allocated in the side stream's pool, consumed by the expand pass on `cur`
-                    done = torch.cuda.Event()
-                    done.record(st_)
-                out.append((t, done))
-            for _, done in out:
-                cur.wait_event(done)
-            return out[0][0], out[1][0], off, off_col, None
-
-        def commuted_inputs():
-            # any other shift array: three 2D convolutions of the right feature (P, Q) and of its first columns (E)
-            if split_prep and (9 * conv.out_channels) % 32 == 0:
-                # the three depth-1 3x3 layers in split mode: P and Q share the right feature's split pair (one host call), E runs on its
-                # first four columns (another)
-                lx_p, lx_q, lx_e = self._commuted_layers_x3(plans, w.detach()[:, c:])
-                p_, q_ = ops.conv2d_x3_from_f32(right, [lx_p, lx_q], prep_ws.setdefault("commuted", {}))
-                e_ = ops.conv2d_x3_from_f32(right[:, :, :, :4], [lx_e], prep_ws.setdefault("commuted_e", {}))[0]
-                _ROUTES["commuted_prep_x3"] += 1
-            else:
-                lay_p, lay_q, lay_e = self._commuted_layers(plans, w.detach()[:, c:])
-                r5 = right.unsqueeze(2)
-                p_, q_ = lay_p(r5).squeeze(2), lay_q(r5).squeeze(2)
-                e_ = lay_e(right[:, :, :, :4].contiguous().unsqueeze(2)).squeeze(2)
-            return p_, q_, e_
-
-        can_commute = commuted and shift.dtype == torch.float32 and left.size(3) <= 2048
+        prep = _Prep(plans, c, conv.weight, st, scale, bias, split_prep, fuse, self.__dict__.setdefault("_snvc_prep_ws", {}))
+        self._left_planes(prep, left)
+        can_commute = commuted and shift.dtype == torch.float32 and w <= 2048
         structure, guess, ready, ready_general = (spacing if known else None), None, None, None
         if ticket is not None:
             guess = plans.get("spacing_seen")    # (q, m0, D, W) of the previous call, or ("general", D, W): a guess, checked below
             _mark(timing, "volume", 0)
-            dims = (shift.size(1), left.size(3))
-            if sheared and guess is not None and guess[0] != "general" and guess[2:] == dims:
-                ready = sheared_inputs(guess[0], guess[1])
-            elif can_commute and (not sheared or (guess is not None and guess[0] == "general" and guess[1:] == dims)):
-                ready_general = commuted_inputs()
-            nonneg, structure = self._shift_structure_end(ticket, shift.size(1))
+            if sheared and guess is not None and guess[0] != "general" and guess[2:] == (d, w):
+                ready = self._sheared_inputs(prep, right, guess[0], guess[1], d, w)
+            elif can_commute and (not sheared or (guess is not None and guess[0] == "general" and guess[1:] == (d, w))):
+                ready_general = self._commuted_inputs(prep, right)
+            nonneg, structure = ops.shift_spacing_result(ticket, d)
             assert nonneg                        # same contract as build_cost_volume (reference __init__.py:12)
             if sheared:
-                plans["spacing_seen"] = structure + dims if structure is not None else ("general",) + dims
+                plans["spacing_seen"] = structure + (d, w) if structure is not None else ("general", d, w)
             else:
                 structure = None                 # the caller asked for the general path
         if pause:
@@ -892,95 +905,76 @@ class GlobalStack(SplitModePolicy, nn.Module):
             if not (self.__dict__.get("_snvc_prep_epoch") == epoch and conv.__dict__.get("_snvc_factored") is plans
                     and fresh(plans["stamp"], (conv.weight,)) and all(a is b for a, b in zip(_folded_bn(bn, plans["plan"]), (scale, bias)))):
                 _ROUTES["lazy_prefetch_stale"] += 1
-                return (yield from self._forward_pair_steps(left, right, shift, downsample, factored, timing, True, sheared, fused_bn,
-                                                            structure, commuted, arithmetic, pause=False))
-        if structure is not None and not self._sheared_fits(structure[0], structure[1], shift.size(1), left.size(3), False):
+                return self._forward_pair_unchecked(left, right, shift, 1, True, timing, True, sheared, True, structure, commuted, arithmetic)
+            # ... and the layers behind the first one are those of the moment the step goes on (conv2's weight is in no key above): the
+            # split-mode state is looked up again, the 2D launches queued before the pause stay as they were decided
+            prep.st = self._x3_select(left.device, arithmetic)
+        if structure is not None and not self._sheared_fits(structure[0], structure[1], d, w, False):
             structure = None                     # rows the sheared kernels do not cover: the paths below
+        cost = None
         if structure is not None:
-            q, m0 = structure
             if ready is None or tuple(guess[:2]) != tuple(structure):
                 _mark(timing, "volume", 0)
-                ready = sheared_inputs(q, m0)    # first call, or the spacing changed: the guess is dropped
-            g, gcol, off, off_col, il = ready
-            _mark(timing, "volume", 1)
-            _mark(timing, "conv1", 0)
-            st = self._x3_select(left.device, arithmetic)
-            if st is not None and il is not None:
-                # the fused first layer: nothing runs here -- conv2's launch (the "conv2" marks) forms the pair itself
-                _mark(timing, "conv1", 1)
-                _ROUTES["sheared_first_conv"] += 1
-                v1_sc, v1_bi = self._x3_v1_affine(st, scale, bias)
-
-                def expand():      # last_first_layer(): the pair, from the operands this call leaves in the prep workspace
-                    t = self._buffer("v1s", (shape[0], 2, c // 8) + tuple(shape[2:]) + (8,), left.device, torch.float16)
-                    ops.sheared_expand_split(g, gcol, planes, v1_sc, v1_bi, t, q, m0, off, off_col, ops.EPI_RELU, None)
-                    return t
-                self.__dict__["_snvc_ws"] = self.__dict__.get("_snvc_ws", {})
-                self.__dict__["_snvc_ws"][("v1s_lazy", (), None)] = expand
-                self.__dict__["_snvc_last_v1"] = "v1s_lazy"
-                return self._tail_x3(st, None, timing, fused=(shape, left.device, dict(
-                    gi=il[0], pitch=il[1], lp=il[2], p_il=p_il, v_scale=v1_sc, v_bias=v1_bi, q=q, m0=m0, off=off, off_col=off_col,
-                    v_flags=ops.EPI_RELU)))
-            if st is not None and c % 8 == 0:
-                # split mode: the expand pass writes the (hi, lo) pair conv2 reads (same bytes as the fp32 tensor, no layout pass)
-                v1s = self._buffer("v1s", (shape[0], 2, c // 8) + tuple(shape[2:]) + (8,), left.device, torch.float16)
-                try:
-                    ops.sheared_expand_split(g, gcol, planes, *self._x3_v1_affine(st, scale, bias), v1s, q, m0, off, off_col,
-                                             ops.EPI_RELU | (ops.EPI_STREAM_OUT if self.stream_out else 0), st["flag"])
-                except ops.Unsupported:
-                    st = None
-                else:
-                    _mark(timing, "conv1", 1)
-                    _ROUTES["sheared_first_conv"] += 1
-                    self.__dict__["_snvc_last_v1"] = "v1s"
-                    return self._tail_x3(st, v1s, timing)
-            v = self._buffer("v1", shape, left.device)
-            try:
-                ops.sheared_expand(g, gcol, planes, scale, bias, v, q, m0, off, off_col, ops.EPI_RELU)
-            except ops.Unsupported:              # a limit _sheared_fits does not mirror: same answer on the general paths
-                structure = None
-            else:
-                _mark(timing, "conv1", 1)
-                _ROUTES["sheared_first_conv"] += 1
-                return self._conv2_tail(v, shape, timing, arithmetic)
-        if can_commute:
-            # any other shift array: interpolation along w commutes with the convolution -- three 2D convolutions of the right
-            # feature, three interpolations per output voxel, the warped volume is not built either (csrc/sheared_conv.hip)
+                ready = self._sheared_inputs(prep, right, structure[0], structure[1], d, w)    # first call, or the spacing changed: the guess is dropped
+            cost = self._sheared_pair(prep, ready, structure, (left.size(0), c, d) + tuple(left.shape[2:]), timing, arithmetic)
+        if cost is None and can_commute:
             if ready_general is None:
                 _mark(timing, "volume", 0)
-                ready_general = commuted_inputs()
-            p_, q_, e_ = ready_general
-            _mark(timing, "volume", 1)
-            _mark(timing, "conv1", 0)
-            st = self._x3_select(left.device, arithmetic)
-            if st is not None and c % 8 == 0:       # split mode: the expand pass writes the (hi, lo) pair conv2 reads
-                v1s = self._buffer("v1s", (shape[0], 2, c // 8) + tuple(shape[2:]) + (8,), left.device, torch.float16)
-                try:
-                    ops.warped_expand_split(p_, q_, e_, planes, shift, *self._x3_v1_affine(st, scale, bias), v1s,
-                                            ops.EPI_RELU | (ops.EPI_STREAM_OUT if self.stream_out else 0), st["flag"])
-                except ops.Unsupported:
-                    pass
-                else:
-                    _mark(timing, "conv1", 1)
-                    _ROUTES["commuted_first_conv"] += 1
-                    self.__dict__["_snvc_last_v1"] = "v1s"
-                    return self._tail_x3(st, v1s, timing)
-            v = self._buffer("v1", shape, left.device)
-            try:
-                ops.warped_expand(p_, q_, e_, planes, shift, scale, bias, v, ops.EPI_RELU)
-            except ops.Unsupported:              # rows that do not fit the LDS (grows with D): build the right half instead
-                pass
-            else:
-                _mark(timing, "conv1", 1)
-                _ROUTES["commuted_first_conv"] += 1
-                return self._conv2_tail(v, shape, timing, arithmetic)
+                ready_general = self._commuted_inputs(prep, right)
+            cost = self._commuted_pair(prep, ready_general, shift, timing, arithmetic)
+        if cost is None:
+            cost = self._right_half_pair(prep, left, right, shift, timing, arithmetic)
+        return cost
+
+    def _sheared_pair(self, prep, ready, structure, shape, timing, arithmetic):
+        """Uniformly spaced planes: the expand pass over G / G' and the left planes, or (fused first layer) nothing at all here."""
+        (q, m0), (g, gcol, off, off_col, il), st, planes = structure, ready, prep.st, prep.planes
+        _mark(timing, "volume", 1)
+        _mark(timing, "conv1", 0)
+        if st is not None and il is not None:
+            # the fused first layer: nothing runs here -- conv2's launch (the "conv2" marks) forms the pair itself
+            _mark(timing, "conv1", 1)
+            _ROUTES["sheared_first_conv"] += 1
+            v1_sc, v1_bi = self._x3_v1_affine(st, prep.scale, prep.bias)
+
+            def expand(t):      # last_first_layer(): the pair, from the operands this call leaves in the prep workspace
+                ops.sheared_expand_split(g, gcol, planes, v1_sc, v1_bi, t, q, m0, off, off_col, ops.EPI_RELU, None)
+                return t
+            self._v1s(shape, g.device, lazy=expand)
+            return self._tail_x3(st, None, timing, fused=(shape, g.device, dict(
+                gi=il[0], pitch=il[1], lp=il[2], p_il=prep.p_il, v_scale=v1_sc, v_bias=v1_bi, q=q, m0=m0, off=off, off_col=off_col,
+                v_flags=ops.EPI_RELU)))
+        flags = ops.EPI_RELU | (ops.EPI_STREAM_OUT if self.stream_out else 0)
+        return self._finish_first_layer(
+            prep, shape, g.device, timing, arithmetic, "sheared_first_conv",
+            lambda v1s, sc, bi: ops.sheared_expand_split(g, gcol, planes, sc, bi, v1s, q, m0, off, off_col, flags, st["flag"]),
+            lambda v: ops.sheared_expand(g, gcol, planes, prep.scale, prep.bias, v, q, m0, off, off_col, ops.EPI_RELU))
+
+    def _commuted_pair(self, prep, ready, shift, timing, arithmetic):
+        """Any other shift array: interpolation along w commutes with the convolution -- three 2D convolutions of the right
+        feature, three interpolations per output voxel, the warped volume is not built either (csrc/sheared_conv.hip).  None: rows
+        that do not fit the LDS (grows with D): the right half is built instead."""
+        (p_, q_, e_), st, planes = ready, prep.st, prep.planes
+        _mark(timing, "volume", 1)
+        _mark(timing, "conv1", 0)
+        flags = ops.EPI_RELU | (ops.EPI_STREAM_OUT if self.stream_out else 0)
+        shape = (planes.size(0), prep.c, shift.size(1)) + tuple(planes.shape[3:])
+        return self._finish_first_layer(
+            prep, shape, planes.device, timing, arithmetic, "commuted_first_conv",
+            lambda v1s, sc, bi: ops.warped_expand_split(p_, q_, e_, planes, shift, sc, bi, v1s, flags, st["flag"]),
+            lambda v: ops.warped_expand(p_, q_, e_, planes, shift, prep.scale, prep.bias, v, ops.EPI_RELU))
+
+    def _right_half_pair(self, prep, left, right, shift, timing, arithmetic):
+        """The warped right half built, the factored 3D convolution over it with the left planes added in its epilogue (r2's path)."""
+        shape = (left.size(0), prep.c, shift.size(1)) + tuple(left.shape[2:])
         _mark(timing, "volume", 0)
         try:
             vol_r = ops.cost_volume_forward_right(right, shift, out=self._buffer("vol_r", shape, left.device))   # [N,C,D,H,W]
         except ops.Unsupported:                  # rows beyond the row builder's width: the materialised volume, as the reference
-            return self.forward_pair(left, right, shift, downsample, factored=False, timing=timing, arithmetic=arithmetic)
+            return self.forward_pair(left, right, shift, 1, factored=False, timing=timing, arithmetic=arithmetic)
         _mark(timing, "volume", 1)
         _mark(timing, "conv1", 0)
-        v = plans["right"](vol_r, scale, bias, None, ops.EPI_RELU, self._buffer("v1", shape, left.device), depth_planes=planes)
+        v = prep.plans["right"](vol_r, prep.scale, prep.bias, None, ops.EPI_RELU, self._v1(shape, left.device), depth_planes=prep.planes)
         _mark(timing, "conv1", 1)
-        return self._conv2_tail(v, shape, timing, arithmetic)
+        return self._conv2_tail(v, shape, timing, arithmetic, prep.st)
+

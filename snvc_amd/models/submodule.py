@@ -78,7 +78,7 @@ def invalidate_plans(module: Optional[nn.Module] = None) -> None:
 # events that copy.deepcopy / pickle must not carry (rebuilt on first use); "workspace": scratch that release_workspace() gives back.
 _ATTRS = {"_snvc_plans": "plans", "_snvc_plans_f16": "plans", "_snvc_plans_x3": "plans", "_snvc_plans2d": "plans", "_snvc_plans2d_t": "plans",
           "_snvc_factored": "cache", "_snvc_factored_train": "cache", "_snvc_ws": "workspace", "_snvc_coor_maps": "cache", "_snvc_x3": "scratch",
-          "_snvc_x3_off": "state", "_snvc_x3_guard": "scratch", "_snvc_last_v1": "state", "_snvc_streams": "scratch", "_snvc_lazy_warned": "state",
+          "_snvc_x3_off": "state", "_snvc_x3_guard": "scratch", "_snvc_last_v1": "state", "_snvc_lazy_warned": "state",
           "_snvc_prep_ws": "workspace", "_snvc_prep_epoch": "state"}
 CACHE_ATTRS = tuple(_ATTRS)
 WORKSPACE_ATTRS = tuple(k for k, v in _ATTRS.items() if v == "workspace")

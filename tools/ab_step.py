@@ -27,8 +27,7 @@ model.eval().to(dev)
 left, right, shift = bench.make_inputs(0, dev)
 
 
-def setup(prep_streams=False, check="call", s2q=True, fused_tail=True, q16_min=256, split_prep=True, stream_out=False):
-    model.prep_streams = prep_streams
+def setup(check="call", s2q=True, fused_tail=True, q16_min=256, split_prep=True, stream_out=False):
     model.overflow_check = check
     model.fused_tail = fused_tail
     ops.X3_Q16_S2[0] = s2q
@@ -39,7 +38,6 @@ def setup(prep_streams=False, check="call", s2q=True, fused_tail=True, q16_min=2
 
 LEGS = {
     "default": {},
-    "prep chains on side streams": {"prep_streams": True},
     "overflow check deferred": {"check": "deferred"},
     "stride-2 layers: 32x32x16 serial-plane form": {"s2q": False},
     "two-launch tail (r4)": {"fused_tail": False},

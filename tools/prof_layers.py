@@ -174,8 +174,7 @@ with torch.no_grad():
         plans = model.conv1[0][0].__dict__["_snvc_factored"]
         from snvc_amd.models.submodule import _folded_bn
         scale, bias = _folded_bn(model.conv1[0][1], plans["plan"])
-        wl = model.conv1[0][0].weight.detach()[:, :bench.C]
-        planes = model._left_planes_layer(plans, wl)(left.unsqueeze(2)).view(1, bench.C, 3, bench.H, bench.W)
+        planes = model._left_planes_layer(plans, model.conv1[0][0].weight, bench.C)(left.unsqueeze(2)).view(1, bench.C, 3, bench.H, bench.W)
         vol_r = ops.cost_volume_forward_right(right, shift)
         fn = lambda: plans["right"](vol_r, scale, bias, None, ops.EPI_RELU, None, depth_planes=planes)  # noqa: E731
     elif args.layer == "cost_volume":
