@@ -30,6 +30,7 @@
 #include "common.hpp"
 #include "elementwise_internal.hpp"
 #include "snvc_fused.h"
+#include "snvc_dedup.h"
 
 namespace snvc {
 namespace {
@@ -105,8 +106,23 @@ struct F16SrcArgs : F16Args {
     const float *p_il;         // [N][3][CGin][Hin][Win][8]: the left half's depth-class planes
     const float *v_scale, *v_bias;      // the first layer's folded affine, [8 * CGin]
     int64_t gi_bs;             // floats between samples of gi
-    int v_pitch, v_lp, v_q, v_m0, v_off, v_off2, v_flags;
+    int v_pitch, v_lp, v_q, v_m0, v_off, v_off2, v_flags;      // v_flags: SNVC_EPI_RELU | SRC_DEDUP
 };
+constexpr int SRC_DEDUP = 1 << 30;      // F16SrcArgs::v_flags, internal (the C entry points refuse it): duplicate wedge tiles are not computed
+
+// The wedge (include/snvc_dedup.h).  Left of the image's first column the sheared half of v1 reads the zero pad of gi -- a G index below
+// 0 -- and on the interior planes (class 1) nothing else of v1 = f(G + P) depends on d.  Tile (d0, w0) of the 4 x 4 x 32 tiling is PURE
+// when its whole input image, planes d0 - 1 .. d0 + 4 and columns w0 - 1 .. w0 + 32, lies there: all interior planes, not the last
+// column (which reads G'), and the largest G index of the image -- column w0 + 32 on plane d0 - 1 -- below 0.  Pure tiles of one
+// (n, th, tw) receive the same image, run the same MFMAs in the same order and store the same bits on each of their depth rows.  The
+// pure d0 of a column are consecutive; the first is the representative, the others are duplicates.  One definition for the kernel
+// that skips the duplicates, the kernel that copies them back, the launcher and the host query.
+__host__ __device__ __forceinline__ bool wedge_tile_pure(int D, int W, int q, int m0, int off, int d0, int w0) {
+    return d0 >= 2 && d0 + 3 <= D - 3 && w0 + 32 < W - 1 && q * (w0 + 32) - (d0 - 1) - m0 + off < 0;
+}
+__host__ __device__ __forceinline__ bool wedge_tile_duplicate(int D, int W, int q, int m0, int off, int d0, int w0) {
+    return wedge_tile_pure(D, W, q, m0, off, d0, w0) && wedge_tile_pure(D, W, q, m0, off, d0 - 4, w0);
+}
 
 // A-fragment register ring depth (k-steps ahead).  Measured on cfg5 (k7 / k5 / k3 ms): 2: 9.70 / 1.92 / 0.91;
 // 4: 9.38 / 2.00 / 0.91; 6: 8.99 / 1.82 / 0.85 (242-246 VGPRs, no spills); 8: 8.89 / 1.83 / 0.86 with spills.
@@ -787,6 +803,9 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
     const int64_t n = blockIdx.z;
     const int od0 = td * Cfg::TD, oh0 = th * TH, ow0 = tw * 32;
     const int id0 = od0 - a.pad_d, ih0 = oh0 - a.pad_h, iw0 = ow0 - a.pad_w;
+    if constexpr (SRC == 1) {      // block-uniform, in front of every LDS access and barrier: wedge_copy_kernel stores this tile behind the launch
+        if ((a.v_flags & SRC_DEDUP) && wedge_tile_duplicate(a.Din, a.Win, a.v_q, a.v_m0, a.v_off, od0, ow0)) return;
+    }
 
     f32x4q acc[NB][2][2];
 #pragma unroll
@@ -1155,6 +1174,64 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
         }
     }
     if (vmax >= kHalfMax && a.overflow) atomicOr(a.overflow, 1);
+}
+
+// Behind conv3d_x3q_kernel<EPI, 1> with SRC_DEDUP, on its stream: the duplicate wedge tiles it returned from.  Workgroup = one
+// duplicate tile (tw, td) of one (n, th): ONE depth row of the column's representative tile -- both planes, every channel group, the
+// tile's rows inside the tensor, 32 columns, and the side head's row -- is read (16.5 KB at 32 channels) and stored to the tile's four
+// depth rows (one row per workgroup -- four times the loads -- measured slower: profiles/wedge_dedup/copy_kernel_variants.txt).  16-byte loads and stores only: a C8 piece is 16 bytes; the side head's rows are
+// 16-byte aligned because the launcher asks W % 4 == 0 of a deduplicated launch.  The grid spans the duplicate range of tile column 0,
+// the widest (wedge_tile_pure is monotone in w0): workgroups of narrower columns' non-duplicates return.
+struct WedgeCopyArgs {
+    _Float16 *y, *y_lo;
+    float *y_head;             // or NULL
+    int64_t y_bs;              // halves between samples of y / y_lo
+    int CG, D, H, W, q, m0, off;
+    int td0, ntw;              // first duplicate depth tile of column 0; tile columns with duplicates
+};
+
+__global__ void __launch_bounds__(256)
+wedge_copy_kernel(const WedgeCopyArgs a) {
+    const int tw = blockIdx.x % a.ntw, td = a.td0 + blockIdx.x / a.ntw;
+    const int d0 = td * X3QCfg::TD, w0 = tw * 32, h0 = blockIdx.y * X3QCfg::TH;
+    if (!wedge_tile_duplicate(a.D, a.W, a.q, a.m0, a.off, d0, w0)) return;      // block-uniform
+    int rep = d0 - X3QCfg::TD;
+    while (wedge_tile_pure(a.D, a.W, a.q, a.m0, a.off, rep - X3QCfg::TD, w0)) rep -= X3QCfg::TD;
+    const int64_t n = blockIdx.z, hw = (int64_t)a.H * a.W, dhw = hw * a.D;
+    const int tid = threadIdx.x;
+    // item = ((plane * CG + group) * 4 + row) * 32 + column: 256 items are two channel groups' rows, CG / 2 rounds per plane
+    const int col = tid & 31, h = h0 + ((tid >> 5) & 3);
+    const int rounds = 2 * a.CG * 128 / 256;
+    if (h < a.H) {
+        for (int r0 = 0; r0 < rounds; r0 += 4) {
+            uint4 *p[4];
+            uint4 v[4];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int g = 2 * (r0 + k) + (tid >> 7);      // plane * CG + group
+                const bool on = r0 + k < rounds;
+                const int plane = on ? g / a.CG : 0, cg = on ? g - plane * a.CG : 0;
+                p[k] = reinterpret_cast<uint4 *>((plane ? a.y_lo : a.y) + n * a.y_bs) + (cg * dhw + (int64_t)h * a.W + w0 + col);
+                if (on) v[k] = p[k][rep * hw];
+            }
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                if (r0 + k < rounds) {
+#pragma unroll
+                    for (int r = 0; r < X3QCfg::TD; ++r) p[k][(d0 + r) * hw] = v[k];
+                }
+            }
+        }
+    }
+    if (a.y_head && tid < 32) {
+        const int hh = h0 + (tid >> 3);
+        if (hh < a.H) {
+            uint4 *p = reinterpret_cast<uint4 *>(a.y_head + n * dhw + (int64_t)hh * a.W + w0) + (tid & 7);
+            const uint4 v = p[rep * hw / 4];
+#pragma unroll
+            for (int r = 0; r < X3QCfg::TD; ++r) p[(d0 + r) * hw / 4] = v;
+        }
+    }
 }
 
 // ------------------------------------------------------------------------- depth-1 (2D) layers in split mode (r5)
@@ -2234,6 +2311,36 @@ template <int EPI>      // the fused sheared first layer: the image is formed in
 void launch_x3q_src(const F16Args &a, const F16Geom &g, hipStream_t st) {
     launch_lds<conv3d_x3q_kernel<EPI, 1>>(g.grid, 256, X3QCfg::LDS_BYTES, st, static_cast<const F16SrcArgs &>(a));
 }
+// The duplicate wedge tiles of a [D][.][W] layer on the 4 x 4 x 32 tiling, by a walk of wedge_tile_pure: per tile column tw < max_tw
+// the representative and the last duplicate depth tile (-1 / -1 without duplicates).  Returns the duplicates of one (n, th).
+struct WedgeRange { int64_t dups; int td0, td1, ntw; };      // column 0's first and last duplicate; columns with duplicates (the leading ones)
+WedgeRange wedge_ranges(int D, int W, int q, int m0, int off, int64_t *first_td, int64_t *last_td, int max_tw) {
+    WedgeRange r{0, -1, -1, 0};
+    const int tiles_d = (D + X3QCfg::TD - 1) / X3QCfg::TD, tiles_w = (W + 31) / 32;
+    for (int tw = 0; tw < tiles_w; ++tw) {
+        int first = -1, last = -1;
+        for (int td = 0; td < tiles_d; ++td) {
+            if (!wedge_tile_pure(D, W, q, m0, off, td * X3QCfg::TD, tw * 32)) continue;
+            if (first < 0) first = td;
+            last = td;
+        }
+        if (last == first) first = last = -1;      // a lone pure tile has no duplicate
+        if (tw < max_tw && first_td && last_td) { first_td[tw] = first; last_td[tw] = last; }
+        if (first < 0) continue;
+        r.dups += last - first;
+        r.ntw = tw + 1;
+        if (tw == 0) { r.td0 = first + 1; r.td1 = last; }
+    }
+    return r;
+}
+// behind launch_x3q_src with SRC_DEDUP: wedge_copy_kernel over the duplicates' bounding range; nothing without duplicates
+void launch_wedge_copy(const F16SrcArgs &a, hipStream_t st) {
+    const WedgeRange r = wedge_ranges(a.Din, a.Win, a.v_q, a.v_m0, a.v_off, nullptr, nullptr, 0);
+    if (r.dups == 0) return;
+    WedgeCopyArgs w{a.y, a.y_lo, a.y_head, a.y_bs, a.Cout / 8, a.Dout, a.Hout, a.Wout, a.v_q, a.v_m0, a.v_off, r.td0, r.ntw};
+    wedge_copy_kernel<<<dim3((unsigned)((r.td1 - r.td0 + 1) * r.ntw), (unsigned)a.tiles_h, (unsigned)a.N), 256, 0, st>>>(w);
+}
+
 // persistent: one workgroup per CU (144 KB of LDS each), a multiple of 8 so that a workgroup's jobs b, b + G, ... stay on its XCD
 void launch_x3s2q(const F16Args &a, const F16Geom &g, hipStream_t st) {
     int wg = device_cu_count();
@@ -2686,7 +2793,13 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const F16x3Call &c) {
     if (!f.launch[call] || (resflags && !f.split_res)) return fail(SNVC_ERR_UNSUPPORTED, f.unsupported);
     if (g.jobs >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles");
     if (c.src && to_f32) return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a split C8 output");
+    // the wedge's duplicate tiles are skipped and copied back only where the copy is all 16-byte accesses (the side head's rows: W % 4
+    // == 0) and there is a duplicate at all; otherwise the launch computes every tile
+    if ((b.v_flags & SRC_DEDUP) && ((c.y_head && (d->Wout % 4 || (reinterpret_cast<uintptr_t>(c.y_head) & 15))) ||
+                                    wedge_ranges(a.Din, a.Win, b.v_q, b.v_m0, b.v_off, nullptr, nullptr, 0).dups == 0))
+        b.v_flags &= ~SRC_DEDUP;
     f.launch[call](b, g, st);
+    if (b.v_flags & SRC_DEDUP) launch_wedge_copy(b, st);
     return check_launch("snvc_f16x3_conv3d_forward");
 }
 
@@ -2706,10 +2819,11 @@ int snvc_f16x3_conv3d_forward(const snvc_conv3d_desc *d, const void *x_hi, const
     return f16x3_forward(d, c);
 }
 
-int snvc_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias, void *y_hi,
-                                    void *y_lo, const float *head, float *y_head, float head_mul, int *overflow, const float *gi,
-                                    int64_t pitch, int64_t lp, const float *p_il, const float *v_scale, const float *v_bias, int q, int m0,
-                                    int off, int off2, int v_flags, void *stream) {
+// snvc_fused_first_conv3d_forward | snvc_dedup_fused_first_conv3d_forward (dedup: the wedge's duplicate tiles are copied, not computed)
+static int fused_first_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias, void *y_hi,
+                               void *y_lo, const float *head, float *y_head, float head_mul, int *overflow, const float *gi,
+                               int64_t pitch, int64_t lp, const float *p_il, const float *v_scale, const float *v_bias, int q, int m0,
+                               int off, int off2, int v_flags, bool dedup, void *stream) {
     using namespace snvc;
     if (!d || !gi || !p_il || !v_scale || !v_bias) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_first_conv3d_forward: null pointer");
     if (d->transposed || d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->dilation != 1 || d->Cin % 8 || d->Din < 1 || d->Hin < 1 || d->Win < 1 ||
@@ -2727,11 +2841,40 @@ int snvc_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packe
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: one sample of gi / p_il must stay below 2 GiB");
     F16SrcArgs s{};
     s.gi = gi; s.p_il = p_il; s.v_scale = v_scale; s.v_bias = v_bias; s.gi_bs = 6 * CG * H * pitch * 8;
-    s.v_pitch = (int)pitch; s.v_lp = (int)lp; s.v_q = q; s.v_m0 = m0; s.v_off = off; s.v_off2 = off2; s.v_flags = v_flags;
+    s.v_pitch = (int)pitch; s.v_lp = (int)lp; s.v_q = q; s.v_m0 = m0; s.v_off = off; s.v_off2 = off2;
+    s.v_flags = v_flags | (dedup ? SRC_DEDUP : 0);
     F16x3Call c;
     c.packed_weight = packed_weight; c.scale = scale; c.bias = bias; c.y_hi = y_hi; c.y_lo = y_lo;
     c.head = head; c.y_head = y_head; c.head_mul = head_mul; c.res_mul = 1.0f; c.overflow = overflow; c.src = &s; c.stream = stream;
     return f16x3_forward(d, c);
+}
+
+int snvc_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias, void *y_hi,
+                                    void *y_lo, const float *head, float *y_head, float head_mul, int *overflow, const float *gi,
+                                    int64_t pitch, int64_t lp, const float *p_il, const float *v_scale, const float *v_bias, int q, int m0,
+                                    int off, int off2, int v_flags, void *stream) {
+    return fused_first_forward(d, packed_weight, scale, bias, y_hi, y_lo, head, y_head, head_mul, overflow, gi, pitch, lp, p_il, v_scale, v_bias,
+                               q, m0, off, off2, v_flags, false, stream);
+}
+
+int snvc_dedup_abi_version(void) { return 1; }
+
+int snvc_dedup_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias,
+                                          void *y_hi, void *y_lo, const float *head, float *y_head, float head_mul, int *overflow,
+                                          const float *gi, int64_t pitch, int64_t lp, const float *p_il, const float *v_scale,
+                                          const float *v_bias, int q, int m0, int off, int off2, int v_flags, void *stream) {
+    return fused_first_forward(d, packed_weight, scale, bias, y_hi, y_lo, head, y_head, head_mul, overflow, gi, pitch, lp, p_il, v_scale, v_bias,
+                               q, m0, off, off2, v_flags, true, stream);
+}
+
+int64_t snvc_dedup_fused_first_tiles(const snvc_conv3d_desc *d, int q, int m0, int off, int64_t *first_td, int64_t *last_td, int max_tw) {
+    using namespace snvc;
+    if (!d || d->Din < 1 || d->Win < 1 || (q != 1 && q != 2) || max_tw < 0 || (max_tw > 0 && (!first_td || !last_td))) {
+        fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_dedup_fused_first_tiles: a desc, q = 1 | 2, and max_tw entries to write");
+        return -1;
+    }
+    for (int tw = 0; tw < max_tw; ++tw) first_td[tw] = last_td[tw] = -1;
+    return wedge_ranges((int)d->Din, (int)d->Win, q, m0, off, first_td, last_td, max_tw).dups;
 }
 
 int64_t snvc_f16x3_conv3d_stats_workspace_bytes(const snvc_conv3d_desc *d) {

@@ -176,6 +176,10 @@ class GlobalStack(SplitModePolicy, nn.Module):
     # (csrc/conv3d_f16.hip, conv3d_x3q_kernel<EPI, 1>): the expand pass, its 0.74 GB pair and conv2's reads of it are gone.  Same bits.
     # False: the expand pass writes the pair, conv2 reads it (every other route does that anyway).
     fused_first = True
+    # the fused first layer's wedge (include/snvc_dedup.h): left of the image's first column the volume does not depend on the plane,
+    # so conv2's tiles that lie wholly there (8.3 % at cfg2) are computed once per (row, column) and copied.  Same bits.  False: every
+    # tile is computed.
+    dedup_wedge = True
     split_prep = True    # split mode: the sheared first layer's depth-1 3 x 7 layers (G, G') on the half pipe too (False: fp32 MFMA, as r4)
     fused_tail = True    # split mode: conv5's epilogue contracts its result with the folded one-channel tail (False: r4's two launches)
 
@@ -269,7 +273,8 @@ class GlobalStack(SplitModePolicy, nn.Module):
         v2_out = self._buffer("v2s", (n, 2, 4, d, h, w, 8), dev, torch.float16)
         if fused is not None:
             v2s, hv = L["conv2"].forward_fused_first(n=n, in_sp=(d, h, w), x_exp=E["v1"], scale=A["conv2"][0], bias=A["conv2"][1], flags=EPI_RELU,
-                                                     out_exp=E["conv2"], head=self.classifier.weight, overflow=flag, out=v2_out, **fused[2])
+                                                     out_exp=E["conv2"], head=self.classifier.weight, overflow=flag, out=v2_out,
+                                                     dedup=bool(self.dedup_wedge), **fused[2])
             _ROUTES["fused_first_conv"] += 1
         else:
             v2s, hv = L["conv2"](v1s, E["v1"], *A["conv2"], flags=EPI_RELU, out_exp=E["conv2"], head=self.classifier.weight, overflow=flag,

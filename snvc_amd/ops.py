@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _derived, _fused, _lib
+from . import _dedup, _derived, _fused, _lib
 from ._lib import (EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID, EPI_STREAM_OUT, F32, F64, Conv3dDesc,
                    Unsupported, check)
 
@@ -1641,6 +1641,20 @@ def fused_il_geometry(q: int, m0: int, d: int, w: int, wu: int, off: int, wu_col
     return hi - lo + 1, -lo
 
 
+def fused_first_wedge_tiles(d: int, w: int, q: int, m0: int, off: int):
+    """The wedge's duplicate tiles of the fused first layer on a [d, ., w] volume (snvc_dedup_fused_first_tiles: the rule the
+    kernels use; include/snvc_dedup.h).  Returns (duplicates per (n, th), first, last): per 32-column tile column the depth tile
+    index of the representative and of the last duplicate, -1 / -1 where the column has none.  Host only."""
+    desc = _lib.Conv3dDesc()
+    desc.Din, desc.Win = int(d), int(w)
+    ntw = (int(w) + 31) // 32
+    first, last = (ctypes.c_int64 * ntw)(), (ctypes.c_int64 * ntw)()
+    dups = int(_dedup.lib().snvc_dedup_fused_first_tiles(ctypes.byref(desc), int(q), int(m0), int(off), first, last, ntw))
+    if dups < 0:
+        raise ValueError(_lib.lib().snvc_last_error_string().decode())
+    return dups, list(first), list(last)
+
+
 def sheared_prep_x3_il(right, q: int, wu: int, off: int, wu_col: int, off_col: int, lay_g: "Conv2dLayerX3", lay_col: "Conv2dLayerX3", ws: dict,
                        pitch: int, lp: int):
     """``sheared_prep_x3`` whose two 3 x 7 layers also write G | G' as the channel-interleaved buffer ``gi`` [N,6,C/8,H,pitch,8]
@@ -1904,11 +1918,12 @@ class Conv3dLayerX3(_ConvGeometry):
 
     def forward_fused_first(self, gi, pitch: int, lp: int, p_il, v_scale, v_bias, q: int, m0: int, off: int, off_col: int, v_flags: int,
                             n: int, in_sp, x_exp: int = 0, scale=None, bias=None, flags: int = 0, out=None, out_exp: int = 0, head=None,
-                            overflow=None):
+                            overflow=None, dedup: bool = False):
         """``self(v1s, x_exp, ...)`` with v1s = the sheared first layer's split result (``sheared_expand_split`` of the same operands:
         ``gi`` / ``p_il`` channel-interleaved, ``v_scale`` / ``v_bias`` its folded affine carrying 2**x_exp) formed inside the launch
         (snvc_fused_first_conv3d_forward): same bits, v1s is never stored.  Raises Unsupported when the launch would not take the
-        16x16x32 form."""
+        16x16x32 form.  ``dedup``: the wedge's duplicate tiles (``fused_first_wedge_tiles``) are copied from their representative
+        instead of computed (snvc_dedup_fused_first_conv3d_forward): same bits again."""
         in_sp = tuple(int(v) for v in in_sp)
         if not self.fused_first_form(n, in_sp):
             raise Unsupported("forward_fused_first: the layer does not run on the 16x16x32 form at this size")
@@ -1925,12 +1940,12 @@ class Conv3dLayerX3(_ConvGeometry):
         if n == 0:
             return (out, y_head) if head is not None else out
         d = self._desc(n, in_sp, flags, algo, 0, _batch_stride(out), 0)
+        entry = (_dedup.lib().snvc_dedup_fused_first_conv3d_forward if dedup else _fused.lib().snvc_fused_first_conv3d_forward)
         with torch.cuda.device(gi.device):
-            check(_fused.lib().snvc_fused_first_conv3d_forward(ctypes.byref(d), _ptr(packed), _ptr(sc), _ptr(bi), _ptr(out), _lo_ptr(out),
-                                                               _ptr(head), _ptr(y_head), float(2.0 ** -out_exp), _ptr(overflow), _ptr(gi),
-                                                               int(pitch), int(lp), _ptr(p_il), _ptr(v_scale), _ptr(v_bias), int(q), int(m0),
-                                                               int(off), int(off_col), int(v_flags), _stream(gi)),
-                  "snvc_fused_first_conv3d_forward")
+            check(entry(ctypes.byref(d), _ptr(packed), _ptr(sc), _ptr(bi), _ptr(out), _lo_ptr(out), _ptr(head), _ptr(y_head),
+                        float(2.0 ** -out_exp), _ptr(overflow), _ptr(gi), int(pitch), int(lp), _ptr(p_il), _ptr(v_scale), _ptr(v_bias), int(q),
+                        int(m0), int(off), int(off_col), int(v_flags), _stream(gi)),
+                  "snvc_dedup_fused_first_conv3d_forward" if dedup else "snvc_fused_first_conv3d_forward")
         return (out, y_head) if head is not None else out
 
     def forward_f32(self, x, x_mul_dev, residual_f32: Optional[torch.Tensor] = None, relu: bool = False):
