@@ -1,6 +1,7 @@
 /*
  * snvc_forms.h -- which kernel form the geometry launchers of libsnvc_hip.so take: the cost volume (csrc/cost_volume.hip) and the
- * feature -> voxel gather in both directions (csrc/voxel_gather.hip, csrc/voxel_gather_bwd.hip).  Kept apart from snvc_hip.h,
+ * feature -> voxel gather in both directions (csrc/voxel_gather.hip, csrc/voxel_gather_bwd.hip); and which form the weight
+ * gradient of the 3D convolutions takes (csrc/conv3d_bwd.hip; last section).  Kept apart from snvc_hip.h,
  * whose declaration set and ABI number are pinned; this header versions itself through snvc_forms_abi_version().
  *
  * Every launcher decides its form in one host function, from the sizes, the element type, the alignment of its operands and the
@@ -90,6 +91,29 @@ enum snvc_voxel_gather_backward_form_id {
     SNVC_GB_SORTED = 3          /* keys, radix sort, gather_bwd_pieces_kernel<64>, combine: no atomics */
 };
 SNVC_API int snvc_voxel_gather_backward_form(int64_t N, int64_t F, int64_t Hf, int64_t Wf, int64_t V, int deterministic, int64_t *info);
+
+/* snvc_conv3d_wgrad / snvc_conv3d_wgrad_amax (csrc/conv3d_bwd.hip): the plan the launcher itself makes for this descriptor.  x_align /
+ * g_align: the largest of 16 / 8 / 4 that divides the address of x / g.  The forms in their order of precedence; a layer that misses
+ * a condition takes the next form of its key (ksize, stride, dilation).  vec: rows and batch strides of both operands in whole
+ * pieces of 4 floats (2: g in pieces of 2) at aligned addresses, without SNVC_ALGO_SCALAR_STAGING; flat16: both tensors readable
+ * as 16-byte aligned float4 streams.
+ * info: [0] bytes of a staging piece (16 / 8 / 4), [1] workspace bytes the form's kernels touch (never more than
+ *       snvc_conv3d_wgrad_workspace_bytes; the split-operand forms keep their amax words at its end), [2] split-operand forms: dparts
+ *       depth parts; 12-wave forms: P partitions; k1: voxel chunks; generic forms: partitions, [3] split-operand forms: dchunk planes per
+ *       part; 12-wave forms: upx units per XCD; generic forms: tap chunks (grid.z), [4] grid.x, [5] grid.y * grid.z, [6] threads per
+ *       workgroup, [7] dynamic LDS bytes. */
+enum snvc_conv3d_wgrad_form_id {
+    SNVC_WG_K1_STREAM = 1,      /* wgrad_k1_small_partial + _final: k1, stride 1, Cout <= 2, D*H*W % 4 == 0, 16-byte aligned operands */
+    SNVC_WG_X3 = 2,             /* conv3d_wgrad_x3_kernel<16- | 8-byte rows>: key 311, flat16, vec == 4 or 8-byte rows on both grids, neither
+                                   WGRAD_FP32 nor DIRECT, columns x depth parts within the slab budget */
+    SNVC_WG_WINO = 3,           /* conv3d_wgrad_wino_kernel: key 311, vec == 4, not DIRECT */
+    SNVC_WG_X3S2 = 4,           /* conv3d_wgrad_x3s2_kernel: key 321, flat16, vec 4 or 2, neither WGRAD_FP32 nor DIRECT, the big grid
+                                   exactly twice the small one, slab budget */
+    SNVC_WG_S2 = 5,             /* conv3d_wgrad_s2_kernel<4 | 2>: key 321, flat16, vec 4 or 2, not DIRECT */
+    SNVC_WG_KSPLIT = 6,         /* conv3d_wgrad_kernel<K-split WgradCfg, 4 | 2>: keys 311 / 321 with vec != 0 */
+    SNVC_WG_TAPS = 7            /* conv3d_wgrad_kernel<tap-split WgradCfg, 0>: keys 111, 311, 321, 511, 512, 711, scalar staging */
+};
+SNVC_API int snvc_conv3d_wgrad_form(const snvc_conv3d_desc *desc_host, int x_align, int g_align, int64_t *info);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
-"""ctypes binding of the kernel-form queries of ``libsnvc_hip.so`` (``include/snvc_forms.h``): which form the cost-volume and
-gather launchers take for a shape.  Host code only -- nothing is launched and no device is needed.
+"""ctypes binding of the kernel-form queries of ``libsnvc_hip.so`` (``include/snvc_forms.h``): which form the cost-volume,
+gather and weight-gradient launchers take for a shape.  Host code only -- nothing is launched and no device is needed.
 
 Kept apart from ``_lib.SIGNATURES`` (the table of ``include/snvc_hip.h``): this header versions itself through
 ``snvc_forms_abi_version()``.  The symbols are resolved on ``_lib.lib()``'s handle at first use, so importing this module
@@ -11,7 +11,7 @@ from typing import Tuple
 
 from . import _lib
 
-_ABI = 1   # snvc_forms_abi_version() this binding was written against
+_ABI = 2   # snvc_forms_abi_version() this binding was written against
 
 c_i64 = ctypes.c_int64
 c_p = ctypes.c_void_p
@@ -29,6 +29,7 @@ SIGNATURES = {
     "snvc_cost_volume_backward_form": (c_int, [c_i64] * 6 + [c_int, c_int, c_p]),
     "snvc_voxel_gather_forward_form": (c_int, [c_int] + [c_i64] * 5 + [c_f, c_f, c_int, c_p]),
     "snvc_voxel_gather_backward_form": (c_int, [c_i64] * 5 + [c_int, c_p]),
+    "snvc_conv3d_wgrad_form": (c_int, [ctypes.POINTER(_lib.Conv3dDesc), c_int, c_int, c_p]),
 }
 
 # info slot names per query (the header's comments)
@@ -36,6 +37,8 @@ CV_FWD_INFO = ("RB", "hblocks", "dsplit", "dchunk", "grid_x", "grid_y", "threads
 CV_BWD_INFO = ("", "", "", "", "grid_x", "", "threads", "")
 GATHER_FWD_INFO = ("run", "nruns", "pow2", "slices", "grid_x", "grid_yz", "threads", "lds")
 GATHER_BWD_INFO = ("vchunk", "nvchunks", "passes", "max_pieces", "grid_x", "grid_y", "threads", "lds")
+# slots 2 and 3 by form family: split-operand forms (dparts, dchunk), 12-wave forms (P, upx), k1 (chunks, -), generic (P, tap chunks)
+WGRAD_INFO = ("piece_bytes", "ws_bytes", "parts", "per_part", "grid_x", "grid_yz", "threads", "lds")
 
 _bound = None
 
@@ -84,3 +87,10 @@ def voxel_gather_forward(kind, n, f, hf, wf, v, resolution, aligned=ALIGNED_ALL)
 
 def voxel_gather_backward(n, f, hf, wf, v, deterministic=True):
     return _query(lib().snvc_voxel_gather_backward_form, GATHER_BWD_INFO, n, f, hf, wf, v, int(deterministic))
+
+
+def conv3d_wgrad(desc, x_align=16, g_align=16):
+    """(form id or -status; info; error text) of snvc_conv3d_wgrad[_amax] for a ``_lib.Conv3dDesc`` and the largest of 16 / 8 / 4
+    that divides the address of x / g.  ``parts`` / ``per_part``: dparts / dchunk (split-operand forms), P / upx (12-wave forms),
+    chunks / 0 (k1 streaming form), partitions / tap chunks (generic forms)."""
+    return _query(lambda *a: lib().snvc_conv3d_wgrad_form(ctypes.byref(desc), *a), WGRAD_INFO, x_align, g_align)

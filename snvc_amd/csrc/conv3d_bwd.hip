@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "snvc_forms.h"
 
 
 namespace snvc {
@@ -1436,43 +1437,340 @@ __global__ void wgrad_reduce_x3_kernel(const float *__restrict__ partial, float 
 }
 
 constexpr int kWgradPartitions = 512;   // 2 workgroups per CU
-#define SNVC_CFG(...) WgradCfg<__VA_ARGS__>
+
+// ------------------------------------------------------------------ host side: one plan behind launch, workspace size and form query
+// The partial sums are slabs of [32][32] floats, one per channel pair, tap and whatever the form splits the voxels into.  Slabs per
+// channel pair that the forms write:
+//   generic forms (K-split, tap-split)   kWgradPartitions x taps
+//   12-wave forms                        P partitions (wgrad_units) x kWinoSlabs / kS2Slabs
+//   split-operand forms                  columns x depth parts x kX3Slabs / kX3S2Slabs, never more than 3x3x3's generic count
+// The workspace holds the largest count a key's forms can reach (wgrad_slab_budget) and, behind the slabs, the split-operand forms'
+// own amax words.
+constexpr int64_t kSlabBytes = 1024 * sizeof(float);
+constexpr int kWinoSlabs = 2 * 3 * WinoWgradCfg::SLABS;      // 2 row halves x 3 kd x 18 (kh, position) per partition
+constexpr int kS2Slabs = 4 * 27;                             // 4 tile quarters x 27 taps per partition
+constexpr int kX3Slabs = 2 * 27, kX3S2Slabs = 27;            // 2 row pairs (stride 2: 1 slab) x 27 taps per column and depth part
+constexpr int64_t kAmaxBytes = 1024;
+static_assert(2 * SNVC_AMAX_SLOTS * sizeof(unsigned) <= kAmaxBytes, "two amax arrays");
+constexpr int64_t kK1Chunk4 = 16384;    // k1 streaming form: 64k voxels per workgroup (x four channels, r6; 8192 measured slower)
+
+struct WgradGeneric;
+
+// Everything snvc_conv3d_wgrad_amax decides, from the descriptor, the operands' alignment and the CU count alone
+struct WgradPlan {
+    int form;                       // snvc_conv3d_wgrad_form_id
+    int vec;                        // WgradArgs::vec: X and G rows staged in pieces of 4 / 2 floats, 0 = scalar
+    int piece_bytes;                // what the form's kernel really stages with
+    int64_t in_sz, out_sz, x_bs, g_bs;
+    int pairs, cx_blocks;           // 32 x 32 channel pairs
+    int tiles_h, tiles_w;           // generic and 12-wave forms
+    int64_t ntiles;
+    int P, upx;                     // partitions; units per XCD (12-wave forms)
+    const WgradGeneric *generic;
+    bool rows16;                    // split-operand forms: the 16-byte-row kernel (else the 8-byte one)
+    int job_pairs, hblocks, wsegs, dparts, dchunk, njobs;
+    int64_t chunks;                 // k1 streaming form
+    dim3 grid;
+    int threads, lds_bytes;
+    int slabs;                      // partial slabs per (pair, tap) the reduce sums
+    int64_t ws_bytes, amax_offset;  // workspace bytes the form touches; where the split-operand forms keep their amax words
+};
+
+// ------------------------------------------------------------------ launch routines: one per form family, each reads only the plan
+// (in the forms' order of precedence, which is also the order the kernels have in the code object)
+struct WgradOperands {
+    const float *x, *g;
+    float *dw;
+    void *workspace;
+    const uint32_t *amax_x, *amax_g;
+    hipStream_t st;
+};
+
+int launch_k1_stream(const snvc_conv3d_desc &d, const WgradPlan &p, const WgradOperands &o) {
+    const int64_t S4 = (int64_t)d.Dout * d.Hout * d.Wout / 4;
+    if (d.Cout == 1)
+        wgrad_k1_small_partial<1><<<p.grid, p.threads, 0, o.st>>>(o.x, o.g, (float *)o.workspace, d.Cin, S4, kK1Chunk4, p.x_bs, p.g_bs);
+    else
+        wgrad_k1_small_partial<2><<<p.grid, p.threads, 0, o.st>>>(o.x, o.g, (float *)o.workspace, d.Cin, S4, kK1Chunk4, p.x_bs, p.g_bs);
+    wgrad_k1_small_final<<<ceil_div(d.Cin * d.Cout, 64), 64, 0, o.st>>>((const float *)o.workspace, o.dw, d.Cin, d.Cout, p.slabs);
+    return check_launch("snvc_conv3d_wgrad(k1 small)");
+}
+
+// A split-operand form: its kernel for 16- and for 8-byte rows, and what the plan needs of its configuration
+struct WgradSplit {
+    void (*rows16)(dim3, dim3, size_t, hipStream_t, const X3WgArgs &), (*rows8)(dim3, dim3, size_t, hipStream_t, const X3WgArgs &);
+    int th, threads, lds_bytes, col_slabs;       // rows of a column; partial slabs per column and depth part
+    const char *what, *what_reduce;              // the form's name in the texts of the two launch checks
+};
+constexpr WgradSplit kX3 = {&launch_lds<conv3d_wgrad_x3_kernel<true>, X3WgArgs>, &launch_lds<conv3d_wgrad_x3_kernel<false>, X3WgArgs>,
+                            X3WgCfg::TH, X3WgCfg::THREADS, X3WgCfg::LDS_ALLOC, kX3Slabs,
+                            "snvc_conv3d_wgrad(split operands)", "snvc_conv3d_wgrad(split operands reduce)"};
+constexpr WgradSplit kX3S2 = {&launch_lds<conv3d_wgrad_x3s2_kernel<true>, X3WgArgs>, &launch_lds<conv3d_wgrad_x3s2_kernel<false>, X3WgArgs>,
+                              X3S2WgCfg::TH, X3S2WgCfg::THREADS, X3S2WgCfg::LDS_BYTES, kX3S2Slabs,
+                              "snvc_conv3d_wgrad(split operands, stride 2)", "snvc_conv3d_wgrad(split operands, stride 2, reduce)"};
+
+// Both split-operand forms: where the amax words are, the pass over the tensors whose maximum the caller did not bring, the
+// kernel for 16- or 8-byte rows, the reduce.
+int launch_split(const WgradSplit &f, const snvc_conv3d_desc &d, const WgradPlan &p, const WgradOperands &o) {
+    X3WgArgs b;
+    b.x = o.x; b.g = o.g; b.partial = (float *)o.workspace;
+    b.N = d.N; b.Cx = d.Cin; b.Cg = d.Cout; b.D = d.Dout; b.H = d.Hout; b.W = d.Wout;
+    b.cx_blocks = p.cx_blocks; b.pairs = p.job_pairs; b.pairs32 = p.pairs; b.x_bs = p.x_bs; b.g_bs = p.g_bs;
+    b.hblocks = p.hblocks; b.wsegs = p.wsegs; b.dparts = p.dparts; b.dchunk = p.dchunk; b.njobs = p.njobs;
+    unsigned *amax = reinterpret_cast<unsigned *>(static_cast<char *>(o.workspace) + p.amax_offset);
+    b.amax_x = o.amax_x ? o.amax_x : amax;
+    b.amax_g = o.amax_g ? o.amax_g : amax + SNVC_AMAX_SLOTS;
+    if (!o.amax_x || !o.amax_g) {        // a maximum the caller did not bring: one more pass over that tensor
+        if (hipMemsetAsync(amax, 0, 2 * SNVC_AMAX_SLOTS * 4, o.st) != hipSuccess) return fail(SNVC_ERR_HIP, "snvc_conv3d_wgrad: hipMemsetAsync failed");
+        const int64_t n4x = o.amax_x ? 0 : p.in_sz / 4, n4g = o.amax_g ? 0 : p.out_sz / 4;
+        const unsigned ab = (unsigned)std::min<int64_t>(ceil_div<int64_t>(std::max(n4x, n4g), 256 * 8), 4096);
+        wgrad_amax2_kernel<<<dim3(ab, 2, (unsigned)d.N), 256, 0, o.st>>>(o.x, o.g, amax, n4x, n4g, p.x_bs, p.g_bs);
+    }
+    (p.rows16 ? f.rows16 : f.rows8)(p.grid, p.threads, p.lds_bytes, o.st, b);
+    if (const int rc = check_launch(f.what)) return rc;
+    const int64_t total = (int64_t)p.pairs * 27 * 1024;
+    wgrad_reduce_x3_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, o.st>>>(
+        (const float *)o.workspace, o.dw, d.Cout, d.Cin, p.cx_blocks, p.pairs, p.slabs, b.amax_x, b.amax_g);
+    return check_launch(f.what_reduce);
+}
+
+WgradArgs wgrad_args(const snvc_conv3d_desc &d, const WgradPlan &p, const WgradOperands &o) {
+    WgradArgs a;
+    a.x = o.x; a.g = o.g; a.partial = (float *)o.workspace;
+    a.N = d.N; a.Cx = d.Cin; a.Di = d.Din; a.Hi = d.Hin; a.Wi = d.Win;
+    a.Cg = d.Cout; a.Do = d.Dout; a.Ho = d.Hout; a.Wo = d.Wout;
+    a.tiles_h = p.tiles_h; a.tiles_w = p.tiles_w; a.ntiles = p.ntiles;
+    a.P = p.P; a.cx_blocks = p.cx_blocks; a.x_bs = p.x_bs; a.g_bs = p.g_bs;
+    a.vec = p.vec; a.pairs = p.pairs; a.upx = p.upx;
+    return a;
+}
+
+int launch_units(const snvc_conv3d_desc &d, const WgradPlan &p, const WgradOperands &o) {
+    const WgradArgs a = wgrad_args(d, p, o);
+    const float *partial = (const float *)o.workspace;
+    if (p.form == SNVC_WG_WINO) {
+        launch_lds<conv3d_wgrad_wino_kernel>(p.grid, p.threads, p.lds_bytes, o.st, a);
+        if (const int rc = check_launch("snvc_conv3d_wgrad(winograd)")) return rc;
+        const int64_t total = (int64_t)p.pairs * 9 * 1024;
+        wgrad_wino_reduce_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, o.st>>>(partial, o.dw, d.Cout, d.Cin, p.cx_blocks,
+                                                                                                   p.pairs, p.slabs);
+        return check_launch("snvc_conv3d_wgrad(winograd reduce)");
+    }
+    if (p.vec == 4) launch_lds<conv3d_wgrad_s2_kernel<4>>(p.grid, p.threads, p.lds_bytes, o.st, a);
+    else launch_lds<conv3d_wgrad_s2_kernel<2>>(p.grid, p.threads, p.lds_bytes, o.st, a);
+    if (const int rc = check_launch("snvc_conv3d_wgrad(stride 2)")) return rc;
+    const int64_t total = (int64_t)p.pairs * 27 * 1024;
+    wgrad_reduce_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, o.st>>>(partial, o.dw, d.Cout, d.Cin, 27, 27, p.cx_blocks,
+                                                                                          p.pairs, p.slabs);
+    return check_launch("snvc_conv3d_wgrad(stride 2 reduce)");
+}
+
+// One generic configuration: its launcher and what the plan needs of WgradCfg
+struct WgradGeneric {
+    void (*launch)(const WgradArgs &, dim3, hipStream_t);    // nullptr: the key has no such form
+    int th, chunks, lds_bytes;
+};
+template <class C>
+constexpr WgradGeneric generic_of() { return {&launch_wgrad<C>, C::TH, C::CH_D * C::CH_H, C::LDS_FLOATS * 4}; }
+
+// (key, K-split configuration, tap-split configuration).  K-split: float4- / float2-staged, register-prefetched, for the 3x3x3 keys
+// when the rows are 16- or 8-byte aligned (stride 2: one output row per tile keeps it inside 256 VGPRs).
+struct WgradKey {
+    int key;
+    WgradGeneric ksplit, taps;
+};
+constexpr WgradKey kWgradKeys[] = {  //        KS S  D  TH KDG KHG
+    {111, {}, generic_of<WgradCfg<1, 1, 1, 2, 1, 1>>()},
+    {311, generic_of<WgradCfg<3, 1, 1, 2, 1, 3, true>>(), generic_of<WgradCfg<3, 1, 1, 2, 3, 3>>()},
+    {321, generic_of<WgradCfg<3, 2, 1, 1, 1, 3, true>>(), generic_of<WgradCfg<3, 2, 1, 1, 3, 3>>()},
+    {511, {}, generic_of<WgradCfg<5, 1, 1, 2, 1, 5>>()},
+    {512, {}, generic_of<WgradCfg<5, 1, 2, 2, 1, 5>>()},
+    {711, {}, generic_of<WgradCfg<7, 1, 1, 2, 1, 4>>()},
+};
+
+int launch_generic(const snvc_conv3d_desc &d, const WgradPlan &p, const WgradOperands &o) {
+    p.generic->launch(wgrad_args(d, p, o), p.grid, o.st);
+    if (const int rc = check_launch("snvc_conv3d_wgrad")) return rc;
+    const int taps = d.ksize * d.ksize * d.ksize;
+    const int64_t total = (int64_t)p.pairs * taps * 1024;
+    wgrad_reduce_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, o.st>>>((const float *)o.workspace, o.dw, d.Cout, d.Cin, taps,
+                                                                                          taps, p.cx_blocks, p.pairs, p.slabs);
+    return check_launch("snvc_conv3d_wgrad(reduce)");
+}
+
+// ------------------------------------------------------------------ the plan
+// Spatial partitions and units per XCD of the two 12-wave forms: one workgroup per CU and (pair, partition, kd) unit, one round
+void wgrad_units(int pairs, int cap, int cus, int &P, int &upx) {
+    upx = cus / 8 / 3;
+    if (upx < 1) upx = 1;
+    P = 8 * upx / pairs;
+    if (P < 1) P = 1;           // more pairs than units: the units take several rounds
+    if (P > cap) P = cap;
+    if (P * pairs > 8 * upx) upx = ceil_div(P * pairs, 8);
+}
+
+// Slabs per channel pair the workspace holds.  Which of a key's forms runs depends on the operands' alignment, known only at launch,
+// so this is the largest of the key's candidates -- each with the partition count its launch really uses (r1-r2 reserved 512
+// partitions for every form: 6x too much for the 12-wave forms).
+int64_t wgrad_slab_budget(const snvc_conv3d_desc &d, int64_t pairs, int cus) {
+    int64_t slabs = (int64_t)kWgradPartitions * d.ksize * d.ksize * d.ksize;       // generic forms; the split-operand ones stay inside
+    if (pairs <= 65535 && d.ksize == 3 && d.dilation == 1 && (d.stride == 1 || d.stride == 2)) {
+        int P, upx;
+        wgrad_units((int)pairs, d.stride == 1 ? kWgradPartitions / 2 : kWgradPartitions / 4, cus, P, upx);
+        slabs = std::max(slabs, (int64_t)P * (d.stride == 1 ? kWinoSlabs : kS2Slabs));
+    }
+    return slabs;
+}
+
+// The descriptor checks of snvc_conv3d_wgrad_amax that come before its pointer check
+int wgrad_desc_checks(const snvc_conv3d_desc *d) {
+    if (!d) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: null desc");
+    if (d->transposed) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: describe the equivalent strided convolution (see header)");
+    if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: sizes must be positive");
+    if (d->pad != d->dilation * (d->ksize - 1) / 2) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_wgrad: pad must equal dilation*(ksize-1)/2");
+    const int eff = d->dilation * (d->ksize - 1) + 1;
+    if (d->Dout != (d->Din + 2 * d->pad - eff) / d->stride + 1 || d->Hout != (d->Hin + 2 * d->pad - eff) / d->stride + 1 ||
+        d->Wout != (d->Win + 2 * d->pad - eff) / d->stride + 1)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: output size does not match the convolution arithmetic");
+    return SNVC_OK;
+}
+
+// Split-operand forms: one workgroup per (column of th x 32 voxels, depth part, channel pair of the job list).  Depth parts: enough
+// jobs for every CU once, parts at least 8 planes long, and no more slabs than 3x3x3's generic forms write.  False: the layer does
+// not fit (too many columns for the slabs, or for the 24-bit job counter) and takes the key's next form.
+bool plan_split(const snvc_conv3d_desc &d, const WgradSplit &f, int job_pairs, int64_t budget, int cus, WgradPlan &p) {
+    const int hblocks = ceil_div(d.Hout, f.th), wsegs = ceil_div(d.Wout, 32);
+    const int64_t cols = (int64_t)d.N * hblocks * wsegs, max_cols = (int64_t)kWgradPartitions * 27 / f.col_slabs;
+    int dparts = 1;
+    while (cols * dparts * job_pairs < cus * 3 / 4 && d.Dout / (dparts * 2) >= 8 && cols * dparts * 2 <= max_cols) dparts *= 2;
+    if (cols * dparts > max_cols || cols * dparts * job_pairs >= ((int64_t)1 << 24) || cols * dparts * f.col_slabs > budget) return false;
+    p.hblocks = hblocks; p.wsegs = wsegs; p.job_pairs = job_pairs;
+    p.dchunk = ceil_div(d.Dout, dparts);
+    p.dparts = ceil_div(d.Dout, p.dchunk);
+    p.njobs = (int)(cols * p.dparts * job_pairs);
+    p.grid = dim3((unsigned)(8 * ceil_div(p.njobs, 8)));
+    p.threads = f.threads;
+    p.lds_bytes = f.lds_bytes;
+    p.rows16 = p.vec == 4;
+    p.piece_bytes = p.rows16 ? 16 : 8;
+    p.slabs = (int)(cols * p.dparts * (f.col_slabs / 27));
+    p.amax_offset = budget * p.pairs * kSlabBytes;
+    p.ws_bytes = p.amax_offset + kAmaxBytes;
+    return true;
+}
+
+// 12-wave forms: one workgroup per CU, one round: upx (pair, partition) units x 3 depth slices on each of the 8 XCDs; tiles of
+// th x 32 voxels on a 32-bit counter.  `parts` slabs of `part_slabs / parts` taps per partition.
+static_assert(WinoWgradCfg::THREADS == S2WgradCfg::THREADS, "twelve waves");
+bool plan_units(const snvc_conv3d_desc &d, int th, int parts, int part_slabs, int cus, WgradPlan &p) {
+    const int64_t tiles = (int64_t)d.N * d.Dout * ceil_div(d.Hout, th) * p.tiles_w;
+    if (tiles >= ((int64_t)1 << 30)) return false;
+    p.tiles_h = ceil_div(d.Hout, th);
+    p.ntiles = tiles;
+    wgrad_units(p.pairs, kWgradPartitions / parts, cus, p.P, p.upx);
+    p.grid = dim3((unsigned)(8 * p.upx * 3));
+    p.threads = WinoWgradCfg::THREADS;
+    p.piece_bytes = 4 * p.vec;
+    p.slabs = parts * p.P;
+    p.ws_bytes = (int64_t)p.P * part_slabs * p.pairs * kSlabBytes;
+    return true;
+}
+
+// x_align / g_align: the largest of 16 / 8 / 4 that divides the operand's address.  Launches nothing, reads no pointer; `cus` is its
+// only input from the environment.  The forms in their order of precedence: include/snvc_forms.h.
+int plan_wgrad(const snvc_conv3d_desc *desc, int x_align, int g_align, int cus, WgradPlan &p) {
+    if (const int rc = wgrad_desc_checks(desc)) return rc;
+    const snvc_conv3d_desc &d = *desc;
+    p = WgradPlan{};
+    p.in_sz = (int64_t)d.Cin * d.Din * d.Hin * d.Win;
+    p.out_sz = (int64_t)d.Cout * d.Dout * d.Hout * d.Wout;
+    if (p.in_sz >= ((int64_t)1 << 31) || p.out_sz >= ((int64_t)1 << 31))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_wgrad: one sample must stay below 2^31 elements");
+    p.tiles_w = ceil_div(d.Wout, 32);
+    p.cx_blocks = ceil_div(d.Cin, 32);
+    p.x_bs = d.x_batch_stride ? d.x_batch_stride : p.in_sz;
+    p.g_bs = d.y_batch_stride ? d.y_batch_stride : p.out_sz;
+    const bool scalar = d.algo & SNVC_ALGO_SCALAR_STAGING, fp32 = d.algo & SNVC_ALGO_WGRAD_FP32;
+    const bool direct = (d.algo & SNVC_ALGO_ARITH_MASK) == SNVC_ALGO_DIRECT;
+    // float4 staging of X needs 16-byte rows on the big grid; G rows may be 16- or 8-byte ones (the W = 78 level of the
+    // cfg2 hourglass: its two layers took the scalar path at 1.0 ms each)
+    const bool xv = d.Win % 4 == 0 && p.x_bs % 4 == 0 && x_align >= 16 && !scalar;
+    const bool g4 = d.Wout % 4 == 0 && p.g_bs % 4 == 0 && g_align >= 16;
+    const bool g2 = d.Wout % 2 == 0 && p.g_bs % 2 == 0 && g_align >= 8;
+    p.vec = xv ? (g4 ? 4 : (g2 ? 2 : 0)) : 0;
+    p.pairs = ceil_div(d.Cout, 32) * p.cx_blocks;
+    if (p.pairs > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_wgrad: too many channel pairs");
+    const int64_t budget = wgrad_slab_budget(d, p.pairs, cus);
+    const bool both16 = x_align >= 16 && g_align >= 16;
+
+    // 1x1x1 to <= 2 channels: streaming dot products (see wgrad_k1_small_partial), four input channels per workgroup
+    const int64_t S = (int64_t)d.Dout * d.Hout * d.Wout;
+    p.chunks = ceil_div<int64_t>(S / 4, kK1Chunk4);
+    p.ws_bytes = p.chunks * d.N * d.Cin * d.Cout * 4;
+    if (d.ksize == 1 && d.stride == 1 && d.Cout <= 2 && S % 4 == 0 && p.x_bs % 4 == 0 && p.g_bs % 4 == 0 && both16 && d.Cin <= 65535 &&
+        d.N <= 65535 && p.ws_bytes <= budget * p.pairs * kSlabBytes + kAmaxBytes) {
+        p.form = SNVC_WG_K1_STREAM;
+        p.grid = dim3((unsigned)p.chunks, (unsigned)ceil_div(d.Cin, 4), (unsigned)d.N);
+        p.threads = 256;
+        p.piece_bytes = 16;
+        p.slabs = (int)(p.chunks * d.N);
+        return SNVC_OK;
+    }
+    p.chunks = 0;
+
+    const int key = d.ksize * 100 + d.stride * 10 + d.dilation;
+    // rows of the split-operand forms: 16-byte aligned, or 8-byte (W % 4 == 2: float2 pieces)
+    const bool x8 = d.Win % 2 == 0 && p.x_bs % 2 == 0 && x_align >= 8 && !scalar;
+    // (their own amax pass reads the tensors as flat float4 streams)
+    const bool flat16 = p.in_sz % 4 == 0 && p.out_sz % 4 == 0 && p.x_bs % 4 == 0 && p.g_bs % 4 == 0 && both16;
+    const bool halves = p.vec == 4 || p.vec == 2;
+    if (key == 311 && flat16 && (p.vec == 4 || (x8 && g2)) && !fp32 && !direct &&
+        plan_split(d, kX3, p.pairs, budget, cus, p)) {
+        p.form = SNVC_WG_X3;                    // split operands (f16x3), see conv3d_wgrad_x3_kernel
+    } else if (key == 311 && p.vec == 4 && !direct && plan_units(d, WinoWgradCfg::TH, 2, kWinoSlabs, cus, p)) {
+        p.form = SNVC_WG_WINO;                  // Winograd domain (see conv3d_wgrad_wino_kernel): half the MFMAs of the direct form
+        p.lds_bytes = WinoWgradCfg::LDS_FLOATS * 4;
+    } else if (key == 321 && flat16 && halves && !fp32 && !direct && d.Din == 2 * d.Dout && d.Hin == 2 * d.Hout && d.Win == 2 * d.Wout &&
+               plan_split(d, kX3S2, ceil_div(d.Cout, 64) * p.cx_blocks, budget, cus, p)) {
+        p.form = SNVC_WG_X3S2;                  // split operands, stride 2, see conv3d_wgrad_x3s2_kernel: jobs take 64 g channels
+    } else if (key == 321 && flat16 && halves && !direct && plan_units(d, S2WgradCfg::TH, 4, kS2Slabs, cus, p)) {
+        p.form = SNVC_WG_S2;                    // 12 waves, stride 2 (see conv3d_wgrad_s2_kernel); DIRECT keeps the generic forms
+        p.lds_bytes = S2WgradCfg::LDS_FLOATS * 4;
+    } else {
+        const WgradKey *k = std::find_if(std::begin(kWgradKeys), std::end(kWgradKeys), [key](const WgradKey &e) { return e.key == key; });
+        if (k == std::end(kWgradKeys))
+            return fail(SNVC_ERR_UNSUPPORTED,
+                        "snvc_conv3d_wgrad: (ksize,stride,dilation) not in {(1,1,1),(3,1,1),(3,2,1),(5,1,1),(5,1,2),(7,1,1)}");
+        const bool ksplit = p.vec && k->ksplit.launch;
+        p.form = ksplit ? SNVC_WG_KSPLIT : SNVC_WG_TAPS;
+        p.generic = ksplit ? &k->ksplit : &k->taps;
+        p.piece_bytes = ksplit ? 4 * p.vec : 4;
+        p.tiles_h = ceil_div(d.Hout, p.generic->th);
+        p.ntiles = (int64_t)d.N * d.Dout * p.tiles_h * p.tiles_w;
+        p.P = p.slabs = kWgradPartitions;
+        p.grid = dim3(kWgradPartitions, (unsigned)p.pairs, (unsigned)p.generic->chunks);
+        p.threads = 256;
+        p.lds_bytes = p.generic->lds_bytes;
+        p.ws_bytes = (int64_t)kWgradPartitions * d.ksize * d.ksize * d.ksize * p.pairs * kSlabBytes;
+    }
+    return SNVC_OK;
+}
+
+inline int address_align(const void *ptr) {
+    const uintptr_t v = reinterpret_cast<uintptr_t>(ptr);
+    return v % 16 == 0 ? 16 : (v % 8 == 0 ? 8 : 4);
+}
 
 }  // namespace
 }  // namespace snvc
 
 extern "C" {
 
-// Spatial partitions and units per XCD of the two 12-wave forms: one workgroup per CU and (pair, partition, kd) unit, one round
-static void wgrad_units(int pairs, int cap, int &P, int &upx) {
-    upx = snvc::device_cu_count() / 8 / 3;
-    if (upx < 1) upx = 1;
-    P = 8 * upx / pairs;
-    if (P < 1) P = 1;           // more pairs than units: the units take several rounds
-    if (P > cap) P = cap;
-    if (P * pairs > 8 * upx) upx = snvc::ceil_div(P * pairs, 8);
-}
-
-// Partial slabs [partitions][pairs][taps][32][32] of the form the layer takes; which of a key's forms runs depends on the
-// operands' alignment, known only at launch, so the size is the largest of the key's candidates -- each with the partition
-// count its launch really uses (r1-r2 reserved 512 partitions for every form: 6x too much for the 12-wave forms).
 int64_t snvc_conv3d_wgrad_workspace_bytes(const snvc_conv3d_desc *d) {
     using namespace snvc;
     if (!d || d->Cin <= 0 || d->Cout <= 0) return -1;
-    const int64_t taps = (int64_t)d->ksize * d->ksize * d->ksize;
     const int64_t pairs = (int64_t)ceil_div(d->Cout, 32) * ceil_div(d->Cin, 32);
-    int64_t slabs = (int64_t)kWgradPartitions * taps;                        // tap-split / K-split forms
-    if (pairs <= 65535) {
-        int P, upx;
-        if (d->ksize == 3 && d->stride == 1 && d->dilation == 1) {            // Winograd-domain form: 2P row-half slabs x 54
-            wgrad_units((int)pairs, kWgradPartitions / 2, P, upx);
-            if ((int64_t)2 * P * 54 > slabs) slabs = (int64_t)2 * P * 54;
-        } else if (d->ksize == 3 && d->stride == 2 && d->dilation == 1) {     // stride-2 form: 4P slabs x 27
-            wgrad_units((int)pairs, kWgradPartitions / 4, P, upx);
-            if ((int64_t)4 * P * 27 > slabs) slabs = (int64_t)4 * P * 27;
-        }
-    }
-    return slabs * pairs * 1024 * (int64_t)sizeof(float) + 1024;     // + the two amax words of the split-operand form (r6), at the end
+    return wgrad_slab_budget(*d, pairs, device_cu_count()) * pairs * kSlabBytes + kAmaxBytes;
 }
 
 // desc describes the FORWARD Conv3d (x = its input on the big grid, g = gradient of its output on
@@ -1488,207 +1786,40 @@ int snvc_conv3d_wgrad(const snvc_conv3d_desc *d, const float *x, const float *g,
 int snvc_conv3d_wgrad_amax(const snvc_conv3d_desc *d, const float *x, const float *g, float *dw, void *workspace,
                            const uint32_t *amax_x, const uint32_t *amax_g, void *stream) {
     using namespace snvc;
-    if (!d) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: null desc");
-    if (d->transposed) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: describe the equivalent strided convolution (see header)");
-    if (d->N <= 0 || d->Cin <= 0 || d->Cout <= 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: sizes must be positive");
-    if (d->pad != d->dilation * (d->ksize - 1) / 2) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_wgrad: pad must equal dilation*(ksize-1)/2");
-    const int eff = d->dilation * (d->ksize - 1) + 1;
-    if (d->Dout != (d->Din + 2 * d->pad - eff) / d->stride + 1 || d->Hout != (d->Hin + 2 * d->pad - eff) / d->stride + 1 ||
-        d->Wout != (d->Win + 2 * d->pad - eff) / d->stride + 1)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: output size does not match the convolution arithmetic");
+    // (the plan runs these checks again: the pointer check stands between them and the plan's further refusals, in that order)
+    if (const int rc = wgrad_desc_checks(d)) return rc;
     if (!x || !g || !dw || !workspace) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad: null pointer");
-    const int64_t in_sz = (int64_t)d->Cin * d->Din * d->Hin * d->Win, out_sz = (int64_t)d->Cout * d->Dout * d->Hout * d->Wout;
-    if (in_sz >= ((int64_t)1 << 31) || out_sz >= ((int64_t)1 << 31))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_wgrad: one sample must stay below 2^31 elements");
+    WgradPlan p;
+    if (const int rc = plan_wgrad(d, address_align(x), address_align(g), device_cu_count(), p)) return rc;
+    const WgradOperands o{x, g, dw, workspace, amax_x, amax_g, as_stream(stream)};
+    switch (p.form) {
+        case SNVC_WG_K1_STREAM: return launch_k1_stream(*d, p, o);
+        case SNVC_WG_X3: return launch_split(kX3, *d, p, o);
+        case SNVC_WG_X3S2: return launch_split(kX3S2, *d, p, o);
+        case SNVC_WG_WINO:
+        case SNVC_WG_S2: return launch_units(*d, p, o);
+        default: return launch_generic(*d, p, o);
+    }
+}
 
-    WgradArgs a;
-    a.x = x; a.g = g; a.partial = (float *)workspace;
-    a.N = d->N; a.Cx = d->Cin; a.Di = d->Din; a.Hi = d->Hin; a.Wi = d->Win;
-    a.Cg = d->Cout; a.Do = d->Dout; a.Ho = d->Hout; a.Wo = d->Wout;
-    const int th = d->stride == 1 ? 2 : 1;   // rows per tile (see the WgradCfg instantiations below)
-    a.tiles_h = ceil_div(d->Hout, th); a.tiles_w = ceil_div(d->Wout, 32);
-    a.ntiles = (int64_t)d->N * d->Dout * a.tiles_h * a.tiles_w;
-    a.P = kWgradPartitions;
-    a.cx_blocks = ceil_div(d->Cin, 32);
-    a.x_bs = d->x_batch_stride ? d->x_batch_stride : in_sz;
-    a.g_bs = d->y_batch_stride ? d->y_batch_stride : out_sz;
-    // float4 staging of X needs 16-byte rows on the big grid; G rows may be 16- or 8-byte ones (the W = 78 level of the
-    // cfg2 hourglass: its two layers took the scalar path at 1.0 ms each)
-    const bool xv = d->Win % 4 == 0 && a.x_bs % 4 == 0 && (reinterpret_cast<uintptr_t>(x) & 15) == 0 &&
-                    !(d->algo & SNVC_ALGO_SCALAR_STAGING);
-    const bool g4 = d->Wout % 4 == 0 && a.g_bs % 4 == 0 && (reinterpret_cast<uintptr_t>(g) & 15) == 0;
-    const bool g2 = d->Wout % 2 == 0 && a.g_bs % 2 == 0 && (reinterpret_cast<uintptr_t>(g) & 7) == 0;
-    a.vec = xv ? (g4 ? 4 : (g2 ? 2 : 0)) : 0;
-    const int pairs = ceil_div(d->Cout, 32) * a.cx_blocks;
-    if (pairs > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_wgrad: too many channel pairs");
-    hipStream_t st = as_stream(stream);
-    {   // 1x1x1 to <= 2 channels: streaming dot products (see wgrad_k1_small_partial)
-        const int64_t S = (int64_t)d->Dout * d->Hout * d->Wout;
-        const int64_t chunk4 = 16384;                                 // 64k voxels per workgroup (x four channels, r6; 8192 measured slower)
-        const int64_t chunks = ceil_div<int64_t>(S / 4, chunk4);
-        if (d->ksize == 1 && d->stride == 1 && d->Cout <= 2 && S % 4 == 0 && a.x_bs % 4 == 0 && a.g_bs % 4 == 0 &&
-            ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15) == 0 && d->Cin <= 65535 && d->N <= 65535 &&
-            chunks * d->N * d->Cin * d->Cout * 4 <= snvc_conv3d_wgrad_workspace_bytes(d)) {
-            dim3 grid((unsigned)chunks, (unsigned)ceil_div(d->Cin, 4), (unsigned)d->N);       // four input channels per workgroup
-            if (d->Cout == 1)
-                wgrad_k1_small_partial<1><<<grid, 256, 0, st>>>(x, g, (float *)workspace, d->Cin, S / 4, chunk4, a.x_bs, a.g_bs);
-            else
-                wgrad_k1_small_partial<2><<<grid, 256, 0, st>>>(x, g, (float *)workspace, d->Cin, S / 4, chunk4, a.x_bs, a.g_bs);
-            wgrad_k1_small_final<<<ceil_div(d->Cin * d->Cout, 64), 64, 0, st>>>((const float *)workspace, dw, d->Cin, d->Cout,
-                                                                               chunks * d->N);
-            return check_launch("snvc_conv3d_wgrad(k1 small)");
-        }
-    }
-    const int key = d->ksize * 100 + d->stride * 10 + d->dilation;
-    // rows of the split-operand forms: 16-byte aligned, or 8-byte (W % 4 == 2: float2 pieces)
-    const bool x8 = d->Win % 2 == 0 && a.x_bs % 2 == 0 && (reinterpret_cast<uintptr_t>(x) & 7) == 0 && !(d->algo & SNVC_ALGO_SCALAR_STAGING);
-    // (their own amax pass reads the tensors as flat float4 streams)
-    const bool flat16 = in_sz % 4 == 0 && out_sz % 4 == 0 && a.x_bs % 4 == 0 && a.g_bs % 4 == 0 &&
-                        ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(g)) & 15) == 0;
-    if (key == 311 && flat16 && (a.vec == 4 || (x8 && g2)) && !(d->algo & SNVC_ALGO_WGRAD_FP32) && (d->algo & SNVC_ALGO_ARITH_MASK) != SNVC_ALGO_DIRECT) {
-        // split-operand (f16x3) form, see conv3d_wgrad_x3_kernel: one workgroup per (column of 4 x 32 voxels, depth part, channel pair)
-        X3WgArgs b;
-        b.x = x; b.g = g; b.partial = (float *)workspace;
-        b.N = d->N; b.Cx = d->Cin; b.Cg = d->Cout; b.D = d->Dout; b.H = d->Hout; b.W = d->Wout;
-        b.cx_blocks = a.cx_blocks; b.pairs = pairs; b.pairs32 = pairs; b.x_bs = a.x_bs; b.g_bs = a.g_bs;
-        b.hblocks = ceil_div(d->Hout, X3WgCfg::TH); b.wsegs = ceil_div(d->Wout, 32);
-        const int64_t cols = (int64_t)d->N * b.hblocks * b.wsegs;
-        // depth parts: enough jobs for every CU once, columns at least 8 planes long, at most 256 columns x parts (512 slabs, the
-        // workspace's size)
-        int dparts = 1;
-        while (cols * dparts * pairs < device_cu_count() * 3 / 4 && d->Dout / (dparts * 2) >= 8 && cols * dparts * 2 <= 256) dparts *= 2;
-        const int64_t slabs_bytes = snvc_conv3d_wgrad_workspace_bytes(d) - 1024;
-        if (cols * dparts <= 256 && cols * dparts * pairs < ((int64_t)1 << 24) &&
-            (int64_t)2 * cols * dparts * pairs * 27 * 1024 * 4 <= slabs_bytes) {
-            b.dparts = dparts; b.dchunk = ceil_div(d->Dout, dparts);
-            b.dparts = ceil_div(d->Dout, b.dchunk);
-            b.njobs = (int)(cols * b.dparts * pairs);
-            unsigned *amax = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + slabs_bytes);
-            b.amax_x = amax_x ? amax_x : amax;
-            b.amax_g = amax_g ? amax_g : amax + SNVC_AMAX_SLOTS;
-            if (!amax_x || !amax_g) {        // a maximum the caller did not bring: one more pass over that tensor
-                if (hipMemsetAsync(amax, 0, 2 * SNVC_AMAX_SLOTS * 4, st) != hipSuccess) return fail(SNVC_ERR_HIP, "snvc_conv3d_wgrad: hipMemsetAsync failed");
-                const int64_t n4x = amax_x ? 0 : in_sz / 4, n4g = amax_g ? 0 : out_sz / 4;
-                const unsigned ab = (unsigned)std::min<int64_t>(ceil_div<int64_t>(std::max(n4x, n4g), 256 * 8), 4096);
-                wgrad_amax2_kernel<<<dim3(ab, 2, (unsigned)d->N), 256, 0, st>>>(x, g, amax, n4x, n4g, a.x_bs, a.g_bs);
-            }
-            const unsigned nwg = (unsigned)(8 * ceil_div(b.njobs, 8));
-            if (a.vec == 4) launch_lds<conv3d_wgrad_x3_kernel<true>>(dim3(nwg), X3WgCfg::THREADS, X3WgCfg::LDS_ALLOC, st, b);
-            else launch_lds<conv3d_wgrad_x3_kernel<false>>(dim3(nwg), X3WgCfg::THREADS, X3WgCfg::LDS_ALLOC, st, b);
-            int rcx = check_launch("snvc_conv3d_wgrad(split operands)");
-            if (rcx) return rcx;
-            const int64_t total = (int64_t)pairs * 27 * 1024;
-            wgrad_reduce_x3_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, st>>>(
-                (const float *)workspace, dw, d->Cout, d->Cin, a.cx_blocks, pairs, (int)(2 * cols * b.dparts), b.amax_x, b.amax_g);
-            return check_launch("snvc_conv3d_wgrad(split operands reduce)");
-        }
-    }
-    const int64_t wino_tiles = (int64_t)d->N * d->Dout * ceil_div(d->Hout, WinoWgradCfg::TH) * a.tiles_w;   // 32-bit tile counter
-    if (key == 311 && a.vec == 4 && wino_tiles < ((int64_t)1 << 30) && (d->algo & SNVC_ALGO_ARITH_MASK) != SNVC_ALGO_DIRECT) {
-        // Winograd-domain form (see conv3d_wgrad_wino_kernel): half the MFMAs of the direct form
-        a.tiles_h = ceil_div(d->Hout, WinoWgradCfg::TH);
-        a.ntiles = (int64_t)d->N * d->Dout * a.tiles_h * a.tiles_w;
-        // one 12-wave workgroup per CU, one round: upx (pair, partition) units x 3 depth slices on each of the 8 XCDs
-        wgrad_units(pairs, kWgradPartitions / 2, a.P, a.upx);
-        a.pairs = pairs;
-        const unsigned nwg = (unsigned)(8 * a.upx * 3);
-        launch_lds<conv3d_wgrad_wino_kernel>(dim3(nwg), WinoWgradCfg::THREADS, WinoWgradCfg::LDS_FLOATS * 4, st, a);
-        int rcw = check_launch("snvc_conv3d_wgrad(winograd)");
-        if (rcw) return rcw;
-        const int64_t total = (int64_t)pairs * 9 * 1024;
-        wgrad_wino_reduce_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, st>>>((const float *)workspace, dw, d->Cout,
-                                                                                                 d->Cin, a.cx_blocks, pairs, 2 * a.P);
-        return check_launch("snvc_conv3d_wgrad(winograd reduce)");
-    }
-    if (key == 321 && flat16 && (a.vec == 4 || a.vec == 2) && !(d->algo & SNVC_ALGO_WGRAD_FP32) && (d->algo & SNVC_ALGO_ARITH_MASK) != SNVC_ALGO_DIRECT &&
-        d->Din == 2 * d->Dout && d->Hin == 2 * d->Hout && d->Win == 2 * d->Wout) {
-        // split-operand (f16x3) form of the stride-2 layers, see conv3d_wgrad_x3s2_kernel
-        X3WgArgs b;
-        b.x = x; b.g = g; b.partial = (float *)workspace;
-        b.N = d->N; b.Cx = d->Cin; b.Cg = d->Cout; b.D = d->Dout; b.H = d->Hout; b.W = d->Wout;
-        b.cx_blocks = a.cx_blocks; b.pairs32 = pairs; b.pairs = ceil_div(d->Cout, 64) * a.cx_blocks; b.x_bs = a.x_bs; b.g_bs = a.g_bs;
-        b.hblocks = ceil_div(d->Hout, X3S2WgCfg::TH); b.wsegs = ceil_div(d->Wout, 32);
-        const int64_t cols = (int64_t)d->N * b.hblocks * b.wsegs;
-        int dparts = 1;
-        while (cols * dparts * b.pairs < device_cu_count() * 3 / 4 && d->Dout / (dparts * 2) >= 8 && cols * dparts * 2 <= 512) dparts *= 2;
-        const int64_t slabs_bytes = snvc_conv3d_wgrad_workspace_bytes(d) - 1024;
-        if (cols * dparts <= 512 && cols * dparts * b.pairs < ((int64_t)1 << 24) &&
-            cols * dparts * pairs * 27 * 1024 * 4 <= slabs_bytes) {
-            b.dchunk = ceil_div(d->Dout, dparts);
-            b.dparts = ceil_div(d->Dout, b.dchunk);
-            b.njobs = (int)(cols * b.dparts * b.pairs);
-            unsigned *amax = reinterpret_cast<unsigned *>(static_cast<char *>(workspace) + slabs_bytes);
-            b.amax_x = amax_x ? amax_x : amax;
-            b.amax_g = amax_g ? amax_g : amax + SNVC_AMAX_SLOTS;
-            if (!amax_x || !amax_g) {
-                if (hipMemsetAsync(amax, 0, 2 * SNVC_AMAX_SLOTS * 4, st) != hipSuccess) return fail(SNVC_ERR_HIP, "snvc_conv3d_wgrad: hipMemsetAsync failed");
-                const int64_t n4x = amax_x ? 0 : in_sz / 4, n4g = amax_g ? 0 : out_sz / 4;
-                const unsigned ab = (unsigned)std::min<int64_t>(ceil_div<int64_t>(std::max(n4x, n4g), 256 * 8), 4096);
-                wgrad_amax2_kernel<<<dim3(ab, 2, (unsigned)d->N), 256, 0, st>>>(x, g, amax, n4x, n4g, a.x_bs, a.g_bs);
-            }
-            const unsigned nwg = (unsigned)(8 * ceil_div(b.njobs, 8));
-            if (a.vec == 4) launch_lds<conv3d_wgrad_x3s2_kernel<true>>(dim3(nwg), X3S2WgCfg::THREADS, X3S2WgCfg::LDS_BYTES, st, b);
-            else launch_lds<conv3d_wgrad_x3s2_kernel<false>>(dim3(nwg), X3S2WgCfg::THREADS, X3S2WgCfg::LDS_BYTES, st, b);
-            int rcx = check_launch("snvc_conv3d_wgrad(split operands, stride 2)");
-            if (rcx) return rcx;
-            const int64_t total = (int64_t)pairs * 27 * 1024;
-            wgrad_reduce_x3_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, st>>>(
-                (const float *)workspace, dw, d->Cout, d->Cin, a.cx_blocks, pairs, (int)(cols * b.dparts), b.amax_x, b.amax_g);
-            return check_launch("snvc_conv3d_wgrad(split operands, stride 2, reduce)");
-        }
-    }
-    const int64_t s2_tiles = (int64_t)d->N * d->Dout * ceil_div(d->Hout, S2WgradCfg::TH) * a.tiles_w;
-    if (key == 321 && flat16 && (a.vec == 4 || a.vec == 2) && s2_tiles < ((int64_t)1 << 30) &&
-        (d->algo & SNVC_ALGO_ARITH_MASK) != SNVC_ALGO_DIRECT) {
-        // 12-wave form (see conv3d_wgrad_s2_kernel); SNVC_ALGO_DIRECT keeps the tap-split kernel below
-        a.tiles_h = ceil_div(d->Hout, S2WgradCfg::TH);
-        a.ntiles = s2_tiles;
-        wgrad_units(pairs, kWgradPartitions / 4, a.P, a.upx);
-        a.pairs = pairs;
-        const unsigned nwg = (unsigned)(8 * a.upx * 3);
-        constexpr int bytes = S2WgradCfg::LDS_FLOATS * 4;
-        if (a.vec == 4) launch_lds<conv3d_wgrad_s2_kernel<4>>(dim3(nwg), S2WgradCfg::THREADS, bytes, st, a);
-        else launch_lds<conv3d_wgrad_s2_kernel<2>>(dim3(nwg), S2WgradCfg::THREADS, bytes, st, a);
-        int rcs = check_launch("snvc_conv3d_wgrad(stride 2)");
-        if (rcs) return rcs;
-        const int64_t total = (int64_t)pairs * 27 * 1024;
-        wgrad_reduce_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, st>>>((const float *)workspace, dw, d->Cout, d->Cin, 27,
-                                                                                            27, a.cx_blocks, pairs, 4 * a.P);
-        return check_launch("snvc_conv3d_wgrad(stride 2 reduce)");
-    }
-#define SNVC_WGRAD_CASE(CFG)                                                                  \
-    {                                                                                         \
-        using C_ = CFG;                                                                       \
-        a.tiles_h = ceil_div(d->Hout, C_::TH);                                                \
-        a.ntiles = (int64_t)d->N * d->Dout * a.tiles_h * a.tiles_w;                           \
-        dim3 grid(kWgradPartitions, (unsigned)pairs, (unsigned)(C_::CH_D * C_::CH_H));        \
-        launch_wgrad<C_>(a, grid, st);                                                        \
-    }
-    switch (key) {  //                            KS S  D  TH KDG KHG
-        case 111: SNVC_WGRAD_CASE(SNVC_CFG(1, 1, 1, 2, 1, 1)) break;
-        case 311:   // float4-staged, register-prefetched, K-split form when the rows are 16-byte aligned
-            if (a.vec) SNVC_WGRAD_CASE(SNVC_CFG(3, 1, 1, 2, 1, 3, true))
-            else SNVC_WGRAD_CASE(SNVC_CFG(3, 1, 1, 2, 3, 3))
-            break;
-        case 321:   // same form for the stride-2 layers (one output row per tile keeps it inside 256 VGPRs)
-            if (a.vec) SNVC_WGRAD_CASE(SNVC_CFG(3, 2, 1, 1, 1, 3, true))
-            else SNVC_WGRAD_CASE(SNVC_CFG(3, 2, 1, 1, 3, 3))
-            break;
-        case 511: SNVC_WGRAD_CASE(SNVC_CFG(5, 1, 1, 2, 1, 5)) break;
-        case 512: SNVC_WGRAD_CASE(SNVC_CFG(5, 1, 2, 2, 1, 5)) break;
-        case 711: SNVC_WGRAD_CASE(SNVC_CFG(7, 1, 1, 2, 1, 4)) break;
-        default:
-            return fail(SNVC_ERR_UNSUPPORTED,
-                        "snvc_conv3d_wgrad: (ksize,stride,dilation) not in {(1,1,1),(3,1,1),(3,2,1),(5,1,1),(5,1,2),(7,1,1)}");
-    }
-#undef SNVC_WGRAD_CASE
-    int rc = check_launch("snvc_conv3d_wgrad");
-    if (rc) return rc;
-    const int taps = d->ksize * d->ksize * d->ksize;
-    const int64_t total = (int64_t)pairs * taps * 1024;
-    wgrad_reduce_kernel<<<dim3((unsigned)ceil_div<int64_t>(total, 256)), 256, 0, st>>>(
-        (const float *)workspace, dw, d->Cout, d->Cin, taps, taps, a.cx_blocks, pairs, kWgradPartitions);
-    return check_launch("snvc_conv3d_wgrad(reduce)");
+int snvc_conv3d_wgrad_form(const snvc_conv3d_desc *d, int x_align, int g_align, int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad_form: info is NULL");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    for (int a : {x_align, g_align})
+        if (a != 16 && a != 8 && a != 4) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_wgrad_form: x_align and g_align are 16, 8 or 4");
+    WgradPlan p;
+    if (const int rc = plan_wgrad(d, x_align, g_align, device_cu_count(), p)) return -rc;
+    const bool split = p.form == SNVC_WG_X3 || p.form == SNVC_WG_X3S2;
+    info[0] = p.piece_bytes;
+    info[1] = p.ws_bytes;
+    info[2] = split ? p.dparts : (p.form == SNVC_WG_K1_STREAM ? p.chunks : p.P);
+    info[3] = split ? p.dchunk : (p.generic ? p.generic->chunks : p.upx);
+    info[4] = p.grid.x;
+    info[5] = (int64_t)p.grid.y * p.grid.z;
+    info[6] = p.threads;
+    info[7] = p.lds_bytes;
+    return p.form;
 }
 
 }  // extern "C"

@@ -833,9 +833,9 @@ def conv3d_wgrad(x_big, g_small, ksize: int, stride: int, pad: int, dilation: in
     d.ksize, d.stride, d.dilation, d.pad = ksize, stride, dilation, pad
     d.transposed, d.flags, d.algo = 0, 0, _algo()
     d.x_batch_stride, d.y_batch_stride, d.res_batch_stride = _batch_stride(x_big), _batch_stride(g_small), 0
-    ws = _workspace(_lib.lib().snvc_conv3d_wgrad_workspace_bytes(ctypes.byref(d)), x_big.device)
     dw = torch.empty((d.Cout, d.Cin, ksize, ksize, ksize), dtype=torch.float32, device=x_big.device)
-    with torch.cuda.device(x_big.device):
+    with torch.cuda.device(x_big.device):     # the workspace's size depends on the current device's CU count, as the launch does
+        ws = _workspace(_lib.lib().snvc_conv3d_wgrad_workspace_bytes(ctypes.byref(d)), x_big.device)
         check(_lib.lib().snvc_conv3d_wgrad_amax(ctypes.byref(d), _ptr(x_big), _ptr(g_small), _ptr(dw), _ptr(ws), _ptr(amax_x),
                                                 _ptr(amax_g), _stream(x_big)), "snvc_conv3d_wgrad")
     return dw

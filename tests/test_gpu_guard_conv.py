@@ -91,7 +91,8 @@ def fused_routes_case():
 # and the entry point refuses anything else.  None: aligned only -- the wrapper falls back to another route for operands off 16 bytes
 # (fused head, side head, avgpool fusion, statistics epilogue, the k1 streaming weight gradient), and the existing test asserts that
 # the fused route was taken; ``fused_routes_case`` runs those entry points at both placements against references that hold either way.
-ARENA = {"wgrad_k57": 2 << 30}          # the generic tap-chunk form's workspace query: 1.4 GB of per-workgroup partials for this k7 layer
+ARENA = {"wgrad_k57": 2 << 30,          # the generic tap-chunk form's workspace query: 1.4 GB of per-workgroup partials for this k7 layer
+         "wgrad_columns_s1": 256 << 20, "wgrad_columns_s2": 256 << 20}      # 57 MB of partials beside operands of up to 34 MB
 CASES = []
 for mode in ("default", "big", "std", "narrow", "direct"):               # (2, 32->32, (5, 7, W)) and (2, 6->64, (2, 9, W)), three epilogues
     CASES += [(f"k3_{mode}_W72", P, "test_k3_kernel_variants_vs_torch", dict(mode=mode, W=72), 4),
@@ -126,13 +127,16 @@ CASES += [
     ("wgrad_depth1", WF, "test_depth_one_vs_float64", dict(case="k3s2 d1 odd channels", variant="auto"), 4),
     ("wgrad_dparts", WF, "test_depth_parts_vs_float64", dict(case="k3 D33"), 4),
     ("wgrad_strided", WF, "test_batch_strided_operands", dict(case="k3 unaligned", variant="auto"), 4),
+    ("wgrad_columns_s1", WF, "test_column_limit_cases_vs_float64", dict(case="k3 257 columns", variant="auto"), 4),
+    ("wgrad_columns_s2", WF, "test_column_limit_cases_vs_float64", dict(case="k3s2 513 columns", variant="auto"), 4),
     ("wgrad_k1_stream", WF, "test_k1_streaming_form_vs_float64", dict(case="k1 idle channels"), None),
     ("wgrad_maxima_s1", "test_gpu_wgrad_x3", "test_wgrad_with_supplied_maxima", dict(stride=1, shape=(2, 40, 24, (5, 10, 44)), slack=1.0), 4),
     ("wgrad_maxima_s2", "test_gpu_wgrad_x3", "test_wgrad_with_supplied_maxima", dict(stride=2, shape=(1, 32, 64, (6, 12, 40)), slack=1.0), 4),
 ]
 assert all(c in WC.K57_CASES or c in WC.ROLE_SWAP_CASES or c in WC.DEPTH1_CASES or c in WC.DPART_CASES or c in WC.STRIDED_CASES
-           or c in WC.K1_STREAM_CASES for c in ("k7 8-byte rows, partial blocks", "40->24 rows of 18", "k3s2 d1 odd channels", "k3 D33",
-                                                "k3 unaligned", "k1 idle channels"))
+           or c in WC.K1_STREAM_CASES or c in WC.COLUMN_LIMIT_CASES
+           for c in ("k7 8-byte rows, partial blocks", "40->24 rows of 18", "k3s2 d1 odd channels", "k3 D33", "k3 unaligned", "k1 idle channels",
+                     "k3 257 columns", "k3s2 513 columns"))
 
 
 RUNS = [(c, off) for c in CASES for off in (0, c[4]) if off is not None]

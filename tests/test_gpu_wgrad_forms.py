@@ -2,13 +2,16 @@
 pinned to the kernel's definition by tests/test_wgrad_ref_host.py), at the shapes where its dispatcher changes its mind; and the data
 gradient of the k5 / dilated k5 / k7 layers.  The case tables and what each shape is for: tests/wgrad_cases.py.
 
-Every weight-gradient test calls ops.conv3d_wgrad twice and requires equal bits (no float atomics: the partial slabs are summed in a
+Every weight-gradient test first asks the library's own plan (snvc_conv3d_wgrad_form, include/snvc_forms.h) which form its shape takes
+at its operands' real alignment on this device, and requires the form of the case table's column (wgrad_cases.FORMS): a case that stops
+reaching its form fails instead of passing on a sibling.  It then calls ops.conv3d_wgrad twice and requires equal bits (no float atomics: the partial slabs are summed in a
 fixed order), then applies test_gpu_parity.check with the project's bounds for the form, relative to max|ref|:
     5e-6  exact-fp32 FMA chains summed in a fixed order: SNVC_ALGO_DIRECT, the generic tap-chunk kernel of the k5 / k5d2 / k7 keys
           under every variant, the k1 streaming form
     2e-5  the Winograd-domain and split-operand forms (and, as in test_conv3d_wgrad_vs_float64, whatever else `auto` / `fp32` reach)
 """
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -49,6 +52,31 @@ def _cus():
     return torch.cuda.get_device_properties(0).multi_processor_count
 
 
+_HEADER = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "snvc_forms.h")).read()
+
+
+def _align(t):
+    return 16 if t.data_ptr() % 16 == 0 else (8 if t.data_ptr() % 8 == 0 else 4)
+
+
+def _planned(group, case, variant, x_dev, g_dev, algo=None):
+    """(form name, info) of the launcher's plan for this case, variant and the operands' real alignment on this device; asserts the
+    case table's form and, for the split-operand and 12-wave forms, the restated plan numbers."""
+    from snvc_amd import _forms
+    fields = WC.case_desc_fields(group, case, variant)
+    if algo is not None:
+        fields["algo"] = algo
+    with torch.cuda.device(x_dev.device):
+        rc, info, text = _forms.conv3d_wgrad(WC.make_desc(fields), _align(x_dev), _align(g_dev))
+    assert rc > 0, text
+    form = {v: k for k, v in _forms.enum_names(_HEADER, "WG").items()}[rc]
+    assert form == WC.expected_form(group, case, variant, _align(x_dev), _align(g_dev)), (case, variant, _align(x_dev), _align(g_dev))
+    numbers = WC.expected_numbers(group, case, variant, form, _cus() // 8 * 8)
+    if numbers is not None:
+        assert (info["parts"], info["per_part"]) == tuple(numbers), (case, variant, form)
+    return form, info
+
+
 # ======================================================================================================== k5 / k5d2 / k7
 @pytest.mark.parametrize("variant", ["auto", "direct"])
 @pytest.mark.parametrize("case", sorted(WC.K57_CASES))
@@ -57,7 +85,9 @@ def test_generic_tap_chunk_kernel_vs_float64(case, variant):
     with a narrow second one, H odd against TH = 2, channel blocks of 8 and 24, rows of 16 / 8 / 4 bytes, and for k7 the ragged
     second tap chunk (3 of KHG = 4 kernel rows)."""
     x, g, ref = WC.conv_case("k57", case)
-    got = _wgrad_twice(x.to(dev()), g.to(dev()), _conv_args(WC.K57_CASES[case]), _bits(variant))
+    xd, gd = x.to(dev()), g.to(dev())
+    assert _planned("k57", case, variant, xd, gd)[0] == "TAPS"
+    got = _wgrad_twice(xd, gd, _conv_args(WC.K57_CASES[case]), _bits(variant))
     check(got, ref.astype(np.float32), DIRECT_TOL, f"wgrad {case} ({variant})")
 
 
@@ -70,8 +100,10 @@ def test_generic_kernel_scalar_staging_agrees(case):
     from snvc_amd import _lib
     x, g, ref = WC.conv_case("k57", case)
     args = _conv_args(WC.K57_CASES[case])
-    plain = _wgrad_twice(x.to(dev()), g.to(dev()), args, 0)
-    scalar = _wgrad_twice(x.to(dev()), g.to(dev()), args, _lib.ALGO_SCALAR_STAGING)
+    xd, gd = x.to(dev()), g.to(dev())
+    assert _planned("k57", case, "auto", xd, gd)[0] == _planned("k57", case, "auto", xd, gd, algo=_lib.ALGO_SCALAR_STAGING)[0] == "TAPS"
+    plain = _wgrad_twice(xd, gd, args, 0)
+    scalar = _wgrad_twice(xd, gd, args, _lib.ALGO_SCALAR_STAGING)
     check(scalar, ref.astype(np.float32), DIRECT_TOL, f"wgrad {case} (scalar staging)")
     diff = np.abs(scalar.astype(np.float64) - plain.astype(np.float64)).max()
     assert diff <= 2 * DIRECT_TOL * np.abs(ref).max(), f"{case}: the two stagings differ by {diff:.3e}"
@@ -84,7 +116,9 @@ def test_role_swapped_call_vs_float64_transposed(case, variant):
     """The call _ConvNormActFn.backward makes for a ConvTranspose3d(k3, s2, p1, op1): x := the output gradient on the doubled grid,
     g := the layer's input; the result must be nn.ConvTranspose3d's [Cin_d][Cout_d][27] as it stands."""
     gy_big, x_small, ref = WC.swap_case(case)
-    got = _wgrad_twice(gy_big.to(dev()), x_small.to(dev()), (3, 2, 1, 1), _bits(variant))
+    xd, gd = gy_big.to(dev()), x_small.to(dev())
+    _planned("swap", case, variant, xd, gd)
+    got = _wgrad_twice(xd, gd, (3, 2, 1, 1), _bits(variant))
     assert got.shape == (x_small.shape[1], gy_big.shape[1], 3, 3, 3)
     check(got, ref.astype(np.float32), _tol(variant), f"role-swapped wgrad {case} ({variant})")
 
@@ -100,7 +134,9 @@ def test_depth_one_vs_float64(case, variant):
     if c[5] == 2:
         assert c[3][0] != 2 * WC.out_extent(c[3][0], 3, 2, 1)
     x, g, ref = WC.conv_case("depth1", case)
-    got = _wgrad_twice(x.to(dev()), g.to(dev()), _conv_args(c), _bits(variant))
+    xd, gd = x.to(dev()), g.to(dev())
+    _planned("depth1", case, variant, xd, gd)
+    got = _wgrad_twice(xd, gd, _conv_args(c), _bits(variant))
     check(got, ref.astype(np.float32), _tol(variant), f"wgrad {case} ({variant})")
 
 
@@ -117,7 +153,13 @@ def test_depth_parts_vs_float64(case):
     if _cus() == 256:
         assert (parts, last) == (parts256, last256)
     x, g, ref = WC.conv_case("dparts", case)
-    got = _wgrad_twice(x.to(dev()), g.to(dev()), _conv_args(c), 0)
+    xd, gd = x.to(dev()), g.to(dev())
+    form, info = _planned("dparts", case, "auto", xd, gd)
+    if form in WC.SPLIT_FORMS:               # (operands off 16 bytes stage scalars: no depth parts to ask about)
+        assert (info["parts"], info["per_part"]) == (parts, dchunk) and info["parts"] > 1
+        if _cus() == 256:
+            assert (info["parts"], info["per_part"]) == WC.PLAN_256[("dparts", case)]["auto"]
+    got = _wgrad_twice(xd, gd, _conv_args(c), 0)
     check(got, ref.astype(np.float32), FORM_TOL, f"wgrad {case}")
 
 
@@ -133,7 +175,15 @@ def test_more_channel_pairs_than_units(case, variant, request):
     assert pairs > units, f"{pairs} pairs fit the {units} units of a {_cus()}-CU device"
     request.addfinalizer(ops.release_workspaces)          # 512 partitions x 99 pairs of slabs: not kept for the rest of the session
     x, g, ref = WC.conv_case("pairs", case)
-    got = _wgrad_twice(x.to(dev()), g.to(dev()), _conv_args(c), _bits(variant))
+    xd, gd = x.to(dev()), g.to(dev())
+    form, info = _planned("pairs", case, variant, xd, gd)
+    if form in WC.UNIT_FORMS:                # one partition, and the units of every XCD hold all the pairs in rounds
+        assert info["parts"] == 1 and 8 * info["per_part"] >= pairs > units and info["grid_x"] == 3 * 8 * info["per_part"]
+    elif form in WC.SPLIT_FORMS:             # one job per (column, pair of the job list): more jobs than units
+        assert info["parts"] == 1 and info["grid_x"] > units
+    else:                                    # generic forms: grid.y = pairs
+        assert info["grid_yz"] == pairs * info["per_part"] and pairs > units
+    got = _wgrad_twice(xd, gd, _conv_args(c), _bits(variant))
     check(got, ref.astype(np.float32), _tol(variant), f"wgrad {case} ({variant})")
 
 
@@ -160,6 +210,7 @@ def test_batch_strided_operands(case, variant):
     xs, gs = _channel_slice(x, lo), _channel_slice(g, lo)
     aligned = xs.data_ptr() % 16 == 0 and gs.data_ptr() % 16 == 0
     assert aligned == case.endswith(" aligned")
+    _planned("strided", case, variant, xs, gs)
     got = _wgrad_twice(xs, gs, args, _bits(variant))
     check(got, ref.astype(np.float32), _tol(variant), f"strided wgrad {case} ({variant})")
 
@@ -176,8 +227,42 @@ def test_k1_streaming_form_vs_float64(case):
     x, g, ref = WC.conv_case("k1", case)
     xd, gd = x.to(dev()), g.to(dev())
     assert xd.data_ptr() % 16 == 0 and gd.data_ptr() % 16 == 0
+    form, info = _planned("k1", case, "auto", xd, gd)
+    assert (form == "K1_STREAM") == streaming and (not streaming or info["parts"] == chunks)
     got = _wgrad_twice(xd, gd, _conv_args(c), 0)
     check(got, ref.astype(np.float32), DIRECT_TOL, f"wgrad {case}")
+
+
+# ======================================================================================================== the column limits
+@pytest.mark.parametrize("variant", ["auto", "fp32"])
+@pytest.mark.parametrize("case", sorted(WC.COLUMN_LIMIT_CASES))
+def test_column_limit_cases_vs_float64(case, variant):
+    """One column more than the split-operand forms' partial slabs hold (257 of 4 x 32 voxels, 513 of 2 x 32 at stride 2): the layer
+    takes its key's 12-wave form under `auto` as under `fp32`, and is right."""
+    c = WC.COLUMN_LIMIT_CASES[case]
+    x, g, ref = WC.conv_case("columns", case)
+    xd, gd = x.to(dev()), g.to(dev())
+    form, _ = _planned("columns", case, variant, xd, gd)
+    if _align(xd) == _align(gd) == 16:
+        assert form == ("WINO" if c[5] == 1 else "S2")
+    got = _wgrad_twice(xd, gd, _conv_args(c), _bits(variant))
+    check(got, ref.astype(np.float32), FORM_TOL, f"wgrad {case} ({variant})")
+
+
+# ======================================================================================================== rows of 8 bytes
+@pytest.mark.parametrize("variant", ["auto", "fp32", "direct"])
+@pytest.mark.parametrize("case", sorted(WC.ROWS8_CASES))
+def test_rows_of_eight_bytes_vs_float64(case, variant):
+    """The float2-piece variants: X3 on rows with W % 4 == 2 on both grids, and X3S2 / S2 / KSPLIT with vec == 2 (16-byte input rows,
+    Wo % 4 == 2)."""
+    c = WC.ROWS8_CASES[case]
+    x, g, ref = WC.conv_case("rows8", case)
+    xd, gd = x.to(dev()), g.to(dev())
+    form, info = _planned("rows8", case, variant, xd, gd)
+    if _align(xd) == _align(gd) == 16 and form != "TAPS":
+        assert info["piece_bytes"] == 8
+    got = _wgrad_twice(xd, gd, _conv_args(c), _bits(variant))
+    check(got, ref.astype(np.float32), _tol(variant), f"wgrad {case} ({variant})")
 
 
 # ======================================================================================================== unsupported keys
