@@ -31,6 +31,7 @@
 #include "elementwise_internal.hpp"
 #include "snvc_fused.h"
 #include "snvc_dedup.h"
+#include "snvc_alias.h"
 
 namespace snvc {
 namespace {
@@ -123,6 +124,28 @@ __host__ __device__ __forceinline__ bool wedge_tile_pure(int D, int W, int q, in
 __host__ __device__ __forceinline__ bool wedge_tile_duplicate(int D, int W, int q, int m0, int off, int d0, int w0) {
     return wedge_tile_pure(D, W, q, m0, off, d0, w0) && wedge_tile_pure(D, W, q, m0, off, d0 - 4, w0);
 }
+
+// Aliased duplicates (include/snvc_alias.h).  A duplicate tile's depth rows hold, bit for bit, what the representative's rows with the
+// same d & 3 hold, so a reader that looks THERE needs no copy behind the producer: the duplicates' rows of the tensor are never written
+// and never read.  WedgeDesc = snvc_wedge_desc: the producer's (D, W, q, m0, off); all zero aliases nothing (D - 3 < 0).
+// wedge_first_pure: the representative's d0 of tile column w0 where the column has pure tiles at all -- the rule of wedge_tile_pure
+// solved for d0: d0 >= 2 on the 4-grid is d0 >= 4, and q (w0 + 32) - (d0 - 1) - m0 + off < 0 is d0 >= q (w0 + 32) - m0 + off + 2.
+// wedge_alias_depth(d, w) -> the plane whose row holds voxel (d, ., w)'s bits: the identity outside duplicate tiles.  No loop, one
+// definition for the three readers and the host query (snvc_alias_depth) that the host test walks against wedge_tile_duplicate.
+using WedgeDesc = snvc_wedge_desc;
+__host__ __device__ __forceinline__ int wedge_first_pure(const WedgeDesc &g, int w0) {
+    const int lo = g.q * (w0 + 32) - g.m0 + g.off + 2;
+    return ((lo > 4 ? lo : 4) + 3) & ~3;
+}
+__host__ __device__ __forceinline__ int wedge_alias_depth(const WedgeDesc &g, int d, int w) {
+    const int w0 = w & ~31, d0 = d & ~3, first = wedge_first_pure(g, w0);
+    return (w0 + 32 < g.W - 1 && d0 > first && d0 + 3 <= g.D - 3) ? first + (d & 3) : d;
+}
+// conv3d_x3s2q_kernel<1>: the input pair's duplicate rows are read at their representative's
+struct F16AliasArgs : F16Args {
+    WedgeDesc in_alias;
+};
+constexpr int SRC_NO_COPY = 1 << 29;    // F16SrcArgs::v_flags, internal, with SRC_DEDUP: no wedge_copy_kernel behind the launch (the readers alias)
 
 // A-fragment register ring depth (k-steps ahead).  Measured on cfg5 (k7 / k5 / k3 ms): 2: 9.70 / 1.92 / 0.91;
 // 4: 9.38 / 2.00 / 0.91; 6: 8.99 / 1.82 / 0.85 (242-246 VGPRs, no spills); 8: 8.89 / 1.83 / 0.86 with spills.
@@ -1176,6 +1199,10 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
     if (vmax >= kHalfMax && a.overflow) atomicOr(a.overflow, 1);
 }
 
+// The COPY route of the wedge (snvc_dedup_fused_first_conv3d_forward: the caller sees a fully populated tensor).  GlobalStack's step no
+// longer takes it where both readers of conv2's results can alias (SRC_NO_COPY, include/snvc_alias.h: conv3d_x3s2q_kernel<1> and
+// deconv_tail_gather_alias_kernel read the representative's rows, this launch and its 33 MB of stores are gone); it remains for every
+// other reader -- another stride-2 form, the unfused tail, a caller of the C entry point.
 // Behind conv3d_x3q_kernel<EPI, 1> with SRC_DEDUP, on its stream: the duplicate wedge tiles it returned from.  Workgroup = one
 // duplicate tile (tw, td) of one (n, th): ONE depth row of the column's representative tile -- both planes, every channel group, the
 // tile's rows inside the tensor, 32 columns, and the side head's row -- is read (16.5 KB at 32 channels) and stored to the tile's four
@@ -1465,8 +1492,11 @@ __device__ __forceinline__ void wait_lgkm_for4(h8 (&b)[4]) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]) : "n"(N) : "memory");
 }
 
+// ALIAS: the input pair's duplicate wedge tiles were not written (a.in_alias, include/snvc_alias.h): a piece of such a row is fetched
+// from the representative's plane -- the same 128-byte lines of another plane, decided in geometry() and nowhere else.
+template <int ALIAS = 0>
 __global__ void __launch_bounds__(512, 1)
-conv3d_x3s2q_kernel(const F16Args a, const int total_jobs) {
+conv3d_x3s2q_kernel(const std::conditional_t<ALIAS == 1, F16AliasArgs, F16Args> a, const int total_jobs) {
     using Cfg = X3S2Cfg;
     constexpr int NB = Cfg::NB, TH = Cfg::TH, IN_H = Cfg::IN_H, IN_W = Cfg::IN_W, VOX = Cfg::VOX, NIT = Cfg::NIT, NQ = Cfg::NQ;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -1515,7 +1545,9 @@ conv3d_x3s2q_kernel(const F16Args a, const int total_jobs) {
             const int ww = pp == 64 ? 64 : (rr_ < 16 ? 2 * (16 * blk + rr_) : 2 * (16 * blk + rr_ - 16) + 1);
             const int gd = id0 + dd, gh = ih0 + hh, gw = iw0 + ww;
             const bool ok = i < VOX && (unsigned)gd < (unsigned)a.Din && (unsigned)gh < (unsigned)a.Hin && (unsigned)gw < (unsigned)a.Win;
-            off[it] = ok ? (unsigned)(gd * in_hw + gh * a.Win + gw) : 0u;
+            int sd = gd;      // the plane that holds the piece
+            if constexpr (ALIAS) sd = wedge_alias_depth(a.in_alias, gd, gw);
+            off[it] = ok ? (unsigned)(sd * in_hw + gh * a.Win + gw) : 0u;
             vmask |= (ok ? 1u : 0u) << it;
         }
     };
@@ -2174,9 +2206,12 @@ __global__ void pack_tail_weights_kernel(const float *__restrict__ w, _Float16 *
 // (k3, s2, p1, op1) to one channel whose per-voxel contraction T was formed by the producing layer (EPI 4).  T is class-major:
 // [27][8 = (i_d & 1, i_h & 1, i_w & 1)][nd][nh][nw], i = 2 p + r.  A thread owns 4 consecutive outputs of one output row
 // (ow = 4 j .. 4 j + 3): every T element is read exactly once, 4-byte loads consecutive across the lanes, one 16-byte store.
-__global__ void __launch_bounds__(256)
-deconv_tail_gather_kernel(const float *__restrict__ t, const float *__restrict__ bias, const float *__restrict__ res, float *__restrict__ y,
-                          int nd, int nh, int nw, int64_t t_bs, int64_t y_bs, int64_t r_bs) {
+// ALIAS: the residual's duplicate wedge tiles were not written (include/snvc_alias.h).  The thread's four outputs lie in one 32-column
+// tile (4 j is 4-aligned) of one plane: one remap of od per thread, for the residual's load only.
+template <int ALIAS>
+__device__ __forceinline__ void deconv_tail_gather_body(const float *__restrict__ t, const float *__restrict__ bias, const float *__restrict__ res,
+                                                        float *__restrict__ y, int nd, int nh, int nw, int64_t t_bs, int64_t y_bs, int64_t r_bs,
+                                                        const WedgeDesc &ra) {
     const int OD = 4 * nd, OH = 4 * nh;
     const int64_t total = (int64_t)OD * OH * nw;
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -2212,10 +2247,23 @@ deconv_tail_gather_kernel(const float *__restrict__ t, const float *__restrict__
     }
     const int64_t sp = ((int64_t)od * OH + oh) * (4 * nw) + 4 * j;
     if (res) {
-        const f32x4 rv = *reinterpret_cast<const f32x4 *>(res + n * r_bs + sp);
+        int64_t rsp = sp;
+        if constexpr (ALIAS) rsp = ((int64_t)wedge_alias_depth(ra, od, 4 * j) * OH + oh) * (4 * nw) + 4 * j;
+        const f32x4 rv = *reinterpret_cast<const f32x4 *>(res + n * r_bs + rsp);
         o0 += rv[0]; o1 += rv[1]; o2 += rv[2]; o3 += rv[3];
     }
     *reinterpret_cast<f32x4 *>(y + n * y_bs + sp) = f32x4{o0, o1, o2, o3};
+}
+
+__global__ void __launch_bounds__(256)
+deconv_tail_gather_kernel(const float *__restrict__ t, const float *__restrict__ bias, const float *__restrict__ res, float *__restrict__ y,
+                          int nd, int nh, int nw, int64_t t_bs, int64_t y_bs, int64_t r_bs) {
+    deconv_tail_gather_body<0>(t, bias, res, y, nd, nh, nw, t_bs, y_bs, r_bs, WedgeDesc{});
+}
+__global__ void __launch_bounds__(256)
+deconv_tail_gather_alias_kernel(const float *__restrict__ t, const float *__restrict__ bias, const float *__restrict__ res, float *__restrict__ y,
+                                int nd, int nh, int nw, int64_t t_bs, int64_t y_bs, int64_t r_bs, const WedgeDesc ra) {
+    deconv_tail_gather_body<1>(t, bias, res, y, nd, nh, nw, t_bs, y_bs, r_bs, ra);
 }
 
 // The power of two that puts max|x| into [2^13, 2^14) (1 for an all-zero or non-finite tensor) -- the scale of a split pair whose range is
@@ -2342,11 +2390,18 @@ void launch_wedge_copy(const F16SrcArgs &a, hipStream_t st) {
 }
 
 // persistent: one workgroup per CU (144 KB of LDS each), a multiple of 8 so that a workgroup's jobs b, b + G, ... stay on its XCD
-void launch_x3s2q(const F16Args &a, const F16Geom &g, hipStream_t st) {
+int x3s2q_workgroups(const F16Geom &g) {
     int wg = device_cu_count();
     if (wg <= 0) wg = 256;
     if (g.jobs < wg) wg = g.jobs >= 8 ? (int)(g.jobs & ~(int64_t)7) : (int)g.jobs;
-    launch_lds<conv3d_x3s2q_kernel>(dim3((unsigned)wg), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)g.jobs);
+    return wg;
+}
+void launch_x3s2q(const F16Args &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_x3s2q_kernel<0>>(dim3((unsigned)x3s2q_workgroups(g)), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)g.jobs);
+}
+// the same launch on an input pair whose duplicate wedge tiles were not written (snvc_alias_f16x3_conv3d_forward)
+void launch_x3s2q_alias(const F16AliasArgs &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_x3s2q_kernel<1>>(dim3((unsigned)x3s2q_workgroups(g)), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)g.jobs);
 }
 
 // a 32x32x16 form: everything but its class mode and its statistics bit follows from the Cfg; EPI 0 C8, 1 plane, 2 float32, 3 side head, 4 tail
@@ -2701,6 +2756,7 @@ struct F16x3Call {
     int64_t *stats_slots = nullptr;
     const float *x_mul = nullptr;
     const snvc::F16SrcArgs *src = nullptr;                // the fused sheared first layer: the image's producer
+    const snvc_wedge_desc *in_alias = nullptr;            // the input pair's duplicate wedge tiles were not written (snvc_alias.h)
     void *stream = nullptr;
 };
 
@@ -2794,12 +2850,24 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const F16x3Call &c) {
     if (g.jobs >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv3d_forward: too many tiles");
     if (c.src && to_f32) return fail(SNVC_ERR_UNSUPPORTED, "snvc_fused_first_conv3d_forward: a split C8 output");
     // the wedge's duplicate tiles are skipped and copied back only where the copy is all 16-byte accesses (the side head's rows: W % 4
-    // == 0) and there is a duplicate at all; otherwise the launch computes every tile
-    if ((b.v_flags & SRC_DEDUP) && ((c.y_head && (d->Wout % 4 || (reinterpret_cast<uintptr_t>(c.y_head) & 15))) ||
+    // == 0) and there is a duplicate at all; otherwise the launch computes every tile.  SRC_NO_COPY: nothing is copied, so only the
+    // second condition counts (a reader that aliases is right either way: computed duplicates hold the representative's bits)
+    if ((b.v_flags & SRC_DEDUP) && ((!(b.v_flags & SRC_NO_COPY) && c.y_head && (d->Wout % 4 || (reinterpret_cast<uintptr_t>(c.y_head) & 15))) ||
                                     wedge_ranges(a.Din, a.Win, b.v_q, b.v_m0, b.v_off, nullptr, nullptr, 0).dups == 0))
         b.v_flags &= ~SRC_DEDUP;
+    if (c.in_alias) {           // one reader form is built; the aliased rows are whole rows of the representative's plane: nothing else moves
+        if (&f != &FORM_K3S2XQ || call != TO_C8)
+            return fail(SNVC_ERR_UNSUPPORTED, "snvc_alias_f16x3_conv3d_forward: built for the stride-2 3x3x3 layer on the 16x16x32 form (SNVC_ALGO_X3_Q16) with a split C8 result");
+        if (c.in_alias->D != d->Din || c.in_alias->W != d->Win || (c.in_alias->q != 1 && c.in_alias->q != 2))
+            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_alias_f16x3_conv3d_forward: in_alias describes a [Din][.][Win] tensor, q = 1 | 2");
+        F16AliasArgs al{};
+        static_cast<F16Args &>(al) = a;
+        al.in_alias = *c.in_alias;
+        launch_x3s2q_alias(al, g, st);
+        return check_launch("snvc_alias_f16x3_conv3d_forward");
+    }
     f.launch[call](b, g, st);
-    if (b.v_flags & SRC_DEDUP) launch_wedge_copy(b, st);
+    if ((b.v_flags & SRC_DEDUP) && !(b.v_flags & SRC_NO_COPY)) launch_wedge_copy(b, st);
     return check_launch("snvc_f16x3_conv3d_forward");
 }
 
@@ -2823,7 +2891,7 @@ int snvc_f16x3_conv3d_forward(const snvc_conv3d_desc *d, const void *x_hi, const
 static int fused_first_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias, void *y_hi,
                                void *y_lo, const float *head, float *y_head, float head_mul, int *overflow, const float *gi,
                                int64_t pitch, int64_t lp, const float *p_il, const float *v_scale, const float *v_bias, int q, int m0,
-                               int off, int off2, int v_flags, bool dedup, void *stream) {
+                               int off, int off2, int v_flags, int dedup, void *stream) {      // dedup: 0 | SRC_DEDUP | SRC_DEDUP | SRC_NO_COPY
     using namespace snvc;
     if (!d || !gi || !p_il || !v_scale || !v_bias) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused_first_conv3d_forward: null pointer");
     if (d->transposed || d->ksize != 3 || d->stride != 1 || d->pad != 1 || d->dilation != 1 || d->Cin % 8 || d->Din < 1 || d->Hin < 1 || d->Win < 1 ||
@@ -2842,7 +2910,7 @@ static int fused_first_forward(const snvc_conv3d_desc *d, const void *packed_wei
     F16SrcArgs s{};
     s.gi = gi; s.p_il = p_il; s.v_scale = v_scale; s.v_bias = v_bias; s.gi_bs = 6 * CG * H * pitch * 8;
     s.v_pitch = (int)pitch; s.v_lp = (int)lp; s.v_q = q; s.v_m0 = m0; s.v_off = off; s.v_off2 = off2;
-    s.v_flags = v_flags | (dedup ? SRC_DEDUP : 0);
+    s.v_flags = v_flags | dedup;
     F16x3Call c;
     c.packed_weight = packed_weight; c.scale = scale; c.bias = bias; c.y_hi = y_hi; c.y_lo = y_lo;
     c.head = head; c.y_head = y_head; c.head_mul = head_mul; c.res_mul = 1.0f; c.overflow = overflow; c.src = &s; c.stream = stream;
@@ -2854,7 +2922,7 @@ int snvc_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packe
                                     int64_t pitch, int64_t lp, const float *p_il, const float *v_scale, const float *v_bias, int q, int m0,
                                     int off, int off2, int v_flags, void *stream) {
     return fused_first_forward(d, packed_weight, scale, bias, y_hi, y_lo, head, y_head, head_mul, overflow, gi, pitch, lp, p_il, v_scale, v_bias,
-                               q, m0, off, off2, v_flags, false, stream);
+                               q, m0, off, off2, v_flags, 0, stream);
 }
 
 int snvc_dedup_abi_version(void) { return 1; }
@@ -2864,7 +2932,7 @@ int snvc_dedup_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void 
                                           const float *gi, int64_t pitch, int64_t lp, const float *p_il, const float *v_scale,
                                           const float *v_bias, int q, int m0, int off, int off2, int v_flags, void *stream) {
     return fused_first_forward(d, packed_weight, scale, bias, y_hi, y_lo, head, y_head, head_mul, overflow, gi, pitch, lp, p_il, v_scale, v_bias,
-                               q, m0, off, off2, v_flags, true, stream);
+                               q, m0, off, off2, v_flags, snvc::SRC_DEDUP, stream);
 }
 
 int64_t snvc_dedup_fused_first_tiles(const snvc_conv3d_desc *d, int q, int m0, int off, int64_t *first_td, int64_t *last_td, int max_tw) {
@@ -2875,6 +2943,35 @@ int64_t snvc_dedup_fused_first_tiles(const snvc_conv3d_desc *d, int q, int m0, i
     }
     for (int tw = 0; tw < max_tw; ++tw) first_td[tw] = last_td[tw] = -1;
     return wedge_ranges((int)d->Din, (int)d->Win, q, m0, off, first_td, last_td, max_tw).dups;
+}
+
+// ---- include/snvc_alias.h: the duplicates are neither computed nor copied; the readers look at the representative's rows
+int snvc_alias_abi_version(void) { return 1; }
+
+int64_t snvc_alias_depth(const snvc_wedge_desc *w, int64_t d, int64_t x) {
+    using namespace snvc;
+    if (!w || (w->q != 1 && w->q != 2) || d < 0 || d >= w->D || x < 0 || x >= w->W) {
+        fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_alias_depth: a desc with q = 1 | 2 and (d, w) inside [0, D) x [0, W)");
+        return -1;
+    }
+    return wedge_alias_depth(*w, (int)d, (int)x);
+}
+
+int snvc_alias_fused_first_conv3d_forward(const snvc_conv3d_desc *d, const void *packed_weight, const float *scale, const float *bias,
+                                          void *y_hi, void *y_lo, const float *head, float *y_head, float head_mul, int *overflow,
+                                          const float *gi, int64_t pitch, int64_t lp, const float *p_il, const float *v_scale,
+                                          const float *v_bias, int q, int m0, int off, int off2, int v_flags, void *stream) {
+    return fused_first_forward(d, packed_weight, scale, bias, y_hi, y_lo, head, y_head, head_mul, overflow, gi, pitch, lp, p_il, v_scale, v_bias,
+                               q, m0, off, off2, v_flags, snvc::SRC_DEDUP | snvc::SRC_NO_COPY, stream);
+}
+
+int snvc_alias_f16x3_conv3d_forward(const snvc_conv3d_desc *d, const void *x_hi, const void *x_lo, const void *packed_weight,
+                                    const float *scale, const float *bias, void *y_hi, void *y_lo, int *overflow,
+                                    const snvc_wedge_desc *in_alias, void *stream) {
+    F16x3Call c;
+    c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias;
+    c.y_hi = y_hi; c.y_lo = y_lo; c.head_mul = 1.0f; c.res_mul = 1.0f; c.overflow = overflow; c.in_alias = in_alias; c.stream = stream;
+    return f16x3_forward(d, c);
 }
 
 int64_t snvc_f16x3_conv3d_stats_workspace_bytes(const snvc_conv3d_desc *d) {
@@ -3139,9 +3236,11 @@ int snvc_f16x3_deconv3d_tail_forward(const snvc_conv3d_desc *d, const void *x_hi
     return f16x3_forward(d, c);
 }
 
-int snvc_deconv_tail_gather(const float *t, const float *bias, const float *residual, float *y, int64_t n, int64_t nd, int64_t nh,
-                            int64_t nw, void *stream) {
+static int tail_gather(const float *t, const float *bias, const float *residual, float *y, int64_t n, int64_t nd, int64_t nh, int64_t nw,
+                       const snvc_wedge_desc *res_alias, void *stream) {
     using namespace snvc;
+    if (res_alias && (!residual || res_alias->D != 4 * nd || res_alias->W != 4 * nw || (res_alias->q != 1 && res_alias->q != 2)))
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_alias_deconv_tail_gather: res_alias describes the residual [4 nd][.][4 nw], q = 1 | 2");
     if (n < 0 || nd <= 0 || nh <= 0 || nw <= 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_deconv_tail_gather: sizes must be positive");
     if (n == 0) return SNVC_OK;
     if (!t || !y) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_deconv_tail_gather: null pointer");
@@ -3151,9 +3250,23 @@ int snvc_deconv_tail_gather(const float *t, const float *bias, const float *resi
     if (threads >= ((int64_t)1 << 31) * 255 || n > 65535 || 27 * 8 * nd * nh * nw >= ((int64_t)1 << 40))
         return fail(SNVC_ERR_UNSUPPORTED, "snvc_deconv_tail_gather: tensor too large");
     const dim3 grid((unsigned)ceil_div<int64_t>(threads, 256), (unsigned)n);
-    deconv_tail_gather_kernel<<<grid, 256, 0, as_stream(stream)>>>(t, bias, residual, y, (int)nd, (int)nh, (int)nw, 27 * 8 * nd * nh * nw,
-                                                                   out_vox, out_vox);
+    if (res_alias)
+        deconv_tail_gather_alias_kernel<<<grid, 256, 0, as_stream(stream)>>>(t, bias, residual, y, (int)nd, (int)nh, (int)nw,
+                                                                             27 * 8 * nd * nh * nw, out_vox, out_vox, *res_alias);
+    else
+        deconv_tail_gather_kernel<<<grid, 256, 0, as_stream(stream)>>>(t, bias, residual, y, (int)nd, (int)nh, (int)nw, 27 * 8 * nd * nh * nw,
+                                                                       out_vox, out_vox);
     return check_launch("snvc_deconv_tail_gather");
+}
+
+int snvc_deconv_tail_gather(const float *t, const float *bias, const float *residual, float *y, int64_t n, int64_t nd, int64_t nh,
+                            int64_t nw, void *stream) {
+    return tail_gather(t, bias, residual, y, n, nd, nh, nw, nullptr, stream);
+}
+
+int snvc_alias_deconv_tail_gather(const float *t, const float *bias, const float *residual, float *y, int64_t n, int64_t nd, int64_t nh,
+                                  int64_t nw, const snvc_wedge_desc *res_alias, void *stream) {
+    return tail_gather(t, bias, residual, y, n, nd, nh, nw, res_alias, stream);
 }
 
 }  // extern "C"

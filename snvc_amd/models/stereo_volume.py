@@ -180,6 +180,11 @@ class GlobalStack(SplitModePolicy, nn.Module):
     # so conv2's tiles that lie wholly there (8.3 % at cfg2) are computed once per (row, column) and copied.  Same bits.  False: every
     # tile is computed.
     dedup_wedge = True
+    # the duplicates are not copied either (include/snvc_alias.h): their rows of v2s and of the side head stay unwritten, and the one
+    # reader of each -- the hourglass's first stride-2 layer, the tail's gather -- reads the representative's row in their place.  Same
+    # bits.  Taken only with dedup_wedge and fused_first on the fused-tail route, where that stride-2 layer runs on its persistent
+    # 16x16x32 form and the shape has duplicates; anything else is the copy route.  False: the copy route.
+    alias_wedge = True
     split_prep = True    # split mode: the sheared first layer's depth-1 3 x 7 layers (G, G') on the half pipe too (False: fp32 MFMA, as r4)
     fused_tail = True    # split mode: conv5's epilogue contracts its result with the folded one-channel tail (False: r4's two launches)
 
@@ -271,17 +276,24 @@ class GlobalStack(SplitModePolicy, nn.Module):
         hg = self.hg_conv3d
         _mark(timing, "conv2", 0)
         v2_out = self._buffer("v2s", (n, 2, 4, d, h, w, 8), dev, torch.float16)
+        alias = None            # the descriptor of v2s / hv when their duplicate rows stay unwritten
         if fused is not None:
+            if self._alias_route(st, n, (d, h, w), fused[2]):
+                alias = ops.wedge_desc(d, w, fused[2]["q"], fused[2]["m0"], fused[2]["off"])
             v2s, hv = L["conv2"].forward_fused_first(n=n, in_sp=(d, h, w), x_exp=E["v1"], scale=A["conv2"][0], bias=A["conv2"][1], flags=EPI_RELU,
                                                      out_exp=E["conv2"], head=self.classifier.weight, overflow=flag, out=v2_out,
-                                                     dedup=bool(self.dedup_wedge), **fused[2])
+                                                     dedup=bool(self.dedup_wedge), alias=alias is not None, **fused[2])
             _ROUTES["fused_first_conv"] += 1
+            _ROUTES["wedge_alias"] += alias is not None
         else:
             v2s, hv = L["conv2"](v1s, E["v1"], *A["conv2"], flags=EPI_RELU, out_exp=E["conv2"], head=self.classifier.weight, overflow=flag,
                                  out=v2_out)
         _mark(timing, "conv2", 1)
         _ROUTES["side_head"] += 1
-        o = L["h1"](v2s, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)                  # 1/2 res, 2C channels
+        if alias is not None:
+            o = L["h1"].forward_aliased(v2s, alias, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)
+        else:
+            o = L["h1"](v2s, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)              # 1/2 res, 2C channels
         pre = L["h2"](o, E["h1"], *A["h2"], flags=EPI_RELU, out_exp=E["h2"], overflow=flag)                     # relu(bn(conv))   :153-156
         o = L["h3"](pre, E["h2"], *A["h3"], flags=EPI_RELU, out_exp=E["h3"], overflow=flag)                     # 1/4 res
         o = L["h4"](o, E["h3"], *A["h4"], flags=EPI_RELU, out_exp=E["h4"], overflow=flag)
@@ -291,7 +303,7 @@ class GlobalStack(SplitModePolicy, nn.Module):
             # fp32 planes per parity class leave instead of 64 channels, and the last launch only sums them
             t = L["h5"].forward_tail(o, E["h4"], *A["h5"], st["tail"], residual=pre, res_exp=E["h2"], flags=EPI_RELU | ops.EPI_ADD_PRE,
                                      out_exp=E["post"], overflow=flag, out=self._buffer("tail_t", (n, 27, 8) + tuple(o.shape[3:6]), dev))
-            cost = ops.deconv_tail_gather(t, st["tail_bias"], hv)                             # deconv'(post) + b' + classifier(v2)
+            cost = ops.deconv_tail_gather(t, st["tail_bias"], hv, res_alias=alias)            # deconv'(post) + b' + classifier(v2)
             _ROUTES["x3_fused_tail"] += 1
         else:
             # post = relu(bn(deconv(o)) + pre): the result leaves as fp32 NCDHW for the one-channel transposed tail (VALU kernel)
@@ -302,6 +314,15 @@ class GlobalStack(SplitModePolicy, nn.Module):
             # waited for while the transposed layer and the tail still run: this call's result is dropped and redone in fp32
             raise SplitOverflow()
         return cost
+
+    def _alias_route(self, st, n, sp, src) -> bool:
+        """True when this call's conv2 may leave the wedge's duplicate rows unwritten: both readers of v2s / hv then take the
+        descriptor.  ``src``: the fused first layer's kwargs (q, m0, off)."""
+        if not (self.alias_wedge and self.dedup_wedge and st["tail"] is not None and self.fused_tail):
+            return False
+        if not st["layers"]["h1"].aliased_form(n, sp):
+            return False
+        return ops.fused_first_wedge_dups(int(sp[0]), int(sp[2]), int(src["q"]), int(src["m0"]), int(src["off"])) > 0
 
     def _tail(self, v, hv=None):
         """v + hourglass(v)[0] -> classifier.  The hourglass's last transposed layer has no activation

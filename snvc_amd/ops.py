@@ -9,6 +9,7 @@ PyTorch is plumbing here: it owns device memory and the HIP stream.  Every funct
 """
 import contextlib
 import ctypes
+import functools
 import math
 import threading
 import time
@@ -16,7 +17,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _dedup, _derived, _fused, _lib
+from . import _alias, _dedup, _derived, _fused, _lib
 from ._lib import (EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID, EPI_STREAM_OUT, F32, F64, Conv3dDesc,
                    Unsupported, check)
 
@@ -1641,6 +1642,12 @@ def fused_il_geometry(q: int, m0: int, d: int, w: int, wu: int, off: int, wu_col
     return hi - lo + 1, -lo
 
 
+@functools.lru_cache(maxsize=64)
+def fused_first_wedge_dups(d: int, w: int, q: int, m0: int, off: int) -> int:
+    """``fused_first_wedge_tiles(...)[0]``, remembered per shape (a step asks it on every call)."""
+    return fused_first_wedge_tiles(d, w, q, m0, off)[0]
+
+
 def fused_first_wedge_tiles(d: int, w: int, q: int, m0: int, off: int):
     """The wedge's duplicate tiles of the fused first layer on a [d, ., w] volume (snvc_dedup_fused_first_tiles: the rule the
     kernels use; include/snvc_dedup.h).  Returns (duplicates per (n, th), first, last): per 32-column tile column the depth tile
@@ -1653,6 +1660,21 @@ def fused_first_wedge_tiles(d: int, w: int, q: int, m0: int, off: int):
     if dups < 0:
         raise ValueError(_lib.lib().snvc_last_error_string().decode())
     return dups, list(first), list(last)
+
+
+def wedge_desc(d: int, w: int, q: int, m0: int, off: int) -> "_alias.WedgeDesc":
+    """The descriptor (snvc_wedge_desc, include/snvc_alias.h) of a [d, ., w] tensor that the fused first layer's conv2 wrote without
+    its duplicate tiles (``forward_fused_first(alias=True)``): what the tensor's readers are given."""
+    return _alias.WedgeDesc(int(d), int(w), int(q), int(m0), int(off))
+
+
+def wedge_alias_depth(desc: "_alias.WedgeDesc", d: int, w: int) -> int:
+    """The plane whose row holds voxel (d, ., w) of a tensor written under ``desc`` (snvc_alias_depth: the remap the kernels use).
+    Host only."""
+    got = int(_alias.lib().snvc_alias_depth(ctypes.byref(desc), int(d), int(w)))
+    if got < 0:
+        raise ValueError(_lib.lib().snvc_last_error_string().decode())
+    return got
 
 
 def sheared_prep_x3_il(right, q: int, wu: int, off: int, wu_col: int, off_col: int, lay_g: "Conv2dLayerX3", lay_col: "Conv2dLayerX3", ws: dict,
@@ -1916,14 +1938,25 @@ class Conv3dLayerX3(_ConvGeometry):
         return (self.ksize == 3 and self.stride == 1 and not self.transposed and self.w_mul_dev is None and self.cin % 8 == 0
                 and x3_form(self.cout, 3, 1, self.dilation, False, n, tuple(sp), True, False, self.forced_algo) == _lib.ALGO_X3_Q16)
 
+    def aliased_form(self, n: int, sp) -> bool:
+        """True when a plain launch (split result, no residual, no side head) on a [n, Cin, *sp] input would take the form that can read
+        an input pair with unwritten duplicate rows (``forward_aliased``): the stride-2 3x3x3 layer on its persistent 16x16x32 form.
+        Asks ``x3_form`` what ``forward_aliased``'s own ``_launch`` asks."""
+        sp = tuple(int(v) for v in sp)
+        return (self.ksize == 3 and self.stride == 2 and not self.transposed and self.w_mul_dev is None
+                and x3_form(self.cout, self.ksize, self.stride, self.dilation, self.transposed, n, self.out_spatial(sp), True, True,
+                            self.forced_algo) == _lib.ALGO_X3_Q16)
+
     def forward_fused_first(self, gi, pitch: int, lp: int, p_il, v_scale, v_bias, q: int, m0: int, off: int, off_col: int, v_flags: int,
                             n: int, in_sp, x_exp: int = 0, scale=None, bias=None, flags: int = 0, out=None, out_exp: int = 0, head=None,
-                            overflow=None, dedup: bool = False):
+                            overflow=None, dedup: bool = False, alias: bool = False, head_out=None):
         """``self(v1s, x_exp, ...)`` with v1s = the sheared first layer's split result (``sheared_expand_split`` of the same operands:
         ``gi`` / ``p_il`` channel-interleaved, ``v_scale`` / ``v_bias`` its folded affine carrying 2**x_exp) formed inside the launch
         (snvc_fused_first_conv3d_forward): same bits, v1s is never stored.  Raises Unsupported when the launch would not take the
         16x16x32 form.  ``dedup``: the wedge's duplicate tiles (``fused_first_wedge_tiles``) are copied from their representative
-        instead of computed (snvc_dedup_fused_first_conv3d_forward): same bits again."""
+        instead of computed (snvc_dedup_fused_first_conv3d_forward): same bits again.  ``alias``: the duplicates are neither computed
+        nor copied (snvc_alias_fused_first_conv3d_forward): their rows of the pair and of the side head keep what they held, and only a
+        reader that is given ``wedge_desc(d, w, q, m0, off)`` may take the results (``forward_aliased``, ``deconv_tail_gather``)."""
         in_sp = tuple(int(v) for v in in_sp)
         if not self.fused_first_form(n, in_sp):
             raise Unsupported("forward_fused_first: the layer does not run on the 16x16x32 form at this size")
@@ -1935,18 +1968,40 @@ class Conv3dLayerX3(_ConvGeometry):
         y_head = None
         if head is not None:
             head = head.detach().reshape(-1).float().contiguous()
-            y_head = torch.empty((n, 1) + out_sp, dtype=torch.float32, device=gi.device)
+            y_head = _result(head_out, (n, 1) + out_sp, torch.float32, gi.device, "`head_out` must be a contiguous float32 [N,1,D,H,W] tensor")
         sc, bi = self.folded(scale, bias, x_exp, out_exp)
         if n == 0:
             return (out, y_head) if head is not None else out
         d = self._desc(n, in_sp, flags, algo, 0, _batch_stride(out), 0)
-        entry = (_dedup.lib().snvc_dedup_fused_first_conv3d_forward if dedup else _fused.lib().snvc_fused_first_conv3d_forward)
+        name = ("snvc_alias_fused_first_conv3d_forward" if alias else "snvc_dedup_fused_first_conv3d_forward" if dedup
+                else "snvc_fused_first_conv3d_forward")
+        entry = getattr((_alias if alias else _dedup if dedup else _fused).lib(), name)
         with torch.cuda.device(gi.device):
             check(entry(ctypes.byref(d), _ptr(packed), _ptr(sc), _ptr(bi), _ptr(out), _lo_ptr(out), _ptr(head), _ptr(y_head),
                         float(2.0 ** -out_exp), _ptr(overflow), _ptr(gi), int(pitch), int(lp), _ptr(p_il), _ptr(v_scale), _ptr(v_bias), int(q),
-                        int(m0), int(off), int(off_col), int(v_flags), _stream(gi)),
-                  "snvc_dedup_fused_first_conv3d_forward" if dedup else "snvc_fused_first_conv3d_forward")
+                        int(m0), int(off), int(off_col), int(v_flags), _stream(gi)), name)
         return (out, y_head) if head is not None else out
+
+    def forward_aliased(self, x, in_alias: "_alias.WedgeDesc", x_exp: int = 0, scale=None, bias=None, flags: int = 0, out=None,
+                        out_exp: int = 0, overflow=None):
+        """``self(x, x_exp, ...)`` (split C8 result, no residual, no side head) on a pair ``x`` that ``forward_fused_first(alias=True)``
+        wrote without its duplicate tiles: their rows are read at the representative's (snvc_alias_f16x3_conv3d_forward).  Same bits as
+        on the fully populated pair.  Raises Unsupported for a layer or kernel form the aliased read is not built for."""
+        _split_check(x, "x")
+        if x.size(2) * 8 != self.cin:
+            raise RuntimeError(f"conv3d input must have {self.cin} channels (split C8), got {x.size(2) * 8}")
+        n, in_sp, out_sp, algo, packed = self._launch(x, plain=True, split_out=True)
+        out = _result(out, (n, 2, self.cout // 8) + out_sp + (8,), torch.float16, x.device,
+                      "conv3d `out` must be a split C8 tensor of the output shape", _split_check)
+        sc, bi = self.folded(scale, bias, x_exp, out_exp)
+        if n == 0:
+            return out
+        d = self._desc(n, in_sp, flags, algo, _batch_stride(x), _batch_stride(out), 0)
+        with torch.cuda.device(x.device):
+            check(_alias.lib().snvc_alias_f16x3_conv3d_forward(ctypes.byref(d), _ptr(x), _lo_ptr(x), _ptr(packed), _ptr(sc), _ptr(bi), _ptr(out),
+                                                               _lo_ptr(out), _ptr(overflow), ctypes.byref(in_alias), _stream(x)),
+                  "snvc_alias_f16x3_conv3d_forward")
+        return out
 
     def forward_f32(self, x, x_mul_dev, residual_f32: Optional[torch.Tensor] = None, relu: bool = False):
         """r6 (training): the plain convolution of a device-scaled layer with a float32 NCDHW result (snvc_f16x3_conv3d_forward_f32):
@@ -2045,10 +2100,12 @@ class TailWeightsX3:
                   "snvc_f16x3_tail_pack_weights")
 
 
-def deconv_tail_gather(t: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, out=None):
+def deconv_tail_gather(t: torch.Tensor, bias: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, out=None,
+                       res_alias: Optional["_alias.WedgeDesc"] = None):
     """The scatter half of a transposed layer (k3, s2, p1, op1) to one channel: ``t`` [N, 27, 8, nd, nh, nw] (per-voxel tap
     contractions, class-major: ``Conv3dLayerX3.forward_tail``) -> float32 [N, 1, 4nd, 4nh, 4nw] = bias + residual + the sums over
-    (voxel, tap) pairs that land on each output (snvc_deconv_tail_gather)."""
+    (voxel, tap) pairs that land on each output (snvc_deconv_tail_gather).  ``res_alias``: the residual is a side head that
+    ``forward_fused_first(alias=True)`` wrote without its duplicate rows (snvc_alias_deconv_tail_gather): same bits."""
     _gpu(t, "t")
     if t.dtype != torch.float32 or t.dim() != 6 or t.size(1) != 27 or t.size(2) != 8 or not t.is_contiguous():
         raise RuntimeError("t must be a contiguous float32 [N, 27, 8, nd, nh, nw] tensor")
@@ -2067,8 +2124,12 @@ def deconv_tail_gather(t: torch.Tensor, bias: Optional[torch.Tensor] = None, res
     if bias is not None:
         bias = bias.detach().reshape(-1)[:1].float().contiguous()
     with torch.cuda.device(t.device):
-        check(_lib.lib().snvc_deconv_tail_gather(_ptr(t), _ptr(bias), _ptr(residual), _ptr(out), n, nd, nh, nw, _stream(t)),
-              "snvc_deconv_tail_gather")
+        if res_alias is not None:
+            check(_alias.lib().snvc_alias_deconv_tail_gather(_ptr(t), _ptr(bias), _ptr(residual), _ptr(out), n, nd, nh, nw,
+                                                             ctypes.byref(res_alias), _stream(t)), "snvc_alias_deconv_tail_gather")
+        else:
+            check(_lib.lib().snvc_deconv_tail_gather(_ptr(t), _ptr(bias), _ptr(residual), _ptr(out), n, nd, nh, nw, _stream(t)),
+                  "snvc_deconv_tail_gather")
     return out
 
 
