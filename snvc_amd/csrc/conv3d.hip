@@ -1096,33 +1096,43 @@ __device__ __forceinline__ void wino_epilogue(const ConvArgs &a, const WinoJob &
     }
     if constexpr (XMODE == 3) {
         // Batch statistics of the layer's result, taken while it is still in registers (train-mode BatchNorm reads the
-        // tensor once less): every lane's fp32 (sum, sum of squares) of its <= 4*NB in-range values per channel go through
-        // the idle LDS buffers, 64 threads add them in fp64 in a fixed order -> stats[job][channel][2].
-        float *const P = xch;                       // [16 registers x 2][256 threads]
+        // tensor once less): every lane's (sum, sum of squares) of its <= 4*NB in-range values per channel, each value widened to
+        // fp64 BEFORE the first addition (a square of a float is exact in fp64; fp32 sums lose the variance of data whose mean
+        // is large against its spread), go through the idle LDS buffers, 8 registers at a time (the same 32 KB), and 32 threads
+        // per half add them in a fixed order -> stats[job][channel][2].
+        double *const P = reinterpret_cast<double *>(xch);       // [8 registers x 2][256 threads]
         const int tid = wave * 64 + lane;
-        __syncthreads();                            // every wave is done with the image / weight buffers
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            float su = 0.0f, sq = 0.0f;
+        for (int h = 0; h < 2; ++h) {
+            __syncthreads();                        // every wave is done with the image / weight buffers (h = 1: with the first half)
 #pragma unroll
-            for (int nb = 0; nb < NB; ++nb) {
-                const float v0 = ok0[nb] ? acc[0][nb][r] : 0.0f, v1 = ok0[nb] ? acc[1][nb][r] : 0.0f;
-                const float v2 = ok1[nb] ? acc[2][nb][r] : 0.0f, v3 = ok1[nb] ? acc[3][nb][r] : 0.0f;
-                su += (v0 + v1) + (v2 + v3);
-                sq += (v0 * v0 + v1 * v1) + (v2 * v2 + v3 * v3);
+            for (int r8 = 0; r8 < 8; ++r8) {
+                const int r = 8 * h + r8;
+                double su = 0.0, sq = 0.0;
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const double v = (double)((j < 2 ? ok0[nb] : ok1[nb]) ? acc[j][nb][r] : 0.0f);
+                        su += v;
+                        sq = __builtin_fma(v, v, sq);
+                    }
+                }
+                P[(2 * r8) * 256 + tid] = su;
+                P[(2 * r8 + 1) * 256 + tid] = sq;
             }
-            P[(2 * r) * 256 + tid] = su;
-            P[(2 * r + 1) * 256 + tid] = sq;
-        }
-        __syncthreads();
-        if (tid < 64) {
-            const int ch = tid >> 1, q = tid & 1;                       // channel (r & 3) + 8 * (r >> 2) + 4 * half
-            const int r = (ch & 3) + 4 * (ch >> 3), hf = (ch >> 2) & 1;
-            const float *src = P + (2 * r + q) * 256 + hf * 32;
-            double t = 0.0;
-            for (int w = 0; w < 4; ++w)
-                for (int l = 0; l < 32; ++l) t += (double)src[w * 64 + ((l + tid) & 31)];   // skewed: no bank conflicts
-            a.stats[(int64_t)job.id * 64 + tid] = t;
+            __syncthreads();
+            if ((tid >> 5) == h) {                  // tid < 64: channel tid >> 1, register r = 8 h + (r & 7)
+                const int ch = tid >> 1, q = tid & 1;                   // channel (r & 3) + 8 * (r >> 2) + 4 * half
+                const int r = (ch & 3) + 4 * (ch >> 3), hf = (ch >> 2) & 1;
+                const double *src = P + (2 * (r & 7) + q) * 256 + hf * 32;
+                double t = 0.0;
+#pragma unroll 1
+                for (int w = 0; w < 4; ++w)         // 8 loads in flight, not 128: half of the accumulators are still live at h = 0
+#pragma unroll 8
+                    for (int l = 0; l < 32; ++l) t += src[w * 64 + ((l + tid) & 31)];       // skewed across the readers
+                a.stats[(int64_t)job.id * 64 + tid] = t;
+            }
         }
     }
     if constexpr (HEAD) {
@@ -1714,17 +1724,19 @@ __device__ __forceinline__ void deconv_epilogue_fast(const ConvArgs &a, f32x16 (
     }
     if constexpr (STATS) {
         // Batch statistics of the layer's result while it is in registers (train-mode BatchNorm, as wino_epilogue's XMODE 3):
-        // fp32 (sum, sum of squares) of a lane's <= 2*NB in-range values per channel, added over the 32 lanes of its half-wave
-        // with xor shuffles, over the four waves through 1 KB of LDS, in fp64 -> a.stats[workgroup slot][32 channels][2].
+        // (sum, sum of squares) of a lane's <= 2*NB in-range values per channel, every value widened to fp64 before the first
+        // addition, added over the 32 lanes of its half-wave with xor shuffles and over the four waves through 2 KB of LDS, all
+        // in fp64 -> a.stats[workgroup slot][32 channels][2].
         static_assert(MI == 1, "one 32-channel group per workgroup");
-        float *const P = xch;                       // [4 waves][64]: channel (r, half) x (sum | sum of squares)
+        static_assert(4 * 64 * 8 <= Cfg::LDS_BYTES, "the statistics epilogue trades 2 KB through the image buffer");
+        double *const P = reinterpret_cast<double *>(xch);      // [4 waves][64]: channel (r, half) x (sum | sum of squares)
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            float su = 0.0f, sq = 0.0f;
+            double su = 0.0, sq = 0.0;
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
-                const float v0 = ok[nb] ? acc[0][nb][0][r] : 0.0f, v1 = ok[nb] ? acc[1][nb][0][r] : 0.0f;
+                const double v0 = ok[nb] ? (double)acc[0][nb][0][r] : 0.0, v1 = ok[nb] ? (double)acc[1][nb][0][r] : 0.0;
                 su += v0 + v1;
                 sq += v0 * v0 + v1 * v1;
             }
@@ -1740,7 +1752,7 @@ __device__ __forceinline__ void deconv_epilogue_fast(const ConvArgs &a, f32x16 (
         const int tid = wave * 64 + lane;
         if (tid < 64) {
             double t = 0.0;
-            for (int w = 0; w < 4; ++w) t += (double)P[w * 64 + tid];
+            for (int w = 0; w < 4; ++w) t += P[w * 64 + tid];
             const int64_t slot = ((n * gridDim.x + blockIdx.x) * gridDim.y + cg);
             a.stats[slot * 64 + tid] = t;
         }

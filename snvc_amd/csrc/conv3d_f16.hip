@@ -209,6 +209,29 @@ __device__ __forceinline__ int xcd_remap16(int b, int n) {
     return base + k;
 }
 
+// The 16x16x32 form's statistics fold of 8 per-lane fp64 sums over the W lanes of an aligned lane group: a transposing butterfly.
+// At xor distance o = W/2, W/4, W/8 a lane keeps one half of its values (the upper half where its bit o is set) and adds its partner's
+// sums of that half; below that the one value left is added across.  v[0] of a lane with (lane & (W/8 - 1)) == 0 is then the group's
+// sum of value `which` = 4 * bit(W/2) + 2 * bit(W/4) + bit(W/8) of that lane: 8 shuffles (W = 16) for 8 values instead of 32, each a
+// pair of 4-byte lane exchanges.  (In conv3d_f16_kernel its selects spill: that kernel keeps the plain xor trees.)
+template <int W>
+__device__ __forceinline__ int stats_fold8(double (&v)[8], int lane) {
+    int which = 0;
+#pragma unroll
+    for (int n = 4, o = W / 2; n >= 1; n >>= 1, o >>= 1) {
+        const bool up = (lane & o) != 0;
+        which += up ? n : 0;
+#pragma unroll
+        for (int k = 0; k < n; ++k) {
+            const double keep = up ? v[k + n] : v[k], send = up ? v[k] : v[k + n];
+            v[k] = keep + __shfl_xor(send, o, 64);
+        }
+    }
+#pragma unroll
+    for (int o = W / 16; o >= 1; o >>= 1) v[0] += __shfl_xor(v[0], o, 64);
+    return which;
+}
+
 // EPI 0: C8 half output (+affine, residual, ReLU); 1: fp32 plane of channel 0 (+Sigmoid); 2: fp32 NCDHW output (split mode);
 // 3: EPI 0 + the side head (split mode, one 32-channel block); 4: tail projection (split transposed layer whose ONLY consumer is a
 // transposed layer to one channel: the per-voxel contraction with that layer's 27 taps is done here, on the matrix pipe)
@@ -624,13 +647,6 @@ conv3d_f16_kernel(const F16Args a_) {
                 float hsum[NB];
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) hsum[nb] = 0.0f;
-                float st_s[2][8], st_q[2][8];          // EPI 2 with a.stats: this lane's sums over its voxels, per channel
-                if constexpr (EPI == 2) {
-#pragma unroll
-                    for (int j = 0; j < 2; ++j)
-#pragma unroll
-                        for (int e = 0; e < 8; ++e) st_s[j][e] = st_q[j][e] = 0.0f;
-                }
                 // one 8-channel group (a C8 piece) at a time: its affine / head weights are live only while its pieces are formed
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -643,6 +659,13 @@ conv3d_f16_kernel(const F16Args a_) {
                         if constexpr (side) hw4[k] = *reinterpret_cast<const f32x4 *>(a.head + cj + 4 * k);
                     }
                     const int64_t gj = (int64_t)(cj >> 3) * out_dhw;        // this group's plane of pieces
+                    // EPI 2 with a.stats: this lane's sums over its voxels of the group's 8 channels, in fp64 from the first value on
+                    // (fp32 sums lose the variance of data whose mean is large against its spread); folded per group: 32 registers
+                    double st_s[8], st_q[8];
+                    if constexpr (EPI == 2) {
+#pragma unroll
+                        for (int e = 0; e < 8; ++e) st_s[e] = st_q[e] = 0.0;
+                    }
 #pragma unroll
                     for (int nb = 0; nb < NB; ++nb) {
                         h8 rv = h8((_Float16)0.0f), rl = h8((_Float16)0.0f);
@@ -675,9 +698,9 @@ conv3d_f16_kernel(const F16Args a_) {
                                     const int64_t at = (int64_t)(cj + e) * out_dhw + sp[nb];
                                     yf[at] = rf ? __builtin_fmaf(v, a.head_mul, rfv[e]) : v * a.head_mul;     // 2^-e_y: exact
                                     if (want_stats) {
-                                        const float sv = v * a.head_mul;
-                                        st_s[j][e] += sv;
-                                        st_q[j][e] = __builtin_fmaf(sv, sv, st_q[j][e]);
+                                        const double sv = (double)(v * a.head_mul);
+                                        st_s[e] += sv;
+                                        st_q[e] = __builtin_fma(sv, sv, st_q[e]);
                                     }
                                 }
                             } else {
@@ -701,29 +724,27 @@ conv3d_f16_kernel(const F16Args a_) {
                             }
                         }
                     }
-                }
-                if constexpr (EPI == 2) {
-                    if (want_stats) {
-                        // the 32 lanes of a half-wave hold the same 16 channels at 32 columns: fold them, lane 0 of the half writes its slot
-                        const int zc = blockIdx.z / a.N, groups = (a.Cout + 31) >> 5;
-                        const int64_t slots = (int64_t)(gridDim.z / a.N) * gridDim.x * 4;
-                        const int64_t slot = ((int64_t)zc * gridDim.x + blockIdx.x) * 4 + wave;
-                        double *dst = a.stats + ((((int64_t)n * slots + slot) * groups + (cb * MI + m)) * 32 + 16 * half) * 2;
+                    if constexpr (EPI == 2) {
+                        if (want_stats) {
+                            // the 32 lanes of a half-wave hold the same 16 channels at 32 columns: fold them, lane 0 of the half writes its slot
+                            const int zc = blockIdx.z / a.N, groups = (a.Cout + 31) >> 5;
+                            const int64_t slots = (int64_t)(gridDim.z / a.N) * gridDim.x * 4;
+                            const int64_t slot = ((int64_t)zc * gridDim.x + blockIdx.x) * 4 + wave;
+                            double *dst = a.stats + ((((int64_t)n * slots + slot) * groups + (cb * MI + m)) * 32 + 16 * half + 8 * j) * 2;
 #pragma unroll
-                        for (int j = 0; j < 2; ++j)
-#pragma unroll
-                            for (int e = 0; e < 8; ++e) {
-                                float s0 = st_s[j][e], s1 = st_q[j][e];
+                            for (int e = 0; e < 8; ++e) {       // plain xor trees: this form has no registers to spare for stats_fold8's selects
+                                double s0 = st_s[e], s1 = st_q[e];
 #pragma unroll
                                 for (int o = 16; o >= 1; o >>= 1) {
                                     s0 += __shfl_xor(s0, o, 64);
                                     s1 += __shfl_xor(s1, o, 64);
                                 }
                                 if ((lane & 31) == 0) {
-                                    dst[(8 * j + e) * 2] = (double)s0;
-                                    dst[(8 * j + e) * 2 + 1] = (double)s1;
+                                    dst[e * 2] = s0;
+                                    dst[e * 2 + 1] = s1;
                                 }
                             }
+                        }
                     }
                 }
                 if constexpr (side) {     // the two half-waves hold channels 0..15 / 16..31 of the same 32 voxels
@@ -1109,9 +1130,9 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
         float *yf = a.y_f32 + n * a.yf_bs + (int64_t)c0 * out_dhw;
         const float *__restrict__ rf = a.res_f32 ? a.res_f32 + n * a.yf_bs + (int64_t)c0 * out_dhw : nullptr;
         const bool want_stats = a.stats != nullptr;
-        float st_s[8], st_q[8];
+        double st_s[8], st_q[8];           // in fp64 from the first value on, as conv3d_f16_kernel's EPI 2
 #pragma unroll
-        for (int e = 0; e < 8; ++e) st_s[e] = st_q[e] = 0.0f;
+        for (int e = 0; e < 8; ++e) st_s[e] = st_q[e] = 0.0;
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb) {
             const int row = wave * NB + nb;
@@ -1134,8 +1155,8 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
                     if (ok) {
                         yf[(int64_t)e * out_dhw + sp] = rf ? sv + rfv[e] : sv;
                         if (want_stats) {
-                            st_s[e] += sv;
-                            st_q[e] = __builtin_fmaf(sv, sv, st_q[e]);
+                            st_s[e] += (double)sv;
+                            st_q[e] = __builtin_fma((double)sv, (double)sv, st_q[e]);
                         }
                     }
                 }
@@ -1144,18 +1165,11 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
         if (want_stats) {
             const int groups = a.Cout >> 5;
             double *dst = a.stats + ((((int64_t)n * ntiles * 4 + (int64_t)t * 4 + wave) * groups + cb) * 32 + 8 * kb) * 2;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                float s0 = st_s[e], s1 = st_q[e];
-#pragma unroll
-                for (int o = 8; o >= 1; o >>= 1) {
-                    s0 += __shfl_xor(s0, o, 64);
-                    s1 += __shfl_xor(s1, o, 64);
-                }
-                if (col == 0) {
-                    dst[e * 2] = (double)s0;
-                    dst[e * 2 + 1] = (double)s1;
-                }
+            const int e = stats_fold8<16>(st_s, lane);            // over the 16 columns of this k-block's lanes
+            stats_fold8<16>(st_q, lane);
+            if ((col & 1) == 0) {
+                dst[e * 2] = st_s[0];
+                dst[e * 2 + 1] = st_q[0];
             }
         }
         return;

@@ -62,6 +62,29 @@ def norm_stats_ref(x, gamma, beta, groups, per_sample, eps):
     return scale, be[None] - mu_c * scale, mean, var
 
 
+def norm_stats_bounds(x, gamma, groups, per_sample, eps):
+    """(em, ev, b_scale, b_shift): how far statistics summed in float64 from the first element on, in any order, may lie from
+    norm_stats_ref -- without the float32 storage terms (u |ref|), which the caller adds.  Each of the two sums (x and x^2 over a
+    row of `count` elements) is off by at most count * 2^-53 * sum|terms|, one rounding per addition of partial sums that the sum of
+    the magnitudes bounds:
+        em = count * 2^-53 * mean|x|,     ev = 4 * count * 2^-53 * mean x^2     (var = E x^2 - mean^2, mean|x|^2 <= mean x^2),
+    [outer, groups]; scale = gamma rstd and shift = beta - mean rstd gamma are formed in float64 from the unrounded mean / var: with
+    rstd' = d rstd / d var = rstd^3 / 2 taken at the lowest admissible variance (where it is largest),
+        b_scale = |gamma| ev rstd',       b_shift = |gamma| (em rstd + |mean| ev rstd' + em ev rstd'),   [outer, C]."""
+    count, m_abs, m_sq = norm_moments_ref(x, groups, per_sample)
+    _, _, r_mean, r_var = norm_stats_ref(x, gamma, None, groups, per_sample, eps)
+    em, ev = count * 2.0 ** -53 * m_abs, 4 * count * 2.0 ** -53 * m_sq
+    c = np.shape(x)[1]
+    cpg = c // groups
+    rep = lambda a: np.repeat(a, cpg, axis=1)       # noqa: E731
+    ga = np.ones(c) if gamma is None else f64(gamma).reshape(c)
+    rstd = 1.0 / np.sqrt(r_var + float(eps))
+    d_rstd = 0.5 * (np.maximum(r_var - ev, 0.0) + float(eps)) ** -1.5 * ev
+    b_scale = np.abs(ga)[None] * rep(d_rstd)
+    b_shift = np.abs(ga)[None] * rep(em * rstd + np.abs(r_mean) * d_rstd + em * d_rstd)
+    return em, ev, b_scale, b_shift
+
+
 def preact_ref(x, scale, shift, res, flags, per_sample):
     """v, the argument of the activation: x * scale + shift, plus the residual under EPI_ADD_PRE; also the two affine terms."""
     x = f64(x)

@@ -138,19 +138,11 @@ def _check_norm_stats(x_np, x_dev, gamma, beta, groups, per_sample, cap, what):
     from snvc_amd import ops
     scale, shift, mean, var = (_np(t).astype(np.float64) for t in ops.norm_stats(x_dev, _t(gamma), _t(beta), groups, per_sample, EPS))
     r_scale, r_shift, r_mean, r_var = ER.norm_stats_ref(x_np, gamma, beta, groups, per_sample, EPS)
-    count, m_abs, m_sq = ER.norm_moments_ref(x_np, groups, per_sample)
-    em, ev = count * 2.0 ** -53 * m_abs, 4 * count * 2.0 ** -53 * m_sq
+    em, ev, b_scale, b_shift = ER.norm_stats_bounds(x_np, gamma, groups, per_sample, EPS)       # the arithmetic of the lines above
     assert (var >= 0.0).all(), f"{what}: negative variance"
     _within(mean, r_mean, em + U * np.abs(r_mean), what + " mean")
     _within(var, r_var, ev + U * r_var, what + " var")
-    c = x_np.shape[1]
-    cpg = c // groups
-    rep = lambda a: np.repeat(a, cpg, axis=1)
-    ga = np.ones(c) if gamma is None else ER.f64(gamma)
-    rstd = 1.0 / np.sqrt(r_var + EPS)
-    d_rstd = 0.5 * (np.maximum(r_var - ev, 0.0) + EPS) ** -1.5 * ev
-    b_scale = np.abs(ga)[None] * rep(d_rstd)
-    b_shift = np.abs(ga)[None] * rep(em * rstd + np.abs(r_mean) * d_rstd + em * d_rstd)
+    rep = lambda a: np.repeat(a, x_np.shape[1] // groups, axis=1)
     if cap:
         assert (b_scale <= 1e-6 * np.abs(r_scale)).all() and (b_shift <= 1e-6 * (np.abs(r_shift) + np.abs(rep(r_mean) * r_scale))).all(), what
     _within(scale, r_scale, b_scale + U * (np.abs(r_scale) + b_scale), what + " scale")

@@ -3,7 +3,10 @@ status, error text and -- for an accepted call -- the sha256 of the packed weigh
 tests/golden/f16_plan_gpu.json (tests/golden/make_golden_f16_plan.py --gpu, recorded on an MI355X from the library of the commit
 before the forms became records).  The kernels are deterministic and their code is what it was, so equal launch arguments give
 equal bits: a mismatch means the host side hands a kernel other arguments, or another kernel.  Shapes: tests/f16_plan_cases.py
-(Cin 16, N = 2, more than one tile and a ragged edge).  The fused first layer's route is held by tests/test_gpu_fused_first_layer.py."""
+(Cin 16, N = 2, more than one tile and a ragged edge).  The fused first layer's route is held by tests/test_gpu_fused_first_layer.py.
+One buffer was recorded again later: the scale / shift / mean / var rows of the `stats` call on the twelve cells that accept it, when the
+statistics epilogues began to sum in float64 from the first value on (tests/test_gpu_stats_epilogue.py holds their values); the float32
+result of that call and every other cell are the first record's."""
 import json
 import os
 

@@ -1574,17 +1574,22 @@ def test_conv_statistics_epilogue_vs_separate_pass(case):
     x = torch.from_numpy(r.standard_normal((2, cin) + shape).astype(np.float32)).to(dev())
     gamma = torch.from_numpy(r.uniform(0.5, 1.5, cout).astype(np.float32)).to(dev())
     beta = torch.from_numpy(r.standard_normal(cout).astype(np.float32)).to(dev())
-    layer = ops.Conv3dLayer(w, 3, stride, 1, 1, transposed)
-    got = layer.forward_stats(x, gamma, beta, 1e-5)
-    if case.startswith("unsupported"):
-        assert got is None
-        return
-    raw, scale, shift, mean, var = got
-    ref = layer(x)
-    assert torch.equal(raw, ref)
-    s2, h2, m2, v2 = ops.norm_stats(ref, gamma, beta, cout, False, 1e-5)
-    for a_, b_, what in ((scale, s2, "scale"), (shift, h2, "shift"), (mean, m2, "mean"), (var, v2, "var")):
-        np.testing.assert_allclose(a_.cpu().numpy(), b_.cpu().numpy(), rtol=2e-6, atol=2e-7, err_msg=what)
+    # the same comparison on a result whose per-channel mean is 50 .. 400 x its spread (tests/stats_cases.py, where the float64 bound is)
+    import stats_cases as SC
+    assert SC.layer_of("fp32", case)[:5] == (cin, cout, shape, stride, transposed)
+    x_off, w_off = (torch.from_numpy(a).to(dev()) for a in SC.conv_inputs("fp32", case, "offset"))
+    for data, x, w in (("ordinary", x, w), ("offset", x_off, w_off)):
+        layer = ops.Conv3dLayer(w, 3, stride, 1, 1, transposed)
+        got = layer.forward_stats(x, gamma, beta, 1e-5)
+        if case.startswith("unsupported"):
+            assert got is None
+            continue
+        raw, scale, shift, mean, var = got
+        ref = layer(x)
+        assert torch.equal(raw, ref)
+        s2, h2, m2, v2 = ops.norm_stats(ref, gamma, beta, cout, False, 1e-5)
+        for a_, b_, what in ((scale, s2, "scale"), (shift, h2, "shift"), (mean, m2, "mean"), (var, v2, "var")):
+            np.testing.assert_allclose(a_.cpu().numpy(), b_.cpu().numpy(), rtol=2e-6, atol=2e-7, err_msg=f"{what}, {data} data")
 
 
 @pytest.mark.parametrize("fused_bn", [True, False])

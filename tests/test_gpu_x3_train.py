@@ -182,6 +182,18 @@ def test_split_layer_f32_output_residual_and_statistics(case):
     s0, h0, m0, v0 = ops.norm_stats(y, gamma, beta, co, False, 1e-5)
     for a, b, what in ((scale, s0, "scale"), (shift, h0, "shift"), (mean, m0, "mean"), (var, v0, "var")):
         check(a.cpu().numpy(), b.cpu().numpy(), 2e-6, f"{case}: {what} from the epilogue")
+    # the statistics once more on a result whose per-channel mean is 50 .. 400 x its spread (tests/stats_cases.py, where the float64 bound is)
+    import stats_cases as SC
+    assert SC.layer_of("x3", case)[:5] == _LAYERS[case]
+    x, w = (_t(a) for a in SC.conv_inputs("x3", case, "offset"))
+    lay = ops.Conv3dLayerX3(w, 3, st, 1, 1, tr, w_mul_dev=ops.split_scale_of(w))
+    mul = ops.split_scale_of(x)
+    xs = ops.to_split(x, mul_dev=mul)
+    raw, scale, shift, mean, var = lay.forward_stats(xs, mul, gamma, beta, 1e-5)
+    assert torch.equal(raw, lay.forward_f32(xs, mul))
+    s0, h0, m0, v0 = ops.norm_stats(raw, gamma, beta, co, False, 1e-5)
+    for a, b, what in ((scale, s0, "scale"), (shift, h0, "shift"), (mean, m0, "mean"), (var, v0, "var")):
+        check(a.cpu().numpy(), b.cpu().numpy(), 2e-6, f"{case}: {what} from the epilogue, offset data")
 
 
 def _hourglass_grads(hg, x0, on):
