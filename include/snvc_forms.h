@@ -1,7 +1,8 @@
 /*
  * snvc_forms.h -- which kernel form the geometry launchers of libsnvc_hip.so take: the cost volume (csrc/cost_volume.hip) and the
  * feature -> voxel gather in both directions (csrc/voxel_gather.hip, csrc/voxel_gather_bwd.hip); and which form the weight
- * gradient of the 3D convolutions takes (csrc/conv3d_bwd.hip; last section).  Kept apart from snvc_hip.h,
+ * gradient of the 3D convolutions takes (csrc/conv3d_bwd.hip) and which form their fp32 forward takes (csrc/conv3d.hip; last
+ * section).  Kept apart from snvc_hip.h,
  * whose declaration set and ABI number are pinned; this header versions itself through snvc_forms_abi_version().
  *
  * Every launcher decides its form in one host function, from the sizes, the element type, the alignment of its operands and the
@@ -114,6 +115,82 @@ enum snvc_conv3d_wgrad_form_id {
     SNVC_WG_TAPS = 7            /* conv3d_wgrad_kernel<tap-split WgradCfg, 0>: keys 111, 311, 321, 511, 512, 711, scalar staging */
 };
 SNVC_API int snvc_conv3d_wgrad_form(const snvc_conv3d_desc *desc_host, int x_align, int g_align, int64_t *info);
+
+/* snvc_conv3d_forward / _forward_ex / _forward_head / _forward_side_head / _forward_stats (csrc/conv3d.hip): what the dispatcher
+ * itself launches for this call.  entry: which entry point is meant.  *_align: the largest of 16 / 8 / 4 that divides the address of
+ * x, y, the residual, the depth planes and y_head; 0 for a NULL pointer (y of forward_head; a residual or planes that are not
+ * given).  The families are tried in the order of the enum's sections; a layer that misses a condition of one goes to the next, and
+ * every layer make_plan accepts ends on the direct (or transposed) MFMA configuration of its key.  In the conditions:
+ *   vec16: Win % 4 == 0, x 16-byte aligned, x batch stride % 4 == 0;  vec8: the same for 2 and 8 bytes;
+ *   fastc: Dout*Hout*Wout < 2^27, Cout % 32 == 0, no Sigmoid, no SNVC_ALGO_GENERIC_EPILOGUE;
+ *   epi16: Wout % 4 == 0, y and residual batch strides % 4 == 0, y / residual / planes 16-byte aligned;  fast = fastc && epi16;
+ *   pair8: Wout % 2 == 0, y and residual batch strides % 2 == 0, y / residual (/ planes) 8-byte aligned;
+ *   stream16: x / y / residual 16-byte aligned, all three batch strides % 4 == 0.
+ * info: [0] bytes of an input staging piece (16 / 8 / 4), [1] the epilogue variant as the kernel's template argument -- direct forms:
+ *       EPI 0 generic, 1 fast, 2 fast with residual; transposed forms: EPI 0..2 as before, 3 / 4 fused head without / with residual,
+ *       5 statistics; Winograd forms: RES + 2 * PLANE + 4 * XMODE (XMODE 1 side head, 2 depth-4 average, 3 statistics); streaming
+ *       and VALU forms: 0, [2] tiles (direct, transposed, K3_COUT1), jobs (Winograd) or 16-byte pieces per channel (streaming forms),
+ *       [3] channel groups, [4] grid.x, [5] grid.y * grid.z, [6] threads per workgroup, [7] dynamic LDS bytes. */
+enum snvc_conv3d_forward_entry {
+    SNVC_CFE_FORWARD = 0,      /* snvc_conv3d_forward, snvc_conv3d_forward_ex */
+    SNVC_CFE_HEAD = 1,         /* snvc_conv3d_forward_head */
+    SNVC_CFE_SIDE_HEAD = 2,    /* snvc_conv3d_forward_side_head */
+    SNVC_CFE_STATS = 3         /* snvc_conv3d_forward_stats */
+};
+enum snvc_conv3d_forward_form_id {
+    /* streaming and VALU forms (not for depth-1 layers) */
+    SNVC_CF_POINTWISE_SMALL_1 = 1,  /* pointwise_small_kernel<1>: k1, stride 1, Cout == 1, D*H*W % 4 == 0, stream16 */
+    SNVC_CF_POINTWISE_SMALL_2 = 2,  /* pointwise_small_kernel<2>: the same with Cout == 2 */
+    SNVC_CF_POINTWISE_EXPAND_1 = 3, /* pointwise_expand_kernel<1>: k1, stride 1, Cin == 1, Cout > 2, D*H*W % 4 == 0, stream16, no planes /
+                                       head / statistics, no SNVC_ALGO arithmetic bits */
+    SNVC_CF_POINTWISE_EXPAND_2 = 4, /* pointwise_expand_kernel<2>: the same with Cin == 2 */
+    SNVC_CF_K3_COUT1 = 5,           /* conv3d_k3_cout1_kernel: 3x3x3, stride 1, dilation 1, Cout == 1, no planes */
+    SNVC_CF_DECONV_COUT1 = 6,       /* deconv3d_cout1_kernel (csrc/conv3d_small.hip): transposed, Cout == 1, no head, Win % 4 == 0, stream16 */
+    /* Winograd, 3x3x3 stride 2: vec16, fast or (fastc && pair8), no planes, not SNVC_ALGO_DIRECT */
+    SNVC_CF_WINO_S2_PIPE4 = 7,      /* conv3d_winos2_pipe_kernel<WinoS2PipeCfg<4>>: fast, not SNVC_ALGO_WINO_TILE_STD; carries the statistics */
+    SNVC_CF_WINO_S2_PIPE2 = 8,      /* conv3d_winos2_pipe_kernel<WinoS2PipeCfg<2>>: 8-byte output rows, not WINO_TILE_STD */
+    SNVC_CF_WINO_S2 = 9,            /* conv3d_winok_kernel<CfgWinoS2>: WINO_TILE_STD, fast */
+    SNVC_CF_WINO_S2_V8 = 10,        /* conv3d_winok_kernel<CfgWinoS2v8>: WINO_TILE_STD, 8-byte output rows */
+    /* Winograd, k5 / k7 stride 1: vec16, fast, no planes, not SNVC_ALGO_DIRECT */
+    SNVC_CF_WINO_K5 = 11,           /* conv3d_winok_kernel<CfgWinoK5> */
+    SNVC_CF_WINO_K5D2 = 12,         /* conv3d_winok_kernel<CfgWinoK5D2>: dilation 2 */
+    SNVC_CF_WINO_K7 = 13,           /* conv3d_winok_kernel<CfgWinoK7> */
+    /* Winograd, depth-1 3x3 stride 1 */
+    SNVC_CF_WINO_P = 14,            /* conv3d_wino_dma_kernel<CfgWinoP>: Hout, Wout >= 32, vec16, fast, not DIRECT, no planes / head / pooling /
+                                       statistics, SNVC_ALGO_WINO_TILE_BIG or at least two jobs (1 x 16 x 32 tiles) per CU */
+    /* Winograd, 3x3x3 stride 1: pair8, fastc, wide (vec16 && epi16) or vec8, not SNVC_ALGO_DIRECT */
+    SNVC_CF_WINO_BIG = 15,          /* conv3d_wino_dma_kernel<CfgWinoBig>: SNVC_ALGO_WINO_TILE_BIG and wide */
+    SNVC_CF_WINO_N3 = 16,           /* conv3d_wino_dma_kernel<CfgWinoN3>: the default form -- wide, no tile bits (or BIG without wide); the only
+                                       one that carries the side head, the depth-4 average and the statistics */
+    SNVC_CF_WINO_N = 17,            /* conv3d_wino_kernel<CfgWinoN>: SNVC_ALGO_WINO_TILE_NARROW_REG and wide */
+    SNVC_CF_WINO_N8 = 18,           /* conv3d_wino_kernel<CfgWinoN8>: not wide (8-byte rows), tile bits other than STD */
+    SNVC_CF_WINO = 19,              /* conv3d_wino_kernel<CfgWino>: SNVC_ALGO_WINO_TILE_STD and wide */
+    SNVC_CF_WINO8 = 20,             /* conv3d_wino_kernel<CfgWino8>: SNVC_ALGO_WINO_TILE_STD, not wide */
+    /* direct MFMA forms, by (ksize, stride, dilation); M2: Cout > 32.  EPI 1 / 2 where the configuration builds them (K3S2*, K5M1,
+     * K7M1, P3*): fast and no planes */
+    SNVC_CF_K1M1 = 21, SNVC_CF_K1M2 = 22,       /* conv3d_mfma_kernel<CfgK1M1 | CfgK1M2> */
+    SNVC_CF_K3M1 = 23, SNVC_CF_K3M2 = 24,       /* <CfgK3M1 | CfgK3M2> */
+    SNVC_CF_K3S2M1 = 25, SNVC_CF_K3S2M2 = 26,   /* <CfgK3S2M1 | CfgK3S2M2> */
+    SNVC_CF_K5M1 = 27, SNVC_CF_K5M2 = 28,       /* <CfgK5M1 | CfgK5M2> */
+    SNVC_CF_K5D2M1 = 29, SNVC_CF_K5D2M2 = 30,   /* <CfgK5D2M1 | CfgK5D2M2> */
+    SNVC_CF_K7M1 = 31, SNVC_CF_K7M2 = 32,       /* <CfgK7M1 | CfgK7M2> */
+    /* depth-1 direct forms (ksize_d == 1), one 32-channel group per workgroup */
+    SNVC_CF_P1M1S = 33,             /* <CfgP1M1s>: k1 */
+    SNVC_CF_P1S2M1S = 34,           /* <CfgP1S2M1s>: k1, stride 2 */
+    SNVC_CF_P3M1S = 35,             /* <CfgP3M1s>: k3 */
+    SNVC_CF_P3S2M1S = 36,           /* <CfgP3S2M1s>: k3, stride 2 */
+    SNVC_CF_P7M1S = 37,             /* <CfgP7M1s>: 3 (H) x 7 (W) */
+    SNVC_CF_P3D2M1S = 38,           /* <CfgP3D2M1s>: k3, dilation 2 */
+    /* transposed MFMA forms (k3, s2, p1, op1); y / residual 8-byte aligned.  EPI 3 / 4 (forward_head) and 5 (statistics) on DCM1 alone */
+    SNVC_CF_DCM1 = 39,              /* deconv3d_mfma_kernel<CfgDCM1>: Cout <= 32 or Cout % 32 == 0; vec16 or not even vec8 */
+    SNVC_CF_DCM2 = 40,              /* <CfgDCM2>: Cout > 32 and Cout % 32 != 0 */
+    SNVC_CF_DCM1_V8 = 41,           /* <CfgDCM1v8>: as DCM1, vec8 without vec16 */
+    SNVC_CF_DCM2_V8 = 42,           /* <CfgDCM2v8>: as DCM2, vec8 without vec16 */
+    SNVC_CF_DCP = 43,               /* <CfgDCP>: the depth-1 transposed layer */
+    SNVC_CF_DCP_V8 = 44             /* <CfgDCPv8>: vec8 without vec16 */
+};
+SNVC_API int snvc_conv3d_forward_form(const snvc_conv3d_desc *desc_host, int entry, int x_align, int y_align, int res_align,
+                                      int planes_align, int y_head_align, int64_t *info);
 
 #ifdef __cplusplus
 }

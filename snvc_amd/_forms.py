@@ -11,7 +11,7 @@ from typing import Tuple
 
 from . import _lib
 
-_ABI = 2   # snvc_forms_abi_version() this binding was written against
+_ABI = 3   # snvc_forms_abi_version() this binding was written against
 
 c_i64 = ctypes.c_int64
 c_p = ctypes.c_void_p
@@ -30,6 +30,7 @@ SIGNATURES = {
     "snvc_voxel_gather_forward_form": (c_int, [c_int] + [c_i64] * 5 + [c_f, c_f, c_int, c_p]),
     "snvc_voxel_gather_backward_form": (c_int, [c_i64] * 5 + [c_int, c_p]),
     "snvc_conv3d_wgrad_form": (c_int, [ctypes.POINTER(_lib.Conv3dDesc), c_int, c_int, c_p]),
+    "snvc_conv3d_forward_form": (c_int, [ctypes.POINTER(_lib.Conv3dDesc)] + [c_int] * 6 + [c_p]),
 }
 
 # info slot names per query (the header's comments)
@@ -39,6 +40,9 @@ GATHER_FWD_INFO = ("run", "nruns", "pow2", "slices", "grid_x", "grid_yz", "threa
 GATHER_BWD_INFO = ("vchunk", "nvchunks", "passes", "max_pieces", "grid_x", "grid_y", "threads", "lds")
 # slots 2 and 3 by form family: split-operand forms (dparts, dchunk), 12-wave forms (P, upx), k1 (chunks, -), generic (P, tap chunks)
 WGRAD_INFO = ("piece_bytes", "ws_bytes", "parts", "per_part", "grid_x", "grid_yz", "threads", "lds")
+# slot 2 by family: tiles (direct, transposed), jobs (Winograd), 16-byte pieces per channel (streaming)
+CONV_FWD_INFO = ("piece_bytes", "epi", "tiles", "groups", "grid_x", "grid_yz", "threads", "lds")
+ENTRY_FORWARD, ENTRY_HEAD, ENTRY_SIDE_HEAD, ENTRY_STATS = 0, 1, 2, 3
 
 _bound = None
 
@@ -94,3 +98,17 @@ def conv3d_wgrad(desc, x_align=16, g_align=16):
     that divides the address of x / g.  ``parts`` / ``per_part``: dparts / dchunk (split-operand forms), P / upx (12-wave forms),
     chunks / 0 (k1 streaming form), partitions / tap chunks (generic forms)."""
     return _query(lambda *a: lib().snvc_conv3d_wgrad_form(ctypes.byref(desc), *a), WGRAD_INFO, x_align, g_align)
+
+
+def conv3d_forward(desc, entry=ENTRY_FORWARD, x_align=16, y_align=16, res_align=0, planes_align=0, y_head_align=0):
+    """(form id, or 0 for no launch, or -status; info; error text) of the fp32 forward entry point ``entry`` for a
+    ``_lib.Conv3dDesc``.  Each ``*_align`` is the largest of 16 / 8 / 4 that divides the operand's address, 0 for NULL."""
+    return _query(lambda *a: lib().snvc_conv3d_forward_form(ctypes.byref(desc), *a), CONV_FWD_INFO, entry, x_align, y_align, res_align,
+                  planes_align, y_head_align)
+
+
+def address_align(ptr) -> int:
+    """The largest of 16 / 8 / 4 that divides ``ptr`` (a tensor's data_ptr()); 0 for None."""
+    if ptr is None:
+        return 0
+    return 16 if ptr % 16 == 0 else 8 if ptr % 8 == 0 else 4

@@ -40,6 +40,7 @@
 //                           fused 1x1x1 head (snvc_conv3d_forward_head)
 //   pointwise_small_kernel, conv3d_k3_cout1_kernel   VALU kernels for layers with 1-2 output channels
 #include "common.hpp"
+#include "snvc_forms.h"
 #include "conv3d_internal.hpp"
 #include "elementwise_internal.hpp"
 #include "wino_tables.hpp"
@@ -2217,13 +2218,59 @@ __global__ void pack_winos2_weights_kernel(const float *__restrict__ w, float *_
 }
 
 // ------------------------------------------------------------------------------------ dispatch
+struct Plan;
+
+// The packed fp32 weight buffer of a layer: [direct MFMA packing][Winograd packing][raw tail], in floats.
+struct PackedLayout {
+    int taps;                  // taps of the direct section
+    int64_t direct, wino, raw;
+    int64_t total() const { return direct + wino + raw; }
+    const float *wino_at(const float *packed) const { return packed + direct; }
+    const float *raw_at(const float *packed) const { return packed + direct + wino; }
+};
+
+// What a call launches: the form (snvc_conv3d_forward_form_id) and the launch numbers of snvc_conv3d_forward_form's `info`.
+struct Chosen {
+    int form;
+    int64_t info[SNVC_FORMS_INFO];
+};
+
+// What the kernel families ask about a call beyond its ConvArgs.  A family is `bool f(const Route &, ConvArgs &, int &rc)`: false
+// when it does not take the layer (the next one is tried), true with the call's status in rc when it does.
+struct Route {
+    const snvc_conv3d_desc &d;
+    const Plan &p;
+    PackedLayout w;
+    const float *packed_weight;
+    hipStream_t st;
+    Chosen *chosen;     // snvc_conv3d_forward_form: the families decide as ever, record here what they would launch, and launch
+                        // nothing (no pointer is read, no HIP call is made); NULL for the entry points
+    bool planar, side_head, pooled, direct_only;
+    bool vec8;          // input rows 8-byte aligned (a.vec: 16-byte)
+    bool fast_common;   // fast epilogues: (wave-uniform channel base) + 32-bit lane byte offsets, whole 32-channel groups, no Sigmoid
+    bool epi16;         // 16-byte stores: output rows, y, residual and depth planes allow them
+    bool stream16;      // x, y and the residual allow the streaming kernels' 16-byte accesses
+    int64_t S;          // output voxels per channel
+};
+
+// Every launch of the forward goes through take(): true when the caller is to launch (an entry point); false after recording the
+// launch for the query.  piece: floats per input staging piece; epi: the kernel's epilogue template argument (snvc_forms.h).
+inline bool take(const Route &r, int form, int piece, int epi, int64_t tiles, int64_t groups, dim3 g, int lds) {
+    if (!r.chosen) return true;
+    *r.chosen = Chosen{form, {4 * piece, epi, tiles, groups, (int64_t)g.x, (int64_t)g.y * g.z, 256, lds}};
+    return false;
+}
+// The status of a launch: the query made none
+inline int launched(const Route &r, const char *what) { return r.chosen ? SNVC_OK : check_launch(what); }
+
 struct Plan {
     int MI, KC, TD, TH;  // tile choice
     int groups, nchunks;
     int tiles_d, tiles_h, tiles_w;
     // the direct / transposed MFMA kernel of the configuration; vec8: the rows are 8-byte aligned (the transposed forms have a
     // configuration for them)
-    void (*launch)(ConvArgs &a, bool vec8, dim3 grid, hipStream_t st);
+    void (*launch)(const Route &r, ConvArgs &a, dim3 grid);
+    int form, form_v8;   // snvc_conv3d_forward_form_id of the configuration, and of its 8-byte-row twin (transposed forms)
     bool dc_m1;  // the single-group ConvTranspose3d form (CfgDCM1): the one that carries the fused head and the statistics epilogue
 };
 
@@ -2282,48 +2329,51 @@ using CfgDCPv8  = DeconvCfg<1, 1, 8, 4, 2>;
 
 // FAST: also build the fast-epilogue variants of this configuration (the ones on a measured path)
 template <class Cfg, bool FAST>
-void launch_conv(ConvArgs &a, bool, dim3 grid, hipStream_t st) {
+void launch_conv(const Route &r, ConvArgs &a, dim3 grid) {
+    const auto go = [&](int epi) { return take(r, r.p.form, a.vec ? 4 : 1, epi, grid.x, grid.y, grid, Cfg::LDS_BYTES); };
     if constexpr (FAST) {
         if (a.fast_epi && !a.plane) {
-            if (a.res) launch_lds<conv3d_mfma_kernel<Cfg, 2>>(grid, 256, Cfg::LDS_BYTES, st, a);
-            else launch_lds<conv3d_mfma_kernel<Cfg, 1>>(grid, 256, Cfg::LDS_BYTES, st, a);
+            if (a.res) { if (go(2)) launch_lds<conv3d_mfma_kernel<Cfg, 2>>(grid, 256, Cfg::LDS_BYTES, r.st, a); }
+            else if (go(1)) launch_lds<conv3d_mfma_kernel<Cfg, 1>>(grid, 256, Cfg::LDS_BYTES, r.st, a);
             return;
         }
     }
-    launch_lds<conv3d_mfma_kernel<Cfg, 0>>(grid, 256, Cfg::LDS_BYTES, st, a);
+    if (go(0)) launch_lds<conv3d_mfma_kernel<Cfg, 0>>(grid, 256, Cfg::LDS_BYTES, r.st, a);
 }
 
 template <class Cfg>
-void launch_deconv(const ConvArgs &a, dim3 grid, hipStream_t st) {
+void launch_deconv(const Route &r, const ConvArgs &a, int form, dim3 grid) {
     constexpr int BYTES = Cfg::LDS_BYTES;
+    const hipStream_t st = r.st;
+    const auto go = [&](int epi) { return take(r, form, a.vec ? Cfg::PIECE : 1, epi, grid.x, grid.y, grid, BYTES); };
     // the pair exchange of the fast epilogue needs an even input width (both lanes of a pair in range)
     if (a.stats) {    // validated by conv3d_forward_impl: fast epilogue conditions, one channel group per workgroup, no addends
-        if constexpr (Cfg::MI == 1) launch_lds<deconv3d_mfma_kernel<Cfg, 5>>(grid, 256, BYTES, st, a);
+        if constexpr (Cfg::MI == 1) { if (go(5)) launch_lds<deconv3d_mfma_kernel<Cfg, 5>>(grid, 256, BYTES, st, a); }
     } else if (a.head_w) {   // validated by snvc_conv3d_forward_head: fast epilogue conditions hold, one channel group
         if constexpr (Cfg::MI == 1) {
-            if (a.res) launch_lds<deconv3d_mfma_kernel<Cfg, 4>>(grid, 256, BYTES, st, a);
-            else launch_lds<deconv3d_mfma_kernel<Cfg, 3>>(grid, 256, BYTES, st, a);
+            if (a.res) { if (go(4)) launch_lds<deconv3d_mfma_kernel<Cfg, 4>>(grid, 256, BYTES, st, a); }
+            else if (go(3)) launch_lds<deconv3d_mfma_kernel<Cfg, 3>>(grid, 256, BYTES, st, a);
         }
     } else if (a.fast_epi && a.Win % 2 == 0) {
-        if (a.res) launch_lds<deconv3d_mfma_kernel<Cfg, 2>>(grid, 256, BYTES, st, a);
-        else launch_lds<deconv3d_mfma_kernel<Cfg, 1>>(grid, 256, BYTES, st, a);
+        if (a.res) { if (go(2)) launch_lds<deconv3d_mfma_kernel<Cfg, 2>>(grid, 256, BYTES, st, a); }
+        else if (go(1)) launch_lds<deconv3d_mfma_kernel<Cfg, 1>>(grid, 256, BYTES, st, a);
     } else {
-        launch_lds<deconv3d_mfma_kernel<Cfg, 0>>(grid, 256, BYTES, st, a);
+        if (go(0)) launch_lds<deconv3d_mfma_kernel<Cfg, 0>>(grid, 256, BYTES, st, a);
     }
 }
 
 // Cfg on 16-byte rows (or unaligned ones), CfgV8 on rows that are only 8-byte aligned
 template <class Cfg, class CfgV8>
-void launch_deconv_rows(ConvArgs &a, bool vec8, dim3 grid, hipStream_t st) {
-    if (!a.vec && vec8) { a.vec = 1; launch_deconv<CfgV8>(a, grid, st); }
-    else launch_deconv<Cfg>(a, grid, st);
+void launch_deconv_rows(const Route &r, ConvArgs &a, dim3 grid) {
+    if (!a.vec && r.vec8) { a.vec = 1; launch_deconv<CfgV8>(r, a, r.p.form_v8, grid); }
+    else launch_deconv<Cfg>(r, a, r.p.form, grid);
 }
 
 template <class Cfg, bool FAST = false>
-constexpr Plan plan_of() { return Plan{Cfg::MI, Cfg::KC, Cfg::TD, Cfg::TH, 0, 0, 0, 0, 0, &launch_conv<Cfg, FAST>, false}; }
+constexpr Plan plan_of(int form) { return Plan{Cfg::MI, Cfg::KC, Cfg::TD, Cfg::TH, 0, 0, 0, 0, 0, &launch_conv<Cfg, FAST>, form, 0, false}; }
 template <class Cfg, class CfgV8>
-constexpr Plan deconv_plan_of(bool dc_m1 = false) {
-    return Plan{Cfg::MI, Cfg::KC, Cfg::TD, Cfg::TH, 0, 0, 0, 0, 0, &launch_deconv_rows<Cfg, CfgV8>, dc_m1};
+constexpr Plan deconv_plan_of(int form, int form_v8, bool dc_m1 = false) {
+    return Plan{Cfg::MI, Cfg::KC, Cfg::TD, Cfg::TH, 0, 0, 0, 0, 0, &launch_deconv_rows<Cfg, CfgV8>, form, form_v8, dc_m1};
 }
 
 int make_plan(const snvc_conv3d_desc &d, Plan &p) {
@@ -2336,14 +2386,15 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
         if (d.ksize_d == 1) {   // depth-1 form: [N,C,1,H,W] -> [N,C,1,2H,2W]; the weight is the 2D kernel on the kd = 1 plane of a 3x3x3 one
             if (d.Din != 1 || d.Dout != 1 || d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win || (d.ksize_h != 0 && d.ksize_h != 3))
                 return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d: a depth-1 transposed layer maps [1,H,W] to [1,2H,2W]");
-            p = deconv_plan_of<CfgDCP, CfgDCPv8>();
+            p = deconv_plan_of<CfgDCP, CfgDCPv8>(SNVC_CF_DCP, SNVC_CF_DCP_V8);
             p.tiles_d = 1; p.tiles_h = ceil_div(d.Hin, p.TH); p.tiles_w = ceil_div(d.Win, 32);
         } else {
         if (d.Dout != 2 * d.Din || d.Hout != 2 * d.Hin || d.Wout != 2 * d.Win)
             return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d: transposed output must be 2x the input");
         // whole 32-channel groups run the single-group form (128 VGPRs: four workgroups per CU); the 64-channel
         // form only remains for channel counts that are not multiples of 32
-        p = (wide && d.Cout % 32 != 0) ? deconv_plan_of<CfgDCM2, CfgDCM2v8>() : deconv_plan_of<CfgDCM1, CfgDCM1v8>(true);
+        p = (wide && d.Cout % 32 != 0) ? deconv_plan_of<CfgDCM2, CfgDCM2v8>(SNVC_CF_DCM2, SNVC_CF_DCM2_V8)
+                                       : deconv_plan_of<CfgDCM1, CfgDCM1v8>(SNVC_CF_DCM1, SNVC_CF_DCM1_V8, true);
         p.tiles_d = ceil_div(d.Din, p.TD); p.tiles_h = ceil_div(d.Hin, p.TH); p.tiles_w = ceil_div(d.Win, 32);
         }
     } else if (d.ksize_d == 1) {
@@ -2367,12 +2418,12 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
         // one 32-channel group per workgroup on 1 x 4 x 32 tiles whatever the layer (see CfgP*s above)
         (void)wide;
         switch (key) {
-            case 11: p = plan_of<CfgP1M1s>(); break;
-            case 12: p = plan_of<CfgP1S2M1s>(); break;
-            case 31: p = plan_of<CfgP3M1s, true>(); break;
-            case 32: p = plan_of<CfgP3S2M1s, true>(); break;
-            case 71: p = plan_of<CfgP7M1s>(); break;
-            case 312: p = plan_of<CfgP3D2M1s, true>(); break;
+            case 11: p = plan_of<CfgP1M1s>(SNVC_CF_P1M1S); break;
+            case 12: p = plan_of<CfgP1S2M1s>(SNVC_CF_P1S2M1S); break;
+            case 31: p = plan_of<CfgP3M1s, true>(SNVC_CF_P3M1S); break;
+            case 32: p = plan_of<CfgP3S2M1s, true>(SNVC_CF_P3S2M1S); break;
+            case 71: p = plan_of<CfgP7M1s>(SNVC_CF_P7M1S); break;
+            case 312: p = plan_of<CfgP3D2M1s, true>(SNVC_CF_P3D2M1S); break;
             default: return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d: depth-1 layers are built for ksize 1 and 3 (stride 1 and 2) and 3 x 7 (stride 1)");
         }
         p.tiles_d = 1; p.tiles_h = ceil_div(d.Hout, p.TH); p.tiles_w = ceil_div(d.Wout, 32);
@@ -2390,12 +2441,12 @@ int make_plan(const snvc_conv3d_desc &d, Plan &p) {
             return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d: output size does not match the convolution arithmetic");
         const int key = d.ksize * 100 + d.stride * 10 + d.dilation;
         switch (key) {
-            case 111: p = wide ? plan_of<CfgK1M2>() : plan_of<CfgK1M1>(); break;
-            case 311: p = wide ? plan_of<CfgK3M2>() : plan_of<CfgK3M1>(); break;
-            case 321: p = wide ? plan_of<CfgK3S2M2, true>() : plan_of<CfgK3S2M1, true>(); break;
-            case 511: p = wide ? plan_of<CfgK5M2>() : plan_of<CfgK5M1, true>(); break;
-            case 512: p = wide ? plan_of<CfgK5D2M2>() : plan_of<CfgK5D2M1>(); break;
-            case 711: p = wide ? plan_of<CfgK7M2>() : plan_of<CfgK7M1, true>(); break;
+            case 111: p = wide ? plan_of<CfgK1M2>(SNVC_CF_K1M2) : plan_of<CfgK1M1>(SNVC_CF_K1M1); break;
+            case 311: p = wide ? plan_of<CfgK3M2>(SNVC_CF_K3M2) : plan_of<CfgK3M1>(SNVC_CF_K3M1); break;
+            case 321: p = wide ? plan_of<CfgK3S2M2, true>(SNVC_CF_K3S2M2) : plan_of<CfgK3S2M1, true>(SNVC_CF_K3S2M1); break;
+            case 511: p = wide ? plan_of<CfgK5M2>(SNVC_CF_K5M2) : plan_of<CfgK5M1, true>(SNVC_CF_K5M1); break;
+            case 512: p = wide ? plan_of<CfgK5D2M2>(SNVC_CF_K5D2M2) : plan_of<CfgK5D2M1>(SNVC_CF_K5D2M1); break;
+            case 711: p = wide ? plan_of<CfgK7M2>(SNVC_CF_K7M2) : plan_of<CfgK7M1, true>(SNVC_CF_K7M1); break;
             default:
                 return fail(SNVC_ERR_UNSUPPORTED,
                             "snvc_conv3d: (ksize,stride,dilation) not in {(1,1,1),(3,1,1),(3,2,1),(5,1,1),(5,1,2),(7,1,1)}");
@@ -2430,15 +2481,6 @@ inline int64_t wino_packed_count(const snvc_conv3d_desc &d) {
     return 0;
 }
 
-// The packed fp32 weight buffer of a layer: [direct MFMA packing][Winograd packing][raw tail], in floats.
-struct PackedLayout {
-    int taps;                  // taps of the direct section
-    int64_t direct, wino, raw;
-    int64_t total() const { return direct + wino + raw; }
-    const float *wino_at(const float *packed) const { return packed + direct; }
-    const float *raw_at(const float *packed) const { return packed + direct + wino; }
-};
-
 PackedLayout packed_layout(const snvc_conv3d_desc &d, const Plan &p) {
     const bool planar = d.ksize_d == 1;      // depth-1 layer: 1 x kh x k taps, never a raw tail
     PackedLayout w;
@@ -2462,20 +2504,29 @@ static_assert(CfgWino::KC == 2 && CfgWinoP::KC == 2 && CfgWinoS2::KC == 2 && Cfg
 template <class Cfg, int XMODE = 0>
 constexpr int wino_lds_bytes = Cfg::LDS_BYTES + (XMODE == 1 ? 384 : 256);
 
+// The epilogue variant of a Winograd kernel as the query reports it: RES + 2 * PLANE (+ 4 * XMODE for the side-head, pooled
+// and statistics variants)
+inline int wino_epi(const ConvArgs &a, int xmode = 0) { return (a.res ? 1 : 0) + (a.plane ? 2 : 0) + 4 * xmode; }
+
 template <class Cfg>
-void launch_winok(const ConvArgs &a, dim3 grid, hipStream_t st) {
-    if (a.res) launch_lds<conv3d_winok_kernel<Cfg, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
-    else launch_lds<conv3d_winok_kernel<Cfg, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
+void launch_winok(const Route &r, int form, const ConvArgs &a, dim3 grid) {
+    if (!take(r, form, Cfg::PIECE, wino_epi(a), a.njobs, a.groups, grid, wino_lds_bytes<Cfg>)) return;
+    if (a.res) launch_lds<conv3d_winok_kernel<Cfg, true>>(grid, 256, wino_lds_bytes<Cfg>, r.st, a);
+    else launch_lds<conv3d_winok_kernel<Cfg, false>>(grid, 256, wino_lds_bytes<Cfg>, r.st, a);
 }
 
 template <class Cfg>
-void launch_winos2_pipe(const ConvArgs &a, dim3 grid, hipStream_t st) {
+void launch_winos2_pipe(const Route &r, int form, const ConvArgs &a, dim3 grid) {
+    const hipStream_t st = r.st;
+    if (!take(r, form, Cfg::PIECE, wino_epi(a), a.njobs, a.groups, grid, wino_lds_bytes<Cfg>)) return;
     if (a.res) launch_lds<conv3d_winos2_pipe_kernel<Cfg, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
     else launch_lds<conv3d_winos2_pipe_kernel<Cfg, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
 }
 
 template <class Cfg>
-void launch_wino_dma(const ConvArgs &a, dim3 grid, hipStream_t st) {
+void launch_wino_dma(const Route &r, int form, const ConvArgs &a, dim3 grid) {
+    const hipStream_t st = r.st;
+    if (!take(r, form, Cfg::PIECE, wino_epi(a), a.njobs, a.groups, grid, wino_lds_bytes<Cfg>)) return;
     if (a.res && a.plane) launch_lds<conv3d_wino_dma_kernel<Cfg, true, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
     else if (a.res) launch_lds<conv3d_wino_dma_kernel<Cfg, true, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
     else if (a.plane) launch_lds<conv3d_wino_dma_kernel<Cfg, false, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
@@ -2483,7 +2534,9 @@ void launch_wino_dma(const ConvArgs &a, dim3 grid, hipStream_t st) {
 }
 
 template <class Cfg>
-void launch_wino(const ConvArgs &a, dim3 grid, hipStream_t st) {
+void launch_wino(const Route &r, int form, const ConvArgs &a, dim3 grid) {
+    const hipStream_t st = r.st;
+    if (!take(r, form, Cfg::PIECE, wino_epi(a), a.njobs, a.groups, grid, wino_lds_bytes<Cfg>)) return;
     if (a.res && a.plane) launch_lds<conv3d_wino_kernel<Cfg, true, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
     else if (a.res) launch_lds<conv3d_wino_kernel<Cfg, true, false>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
     else if (a.plane) launch_lds<conv3d_wino_kernel<Cfg, false, true>>(grid, 256, wino_lds_bytes<Cfg>, st, a);
@@ -2496,7 +2549,7 @@ void launch_wino(const ConvArgs &a, dim3 grid, hipStream_t st) {
 namespace snvc {
 int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *packed_weight, const float *scale,
                         const float *bias, const float *residual, const float *depth_planes, float *y,
-                        const float *head_w, float *y_head, void *stream, double *stats = nullptr);
+                        const float *head_w, float *y_head, void *stream, double *stats = nullptr, Chosen *chosen = nullptr);
 
 namespace {
 // stats[((n * tiles + t) * groups + cg)][32][2] -> partial[(n * C + c)][2]: one workgroup per (n, c), fixed-order tree
@@ -2568,7 +2621,71 @@ void launch_conv_stats_fold(const double *stats, double *scratch, double *partia
 }
 }
 
+namespace snvc {
+namespace {
+// What snvc_conv3d_forward_head and snvc_conv3d_forward_stats ask of the layer before the dispatcher sees it (the query asks
+// the same)
+int head_entry_check(const snvc_conv3d_desc &d, const float *residual, const float *y_head) {
+    if (!d.transposed || d.Cout != 32 || d.Win % 2 != 0 || (d.flags & SNVC_EPI_SIGMOID) ||
+        (int64_t)d.Dout * d.Hout * d.Wout >= ((int64_t)1 << 27) || !aligned(8, y_head) || !aligned(16, residual) ||
+        (d.res_batch_stride % 4) != 0)
+        return fail(SNVC_ERR_UNSUPPORTED,
+                    "snvc_conv3d_forward_head: needs a transposed layer with 32 output channels, an even input width, "
+                    "no Sigmoid, a 16-byte aligned residual and an 8-byte aligned head output");
+    return SNVC_OK;
+}
+int stats_entry_check(const snvc_conv3d_desc &d) {
+    if (d.N <= 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_stats: empty batch");
+    if (d.flags || d.ksize_d == 1 || d.ksize != 3 || d.dilation != 1 || (d.stride != 1 && d.stride != 2) || d.Cout % 32 != 0 ||
+        (d.transposed && d.stride != 2))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: built for 3x3x3 Conv3d layers (stride 1 or 2) and "
+                                          "ConvTranspose3d(k3,s2,p1,op1) with whole 32-channel groups and no epilogue");
+    return SNVC_OK;
+}
+}  // namespace
+}  // namespace snvc
+
 extern "C" {
+
+// include/snvc_forms.h: the dispatcher itself, asked what it would launch.  The operands stand in as addresses of the given
+// alignment (0: NULL); conv3d_forward_impl reads none of them when it is given a record to fill.
+int snvc_conv3d_forward_form(const snvc_conv3d_desc *d, int entry, int x_align, int y_align, int res_align, int planes_align,
+                             int y_head_align, int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_form: null info");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    const auto valid = [](int a) { return a == 0 || a == 4 || a == 8 || a == 16; };
+    if (!d || entry < SNVC_CFE_FORWARD || entry > SNVC_CFE_STATS || !valid(x_align) || !valid(y_align) || !valid(res_align) ||
+        !valid(planes_align) || !valid(y_head_align))
+        return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_form: null desc, unknown entry point or an alignment that is not 16 / 8 / 4 / 0");
+    const auto at = [](int a) { return reinterpret_cast<float *>(static_cast<uintptr_t>(a)); };
+    float *const some = at(16);     // stands for the operands whose address decides nothing (weights, head weights, workspace)
+    const float *x = at(x_align), *residual = at(res_align), *planes = at(planes_align), *head_w = nullptr;
+    float *y = at(y_align), *y_head = at(y_head_align);
+    double *stats = nullptr;
+    switch (entry) {
+        case SNVC_CFE_FORWARD: y_head = nullptr; break;
+        case SNVC_CFE_HEAD:
+            if (!y_head) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_head: null pointer");
+            if (const int rc = head_entry_check(*d, residual, y_head)) return -rc;
+            head_w = some; y = nullptr; planes = nullptr;
+            break;
+        case SNVC_CFE_SIDE_HEAD:
+            if (!y || !y_head) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_side_head: null pointer");
+            head_w = some; planes = nullptr;
+            break;
+        default:
+            if (!y) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_stats: null pointer");
+            if (const int rc = stats_entry_check(*d)) return -rc;
+            residual = nullptr; planes = nullptr; y_head = nullptr;
+            stats = reinterpret_cast<double *>(some);
+            break;
+    }
+    Chosen c{};
+    if (const int rc = conv3d_forward_impl(d, x, some, nullptr, nullptr, residual, planes, y, head_w, y_head, nullptr, stats, &c)) return -rc;
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = c.info[i];
+    return c.form;
+}
 
 int64_t snvc_conv3d_packed_weight_count(const snvc_conv3d_desc *d) {
     using namespace snvc;
@@ -2631,12 +2748,7 @@ int snvc_conv3d_forward_head(const snvc_conv3d_desc *d, const float *x, const fl
                              const float *head_weight, float *y_head, void *stream) {
     using namespace snvc;
     if (!d || !head_weight || !y_head) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_head: null pointer");
-    if (!d->transposed || d->Cout != 32 || d->Win % 2 != 0 || (d->flags & SNVC_EPI_SIGMOID) ||
-        (int64_t)d->Dout * d->Hout * d->Wout >= ((int64_t)1 << 27) || !aligned(8, y_head) || !aligned(16, residual) ||
-        (d->res_batch_stride % 4) != 0)
-        return fail(SNVC_ERR_UNSUPPORTED,
-                    "snvc_conv3d_forward_head: needs a transposed layer with 32 output channels, an even input width, "
-                    "no Sigmoid, a 16-byte aligned residual and an 8-byte aligned head output");
+    if (const int rc = head_entry_check(*d, residual, y_head)) return rc;
     return conv3d_forward_impl(d, x, packed_weight, scale, bias, residual, nullptr, nullptr, head_weight, y_head, stream);
 }
 
@@ -2660,11 +2772,7 @@ int snvc_conv3d_forward_stats(const snvc_conv3d_desc *d, const float *x, const f
                               void *stream) {
     using namespace snvc;
     if (!d || !y || !scale || !shift || !workspace) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_stats: null pointer");
-    if (d->N <= 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward_stats: empty batch");
-    if (d->flags || d->ksize_d == 1 || d->ksize != 3 || d->dilation != 1 || (d->stride != 1 && d->stride != 2) || d->Cout % 32 != 0 ||
-        (d->transposed && d->stride != 2))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: built for 3x3x3 Conv3d layers (stride 1 or 2) and "
-                                          "ConvTranspose3d(k3,s2,p1,op1) with whole 32-channel groups and no epilogue");
+    if (const int rc0 = stats_entry_check(*d)) return rc0;
     double *stats = static_cast<double *>(workspace);
     int rc = conv3d_forward_impl(d, x, packed_weight, nullptr, nullptr, nullptr, nullptr, y, nullptr, nullptr, stream, stats);
     if (rc) return rc;
@@ -2684,22 +2792,6 @@ int snvc_conv3d_forward_stats(const snvc_conv3d_desc *d, const float *x, const f
 namespace snvc {
 namespace {
 
-// What the kernel families ask about a call beyond its ConvArgs.  A family is `bool f(const Route &, ConvArgs &, int &rc)`: false
-// when it does not take the layer (the next one is tried), true with the call's status in rc when it does.
-struct Route {
-    const snvc_conv3d_desc &d;
-    const Plan &p;
-    PackedLayout w;
-    const float *packed_weight;
-    hipStream_t st;
-    bool planar, side_head, pooled, direct_only;
-    bool vec8;          // input rows 8-byte aligned (a.vec: 16-byte)
-    bool fast_common;   // fast epilogues: (wave-uniform channel base) + 32-bit lane byte offsets, whole 32-channel groups, no Sigmoid
-    bool epi16;         // 16-byte stores: output rows, y, residual and depth planes allow them
-    bool stream16;      // x, y and the residual allow the streaming kernels' 16-byte accesses
-    int64_t S;          // output voxels per channel
-};
-
 inline dim3 stream_grid(const Route &r) {
     int64_t blocks = ceil_div<int64_t>(r.S / 4, 256);
     if (blocks > 4096) blocks = 4096;
@@ -2711,11 +2803,13 @@ bool pointwise_to_few(const Route &r, ConvArgs &a, int &rc) {
     const snvc_conv3d_desc &d = r.d;
     if (r.planar || d.transposed || d.ksize != 1 || d.stride != 1 || d.Cout > 2 || (r.S % 4) != 0 || !r.stream16) return false;
     const float *wraw = r.w.raw_at(r.packed_weight);
+    const dim3 g = stream_grid(r);
+    if (!take(r, d.Cout == 1 ? SNVC_CF_POINTWISE_SMALL_1 : SNVC_CF_POINTWISE_SMALL_2, 4, 0, r.S / 4, 1, g, 0)) { rc = SNVC_OK; return true; }
     if (d.Cout == 1)
-        pointwise_small_kernel<1><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cin, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+        pointwise_small_kernel<1><<<g, 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cin, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
     else
-        pointwise_small_kernel<2><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cin, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
-    rc = check_launch("snvc_conv3d_forward(pointwise)");
+        pointwise_small_kernel<2><<<g, 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cin, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+    rc = launched(r, "snvc_conv3d_forward(pointwise)");
     return true;
 }
 
@@ -2726,11 +2820,13 @@ bool pointwise_from_few(const Route &r, ConvArgs &a, int &rc) {
         a.stats || (d.algo & SNVC_ALGO_ARITH_MASK) != 0 || !r.stream16)
         return false;
     const float *wraw = r.w.raw_at(r.packed_weight);
+    const dim3 g = stream_grid(r);
+    if (!take(r, d.Cin == 1 ? SNVC_CF_POINTWISE_EXPAND_1 : SNVC_CF_POINTWISE_EXPAND_2, 4, 0, r.S / 4, 1, g, 0)) { rc = SNVC_OK; return true; }
     if (d.Cin == 1)
-        pointwise_expand_kernel<1><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cout, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+        pointwise_expand_kernel<1><<<g, 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cout, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
     else
-        pointwise_expand_kernel<2><<<stream_grid(r), 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cout, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
-    rc = check_launch("snvc_conv3d_forward(pointwise expand)");
+        pointwise_expand_kernel<2><<<g, 256, 0, r.st>>>(a.x, wraw, a.scale, a.bias, a.res, a.y, d.Cout, r.S, a.x_bs, a.y_bs, a.r_bs, d.flags);
+    rc = launched(r, "snvc_conv3d_forward(pointwise expand)");
     return true;
 }
 
@@ -2741,17 +2837,21 @@ bool k3_to_one(const Route &r, ConvArgs &a, int &rc) {
     const int th_ = ceil_div(d.Hout, K3C1_TH), tw_ = ceil_div(d.Wout, 32);
     const int64_t nt = (int64_t)ceil_div(d.Dout, K3C1_TD) * th_ * tw_;
     if (nt >= ((int64_t)1 << 31) || d.N > 65535) return false;
-    conv3d_k3_cout1_kernel<<<dim3((unsigned)nt, (unsigned)d.N), 256, 0, r.st>>>(a.x, r.w.raw_at(r.packed_weight), a.scale, a.bias, a.res, a.y, d.Cin, d.Dout,
+    const dim3 g((unsigned)nt, (unsigned)d.N);
+    if (!take(r, SNVC_CF_K3_COUT1, 1, 0, nt, 1, g, 0)) { rc = SNVC_OK; return true; }
+    conv3d_k3_cout1_kernel<<<g, 256, 0, r.st>>>(a.x, r.w.raw_at(r.packed_weight), a.scale, a.bias, a.res, a.y, d.Cin, d.Dout,
                                                                                 d.Hout, d.Wout, th_, tw_, a.x_bs, a.y_bs, a.r_bs, d.flags);
-    rc = check_launch("snvc_conv3d_forward(k3 to one channel)");
+    rc = launched(r, "snvc_conv3d_forward(k3 to one channel)");
     return true;
 }
 
 // transposed layer to ONE channel (the folded hourglass tail + classifier): VALU kernel, raw weights as above
 bool transposed_to_one(const Route &r, ConvArgs &a, int &rc) {
     if (r.planar || a.head_w || !deconv3d_cout1_qualifies(r.d, a.x, a.y, a.res, a.x_bs, a.y_bs, a.r_bs)) return false;
+    const int64_t quads = (int64_t)r.d.Din * r.d.Hin * (r.d.Win / 4);      // one thread per four input voxels of a row
+    if (!take(r, SNVC_CF_DECONV_COUT1, 4, 0, quads, 1, dim3((unsigned)ceil_div<int64_t>(quads, 256), (unsigned)r.d.N), 0)) { rc = SNVC_OK; return true; }
     deconv3d_cout1_launch(r.d, a.x, r.w.raw_at(r.packed_weight), a.scale, a.bias, a.res, a.y, a.x_bs, a.y_bs, a.r_bs, r.st);
-    rc = check_launch("snvc_conv3d_forward(transposed to one channel)");
+    rc = launched(r, "snvc_conv3d_forward(transposed to one channel)");
     return true;
 }
 
@@ -2786,16 +2886,17 @@ bool winograd_stride2(const Route &r, ConvArgs &a, int &rc) {
         if (per_chunk || !a.fast_epi || a.res)
             rc = fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: this stride-2 layer does not take the default kernel form");
         else {
-            launch_lds<conv3d_winos2_pipe_kernel<Cfg, false, 3>>(g, 256, wino_lds_bytes<Cfg>, r.st, a);
-            rc = check_launch("snvc_conv3d_forward_stats(winograd stride 2)");
+            if (take(r, SNVC_CF_WINO_S2_PIPE4, Cfg::PIECE, wino_epi(a, 3), a.njobs, a.groups, g, wino_lds_bytes<Cfg>))
+                launch_lds<conv3d_winos2_pipe_kernel<Cfg, false, 3>>(g, 256, wino_lds_bytes<Cfg>, r.st, a);
+            rc = launched(r, "snvc_conv3d_forward_stats(winograd stride 2)");
         }
         return true;
     }
-    if (per_chunk && a.fast_epi) launch_winok<CfgWinoS2>(a, g, r.st);
-    else if (per_chunk) launch_winok<CfgWinoS2v8>(a, g, r.st);
-    else if (a.fast_epi) launch_winos2_pipe<WinoS2PipeCfg<4>>(a, g, r.st);
-    else launch_winos2_pipe<WinoS2PipeCfg<2>>(a, g, r.st);
-    rc = check_launch("snvc_conv3d_forward(winograd stride 2)");
+    if (per_chunk && a.fast_epi) launch_winok<CfgWinoS2>(r, SNVC_CF_WINO_S2, a, g);
+    else if (per_chunk) launch_winok<CfgWinoS2v8>(r, SNVC_CF_WINO_S2_V8, a, g);
+    else if (a.fast_epi) launch_winos2_pipe<WinoS2PipeCfg<4>>(r, SNVC_CF_WINO_S2_PIPE4, a, g);
+    else launch_winos2_pipe<WinoS2PipeCfg<2>>(r, SNVC_CF_WINO_S2_PIPE2, a, g);
+    rc = launched(r, "snvc_conv3d_forward(winograd stride 2)");
     return true;
 }
 
@@ -2806,10 +2907,10 @@ bool winograd_k5k7(const Route &r, ConvArgs &a, int &rc) {
         !a.vec || !a.fast_epi || a.plane || r.direct_only || !wino_job_grid(r, a, 4, 4, 32))
         return false;
     const dim3 g((unsigned)a.njobs, 1, 1);
-    if (d.ksize == 5 && d.dilation == 2) launch_winok<CfgWinoK5D2>(a, g, r.st);
-    else if (d.ksize == 5) launch_winok<CfgWinoK5>(a, g, r.st);
-    else launch_winok<CfgWinoK7>(a, g, r.st);
-    rc = check_launch("snvc_conv3d_forward(winograd k5/k7)");
+    if (d.ksize == 5 && d.dilation == 2) launch_winok<CfgWinoK5D2>(r, SNVC_CF_WINO_K5D2, a, g);
+    else if (d.ksize == 5) launch_winok<CfgWinoK5>(r, SNVC_CF_WINO_K5, a, g);
+    else launch_winok<CfgWinoK7>(r, SNVC_CF_WINO_K7, a, g);
+    rc = launched(r, "snvc_conv3d_forward(winograd k5/k7)");
     return true;
 }
 
@@ -2825,8 +2926,8 @@ bool winograd_depth1(const Route &r, ConvArgs &a, int &rc) {
     if (!(forced || wino_job_count(d, 1, CfgWinoP::TH, CfgWinoP::TW) >= 2 * device_cu_count()) ||
         !wino_job_grid(r, a, 1, CfgWinoP::TH, CfgWinoP::TW))
         return false;
-    launch_wino_dma<CfgWinoP>(a, dim3((unsigned)a.njobs, 1, 1), r.st);
-    rc = check_launch("snvc_conv3d_forward(depth-1 winograd)");
+    launch_wino_dma<CfgWinoP>(r, SNVC_CF_WINO_P, a, dim3((unsigned)a.njobs, 1, 1));
+    rc = launched(r, "snvc_conv3d_forward(depth-1 winograd)");
     return true;
 }
 
@@ -2854,31 +2955,34 @@ bool winograd_k3(const Route &r, ConvArgs &a, int &rc) {
                                             "channels, no residual / depth planes and a 16-byte aligned y_head");
             return true;
         }
-        launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 1>>(g, 256, wino_lds_bytes<CfgWinoN3, 1>, r.st, a);
-        rc = check_launch("snvc_conv3d_forward_side_head");
+        if (take(r, SNVC_CF_WINO_N3, CfgWinoN3::PIECE, wino_epi(a, 1), a.njobs, a.groups, g, wino_lds_bytes<CfgWinoN3, 1>))
+            launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 1>>(g, 256, wino_lds_bytes<CfgWinoN3, 1>, r.st, a);
+        rc = launched(r, "snvc_conv3d_forward_side_head");
     } else if (a.stats) {       // the default kernel form without addends carries the statistics epilogue
         if (!dflt || a.res || a.plane) {
             rc = fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward_stats: this layer does not take the default Winograd form");
             return true;
         }
-        launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 3>>(g, 256, wino_lds_bytes<CfgWinoN3, 3>, r.st, a);
-        rc = check_launch("snvc_conv3d_forward_stats(winograd)");
+        if (take(r, SNVC_CF_WINO_N3, CfgWinoN3::PIECE, wino_epi(a, 3), a.njobs, a.groups, g, wino_lds_bytes<CfgWinoN3, 3>))
+            launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 3>>(g, 256, wino_lds_bytes<CfgWinoN3, 3>, r.st, a);
+        rc = launched(r, "snvc_conv3d_forward_stats(winograd)");
     } else if (r.pooled) {      // built for the default kernel form without addends (the local trunk's conv4)
         if (!dflt || a.res || a.plane) {
             rc = fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: SNVC_EPI_AVGPOOL_D4 needs the default Winograd "
                                             "form and no residual / depth planes");
             return true;
         }
-        launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 2>>(g, 256, wino_lds_bytes<CfgWinoN3, 2>, r.st, a);
-        rc = check_launch("snvc_conv3d_forward(pooled)");
+        if (take(r, SNVC_CF_WINO_N3, CfgWinoN3::PIECE, wino_epi(a, 2), a.njobs, a.groups, g, wino_lds_bytes<CfgWinoN3, 2>))
+            launch_lds<conv3d_wino_dma_kernel<CfgWinoN3, false, false, 2>>(g, 256, wino_lds_bytes<CfgWinoN3, 2>, r.st, a);
+        rc = launched(r, "snvc_conv3d_forward(pooled)");
     } else {
-        if (big) launch_wino_dma<CfgWinoBig>(a, g, r.st);
-        else if (dflt) launch_wino_dma<CfgWinoN3>(a, g, r.st);
-        else if (narrow && wide) launch_wino<CfgWinoN>(a, g, r.st);
-        else if (narrow) launch_wino<CfgWinoN8>(a, g, r.st);
-        else if (wide) launch_wino<CfgWino>(a, g, r.st);
-        else launch_wino<CfgWino8>(a, g, r.st);
-        rc = check_launch("snvc_conv3d_forward(winograd)");
+        if (big) launch_wino_dma<CfgWinoBig>(r, SNVC_CF_WINO_BIG, a, g);
+        else if (dflt) launch_wino_dma<CfgWinoN3>(r, SNVC_CF_WINO_N3, a, g);
+        else if (narrow && wide) launch_wino<CfgWinoN>(r, SNVC_CF_WINO_N, a, g);
+        else if (narrow) launch_wino<CfgWinoN8>(r, SNVC_CF_WINO_N8, a, g);
+        else if (wide) launch_wino<CfgWino>(r, SNVC_CF_WINO, a, g);
+        else launch_wino<CfgWino8>(r, SNVC_CF_WINO8, a, g);
+        rc = launched(r, "snvc_conv3d_forward(winograd)");
     }
     return true;
 }
@@ -2895,15 +2999,15 @@ int direct_mfma(const Route &r, ConvArgs &a) {
     const int64_t ntiles = (int64_t)r.p.tiles_d * r.p.tiles_h * r.p.tiles_w;
     const int64_t gx = d.transposed ? ntiles * (a.dc_planar ? 2 : 4) : ntiles;
     if (gx >= ((int64_t)1 << 31)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_conv3d_forward: too many tiles");
-    r.p.launch(a, r.vec8, dim3((unsigned)gx, (unsigned)r.p.groups, (unsigned)d.N), r.st);
-    return check_launch("snvc_conv3d_forward");
+    r.p.launch(r, a, dim3((unsigned)gx, (unsigned)r.p.groups, (unsigned)d.N));
+    return launched(r, "snvc_conv3d_forward");
 }
 
 }  // namespace
 
 int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *packed_weight, const float *scale,
                         const float *bias, const float *residual, const float *depth_planes, float *y,
-                        const float *head_w, float *y_head, void *stream, double *stats) {
+                        const float *head_w, float *y_head, void *stream, double *stats, Chosen *chosen) {
     Plan p;
     if (!d) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_conv3d_forward: null desc");
     int rc = make_plan(*d, p);
@@ -2954,7 +3058,7 @@ int conv3d_forward_impl(const snvc_conv3d_desc *d, const float *x, const float *
     a.r_bs = d->res_batch_stride ? d->res_batch_stride : out_sz;
     a.vec = (d->Win % 4 == 0) && aligned(16, x) && (a.x_bs % 4 == 0);
 
-    Route r{*d, p, packed_layout(*d, p), packed_weight, as_stream(stream)};
+    Route r{*d, p, packed_layout(*d, p), packed_weight, as_stream(stream), chosen};
     r.planar = d->ksize_d == 1; r.side_head = side_head; r.pooled = pooled; r.direct_only = direct_only;
     r.vec8 = (d->Win % 2 == 0) && aligned(8, x) && (a.x_bs % 2 == 0);
     r.fast_common = (int64_t)d->Dout * d->Hout * d->Wout < ((int64_t)1 << 27) && d->Cout % 32 == 0 &&

@@ -54,6 +54,26 @@ def check(a, b, tol=TIGHT, what=""):
     assert frac <= 1e-4 and worst <= 10.0, f"{what}: elementwise 1e-3 criterion: {100 * frac:.4f} % of elements outside, worst {worst:.2f}x"
 
 
+def require_form(module, x_shape, want, residual=False, exact=False):
+    """Asks the dispatcher which kernel form the convolution of ``module`` (a convbn_3d or its conv) takes for a dense, allocator-aligned
+    input of ``x_shape`` under the conv_variant bits in force (snvc_conv3d_forward_form, include/snvc_forms.h), and requires ``want``:
+    a test written for one form fails when its shapes stop reaching it, instead of passing on the direct kernel."""
+    import math
+    import os
+    from snvc_amd import _forms, _lib, ops
+    from snvc_amd.models.submodule import _get_layer, _Plan
+    conv = module[0] if hasattr(module, "__getitem__") else module
+    layer = _get_layer(conv, _Plan())
+    n, in_sp = x_shape[0], tuple(x_shape[2:])
+    out_sz = layer.cout * math.prod(layer.out_spatial(in_sp))
+    flags = (_lib.EPI_RELU | _lib.EPI_ADD_PRE) if residual else 0
+    d = layer._desc(n, in_sp, flags, ops._algo(exact), layer.cin * math.prod(in_sp), out_sz, out_sz if residual else 0)
+    rc, _, text = _forms.conv3d_forward(d, _forms.ENTRY_FORWARD, 16, 16, 16 if residual else 0, 0, 0)
+    with open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "snvc_forms.h")) as f:
+        names = {v: k for k, v in _forms.enum_names(f.read(), "CF").items()}
+    assert rc > 0 and names[rc] == want, f"the dispatcher takes {names.get(rc, rc)} ({text}) for {tuple(x_shape)}, the test is written for {want}"
+
+
 @pytest.fixture(scope="module")
 def G():
     return GC.load_golden()
@@ -393,6 +413,11 @@ def test_k5_k7_winograd_vs_torch(k, dil, W):
                                m[1].weight, m[1].bias, False, 0.0, m[1].eps)
             res = torch.from_numpy(r.standard_normal(tuple(ref.shape)).astype(np.float32))
             m = m.to(dev())
+            wino = {(5, 1): "WINO_K5", (5, 2): "WINO_K5D2", (7, 1): "WINO_K7"}[(k, dil)]
+            direct = {(5, 1): "K5M", (5, 2): "K5D2M", (7, 1): "K7M"}[(k, dil)] + ("2" if cout > 32 else "1")
+            require_form(m, x.shape, wino)
+            require_form(m, x.shape, wino, residual=True)
+            require_form(m, x.shape, direct, exact=True)
             check(m(x.to(dev())).cpu().numpy(), ref.numpy(), tol, f"k{k} d{dil} W={W} conv+bn")
             y = m.fused(x.to(dev()), relu=True, residual=res.to(dev()))
             check(y.cpu().numpy(), F.relu(ref + res).numpy(), tol, f"k{k} d{dil} W={W} relu(conv+res)")
@@ -424,13 +449,20 @@ def test_k3_stride2_winograd_vs_torch(W, form):
                                m[1].weight, m[1].bias, False, 0.0, m[1].eps)
             res = torch.from_numpy(r.standard_normal(tuple(ref.shape)).astype(np.float32))
             m = m.to(dev())
+            rows16 = (W // 2) % 4 == 0          # output rows of 20 and 36 against rows of 22
+            want = {("slice_pipelined", True): "WINO_S2_PIPE4", ("slice_pipelined", False): "WINO_S2_PIPE2",
+                    ("per_chunk", True): "WINO_S2", ("per_chunk", False): "WINO_S2_V8"}[(form, rows16)]
+            require_form(m, x.shape, want)
+            require_form(m, x.shape, want, residual=True)
             check(m(x.to(dev())).cpu().numpy(), ref.numpy(), TIGHT, f"s2 W={W} conv+bn")
             y = m.fused(x.to(dev()), relu=True, residual=res.to(dev()))
             check(y.cpu().numpy(), F.relu(ref + res).numpy(), TIGHT, f"s2 W={W} relu(conv+res)")
             from snvc_amd import _lib, ops
             with ops.conv_variant(_lib.ALGO_DIRECT):
+                require_form(m, x.shape, "K3S2M2" if cout > 32 else "K3S2M1")
                 check(m(x.to(dev())).cpu().numpy(), ref.numpy(), TIGHT, f"s2 W={W} direct")
             with ops.conv_variant(_lib.ALGO_DIRECT | _lib.ALGO_GENERIC_EPILOGUE):
+                require_form(m, x.shape, "K3S2M2" if cout > 32 else "K3S2M1")
                 check(m(x.to(dev())).cpu().numpy(), ref.numpy(), TIGHT, f"s2 W={W} direct, generic epilogue")
 
 
@@ -486,6 +518,12 @@ def test_k3_kernel_variants_vs_torch(mode, W):
                                m[1].weight, m[1].bias, False, 0.0, m[1].eps)
             res = torch.from_numpy(r.standard_normal(tuple(ref.shape)).astype(np.float32))
             m = m.to(dev())
+            rows16 = W % 4 == 0                 # 72 and 156 against 78: the 8-byte-row twins
+            want = {"default": "WINO_N3" if rows16 else "WINO_N8", "big": "WINO_BIG" if rows16 else "WINO_N8",
+                    "std": "WINO" if rows16 else "WINO8", "narrow": "WINO_N" if rows16 else "WINO_N8",
+                    "direct": "K3M2" if cout > 32 else "K3M1"}[mode]
+            require_form(m, x.shape, want)
+            require_form(m, x.shape, want, residual=True)
             check(m(x.to(dev())).cpu().numpy(), ref.numpy(), TIGHT, f"{mode} W={W} conv+bn")
             y = m.fused(x.to(dev()), relu=True, residual=res.to(dev()))
             check(y.cpu().numpy(), F.relu(ref + res).numpy(), TIGHT, f"{mode} W={W} relu(conv+res)")
