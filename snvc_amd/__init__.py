@@ -9,10 +9,12 @@
     snvc_amd.models.hrnet                  <->  snvc.models.hrnet     (HRNet backbone; install_as_snvc(backbone="hip"))
     snvc_amd.models.loss3d                 <->  snvc.models.loss3d    (training losses)
     snvc_amd.models.FCmodel                <->  snvc.models.FCmodel   (the FC box head of use_bbox_head)
+    snvc_amd.thirdparty.oriented_iou_loss  <->  snvc.thirdparty.oriented_iou_loss (the IoU losses' geometry; upstream never shipped it)
 
 Everything executes in hand-written HIP kernels from ``libsnvc_hip.so`` (C ABI:
 ``include/snvc_hip.h``, ``include/snvc_iou3d.h``, ``include/snvc_hrnet.h``).  There is no CPU path: CPU tensors raise, and a missing shared
-library raises at first use.
+library raises at first use.  The exceptions are the losses (``models.loss3d``, ``models.iou_loss``,
+``thirdparty.oriented_iou_loss``), whose CPU and float64 inputs take a torch route written from the same definitions.
 """
 __version__ = "0.1.0"
 
@@ -25,6 +27,7 @@ _ALIASES = {
     "snvc.models.vernier": "snvc_amd.models.vernier",
     "snvc.models.loss3d": "snvc_amd.models.loss3d",
     "snvc.models.FCmodel": "snvc_amd.models.FCmodel",
+    "snvc.thirdparty.oriented_iou_loss": "snvc_amd.thirdparty.oriented_iou_loss",
 }
 
 

@@ -370,10 +370,12 @@ def compute_area_4pts(pts, method='cross-product'):
 
 
 def compute_IoU_loss_corner(pred, gt):
+    """Not built under this name; ``snvc_amd.models.iou_loss.compute_IoU_loss_corner`` computes it."""
     _unbuilt("compute_IoU_loss_corner", _MISSING_UPSTREAM.format("oriented_box_intersection_2d and enclosing_box"))
 
 
 def approximated_3d_iou_pt(pred, gt, bev_indices):
+    """Not built under this name; ``snvc_amd.models.iou_loss.approximated_3d_iou_pt`` computes it."""
     _unbuilt("approximated_3d_iou_pt", _MISSING_UPSTREAM.format("cal_diou"))
 
 
@@ -391,7 +393,8 @@ class ShapeLoss(nn.Module):
 
 
 class BboxLoss(nn.Module):
-    """L1 mean of ``outputs['bbox']`` against ``data_dict['gt_box_local']``, returned as ``{'l1': loss}``."""
+    """L1 mean of ``outputs['bbox']`` against ``data_dict['gt_box_local']``, returned as ``{'l1': loss}``.  The '3D' loss of
+    ``head_reg_type == 'vector3d'`` is not built under this name; ``snvc_amd.models.iou_loss.Bbox3DLoss`` computes it."""
 
     def __init__(self, cfg):
         super(BboxLoss, self).__init__()
@@ -407,7 +410,8 @@ class BboxLoss(nn.Module):
 
 class CoordinateLoss(nn.Module):
     """L1 mean of the predicted bird's-eye-view corner coordinates ``outputs['coordinates']`` [N,9,2] against the x and z
-    columns of ``meta_data['gt_corners_local']`` [N,9,3], the latter normalised to the crop's range with ``normalize_gt``."""
+    columns of ``meta_data['gt_corners_local']`` [N,9,3], the latter normalised to the crop's range with ``normalize_gt``.
+    ``enable_IoU=True`` is not built under this name; ``snvc_amd.models.iou_loss.CoordinateIoULoss`` computes it."""
 
     def __init__(self, cfg, enable_IoU=False, IoU_type='corner', normalize_gt=False):
         super(CoordinateLoss, self).__init__()
