@@ -143,8 +143,11 @@ mul_broadcast_c8_split_kernel(const _Float16 *__restrict__ fh, const _Float16 *_
     const h8 b = *reinterpret_cast<const h8 *>(fl + n * f_bs + ((int64_t)g * S + s) * 8);
     const float w = occ[n * S + s];
     h8 o, l;
+    // lo is what hi's rounding leaves of the ROUNDED product v (the format's definition): contracted, v - hi becomes
+    // fma(a + b, w, -hi) and lo is taken from the exact product instead
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
+#pragma clang fp contract(off)
         const float v = ((float)a[e] + (float)b[e]) * w;
         o[e] = (_Float16)v;
         l[e] = (_Float16)(v - (float)o[e]);

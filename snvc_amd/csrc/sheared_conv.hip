@@ -1372,8 +1372,8 @@ warped_expand_split_kernel(const float *__restrict__ p, const float *__restrict_
             float o = a2[0] + a2[1];
             if (last) o -= tas[c * DC + (d - d_lo)];
             float t = __builtin_fmaf(o, sc[c], bi[c]);
-            vmax = __builtin_fmaxf(vmax, __builtin_fabsf(t));
             t = __builtin_amdgcn_fmed3f(t, lo_bound, 65504.0f);      // ReLU and the clamp to half's range in one
+            vmax = __builtin_fmaxf(vmax, __builtin_fabsf(t));        // what is stored, as in sheared_expand_split_kernel (|x| is a source modifier)
             hi[c] = (_Float16)t;
             lo[c] = (_Float16)(t - (float)hi[c]);
         }

@@ -8,6 +8,7 @@ import hashlib
 import numpy as np
 
 from snvc_amd import _lib
+from split_format import split_pair
 
 SERIAL, NARROW, SMALL, Q16 = _lib.ALGO_X3_SERIAL, _lib.ALGO_X3_NARROW, _lib.ALGO_X3_SMALL, _lib.ALGO_X3_Q16
 ALGOS = [0, SERIAL, NARROW, SMALL, Q16]
@@ -144,8 +145,7 @@ def run_form(name, torch, dev, x_pad=0):
 
     def pair(shape_c, sp, pad=0):          # [N][2][C/8][sp][8] halves (+ pad per sample), value = hi + lo
         v = r.standard_normal((n, shape_c // 8, sp, 8)).astype(np.float32)
-        hi = v.astype(np.float16)
-        lo = (v - hi.astype(np.float32)).astype(np.float16)
+        hi, lo = split_pair(v, 1.0)
         buf = np.zeros((n, 2 * shape_c * sp + pad), np.float16)
         buf[:, :shape_c * sp] = hi.reshape(n, -1)
         buf[:, shape_c * sp:2 * shape_c * sp] = lo.reshape(n, -1)

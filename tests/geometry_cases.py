@@ -14,6 +14,8 @@ from typing import Optional, Tuple
 
 import numpy as np
 
+from split_format import split_pair  # noqa: F401  (the split format's one definition; the gather tests take it from here)
+
 F32, F64 = 0, 1                           # snvc_dtype
 KIND = {"f32": 0, "c8": 1, "split": 2}    # snvc_voxel_gather_kind
 UNSUPPORTED = 2                           # SNVC_ERR_UNSUPPORTED
@@ -206,16 +208,6 @@ def gather_forward_inputs(c: Case):
     pts[n - 1, :, v // 2:v // 2 + min(100, v // 4)] = 1e-41          # subnormal coordinates: x / 2^k and x * 2^-k round alike
     pts[0, :, v - 1] = [res[1], res[0]]                               # the last voxel of the ragged last run: the far corner
     return lf, rf, pts, pts[:, :, ::-1].copy()
-
-
-def split_pair(v: np.ndarray, mul: float):
-    """The split format's definition (tests/f16_plan_cases.py): hi = float16(v * mul), lo = float16(v * mul - float32(hi)), every
-    operation in float32."""
-    with np.errstate(invalid="ignore", over="ignore"):
-        vm = (v.astype(np.float32) * np.float32(mul)).astype(np.float32)
-        hi = vm.astype(np.float16)
-        lo = (vm - hi.astype(np.float32)).astype(np.float32).astype(np.float16)
-    return hi, lo
 
 
 def to_c8(x: np.ndarray):

@@ -1,5 +1,5 @@
 """Guard bands (tests/guarded.py) around the split-mode kernels of conv3d_f16.hip, the layout passes of layout_f16.hip, the fused
-first layer and the sheared first layer of sheared_conv.hip: the partial tiles, tile hand-overs, fused image fills and early-loading
+first layer and the sheared and warped first layers of sheared_conv.hip: the partial tiles, tile hand-overs, fused image fills and early-loading
 epilogues that get rewritten most.  Cases and assertions as in tests/test_gpu_guard_conv.py: each is an existing test run unchanged,
 once as it is and once with every operand placed between NaN guards and every allocation of the wrappers between guard zones.
 
@@ -20,8 +20,8 @@ import test_gpu_x3_train as X3T_M
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-P, EP, F16, TAIL, X3T, FFL = ("test_gpu_parity", "test_gpu_epilogue_paths", "test_gpu_f16", "test_gpu_tail", "test_gpu_x3_train",
-                              "test_gpu_fused_first_layer")
+P, EP, F16, TAIL, X3T, FFL, SPLIT = ("test_gpu_parity", "test_gpu_epilogue_paths", "test_gpu_f16", "test_gpu_tail", "test_gpu_x3_train",
+                                     "test_gpu_fused_first_layer", "test_gpu_split_format")
 ROUND_TRIP_SHAPES = [(1, 8, (2, 3, 258)), (1, 32, (3, 5, 68)), (2, 64, (6, 8, 20))]
 
 
@@ -122,6 +122,13 @@ for q, m0 in ((2, 0), (2, 5), (1, 1)):
     CASES += [(f"sheared_bn_q{q}_m{m0}", P, "test_sheared_fused_batchnorm_entry_points_vs_numpy", dict(q=q, m0=m0), 16, {}),
               (f"sheared_bwd_q{q}_m{m0}", P, "test_sheared_backward_entry_points_vs_numpy", dict(q=q, m0=m0), 4, {})]
 CASES += [(f"sheared_upsample_split_q{q}", TAIL, "test_sheared_upsample_split_equals_upsample_then_split", dict(q=q), 4, {}) for q in (1, 2)]
+# the producers that tests/test_gpu_split_format.py calls directly, at its shapes (ragged channel group, two depth chunks, partial wave)
+CASES += [("mul_broadcast_split_c20", SPLIT, "mul_broadcast_split_case", dict(c=20, sp=(2, 3, 67)), 4, {}),
+          ("mul_broadcast_split_c8_one_voxel", SPLIT, "mul_broadcast_split_case", dict(c=8, sp=(1, 1, 1)), 4, {})]
+CASES += [(f"sheared_expand_split_q{q}_{'planes' if pl else 'no_planes'}", SPLIT, "sheared_expand_split_case", dict(q=q, with_planes=pl), 16, {})
+          for q, pl in ((1, True), (2, False))]
+CASES += [(f"warped_expand_split_{'planes' if pl else 'no_planes'}", SPLIT, "warped_expand_split_case", dict(with_planes=pl), 16, {})
+          for pl in (True, False)]
 
 RUNS = [(c, off) for c in CASES for off in (0, c[4]) if off is not None]          # the two placements back to back: one unguarded run
 
