@@ -32,6 +32,7 @@
 #include "snvc_fused.h"
 #include "snvc_dedup.h"
 #include "snvc_alias.h"
+#include "snvc_hgdedup.h"
 
 namespace snvc {
 namespace {
@@ -144,6 +145,52 @@ __host__ __device__ __forceinline__ int wedge_alias_depth(const WedgeDesc &g, in
 // conv3d_x3s2q_kernel<1>: the input pair's duplicate rows are read at their representative's
 struct F16AliasArgs : F16Args {
     WedgeDesc in_alias;
+};
+// The hourglass's duplicates (include/snvc_hgdedup.h).  v2, conv2's result, at voxel (d, w) reads v1 on planes d - 1 .. d + 1 and columns
+// w - 1 .. w + 1, so it is d-invariant -- v2(d) == v2(d - 4) bit for bit: same image, same MFMAs, same lane of a 4-plane tile -- where
+// those all lie on the wedge: d - 1 >= 1, d + 1 <= D - 2, w + 1 < W - 1 and the largest G index, column w + 1 on plane d - 1, below 0.
+// The first stride-2 layer's output tile (od0, ow0) of the 2 x 4 x 32 tiling is PURE when its whole 5 x 9 x 65 image, planes 2 od0 - 1 ..
+// 2 od0 + 3 and columns 2 ow0 - 1 .. 2 ow0 + 63, lies there; it then stores what tile (od0 - 2, ow0) stores.  The pure od0 of a column are
+// consecutive even numbers; the first is the representative, the others are duplicates.  g is still the PRODUCER's (D, W, q, m0, off).
+// hg_first_pure: the rule solved for od0: 2 od0 - 2 > X = q (2 ow0 + 64) - m0 + off is od0 >= (X + 4) >> 1, od0 >= 2, on the 2-grid.
+// hg_alias_depth(od, ow) -> the output plane whose row holds voxel (od, ., ow)'s bits: the identity outside duplicate tiles.  One
+// definition for the walk that skips the duplicates (conv3d_x3s2q_kernel<2>), the reader (conv3d_x3q_kernel<0, 2>) and the host query.
+__host__ __device__ __forceinline__ bool hg_tile_pure(const WedgeDesc &g, int od0, int ow0) {
+    return od0 >= 2 && 2 * od0 + 4 <= g.D - 2 && 2 * ow0 + 64 < g.W - 1 && g.q * (2 * ow0 + 64) - (2 * od0 - 2) - g.m0 + g.off < 0;
+}
+__host__ __device__ __forceinline__ int hg_first_pure(const WedgeDesc &g, int ow0) {
+    const int lo = (g.q * (2 * ow0 + 64) - g.m0 + g.off + 4) >> 1;
+    return ((lo > 2 ? lo : 2) + 1) & ~1;
+}
+__host__ __device__ __forceinline__ int hg_alias_depth(const WedgeDesc &g, int od, int ow) {
+    const int ow0 = ow & ~31, od0 = od & ~1, first = hg_first_pure(g, ow0);
+    return (2 * ow0 + 64 < g.W - 1 && od0 > first && 2 * od0 + 4 <= g.D - 2) ? first + (od & 1) : od;
+}
+// conv3d_x3s2q_kernel<2>'s walk over the LIVE tiles of a sample.  First representatives do not fall from one tile column to the next, and
+// every column's last pure tile is the same, so the duplicate columns of depth tile td are the leading k(td) ones and k steps up, one
+// column at a time, then back to 0: at most HG_COLS + 2 runs of depth tiles with a constant k.  Run s holds the depth tiles from td0[s]
+// on, tiles_w - k_s live tiles per row (k_s = s, and 0 for the last run), and ends at live tile cum[s] of the sample; an empty run
+// repeats its predecessor's cum.  Built by hg_live_walk from hg_first_pure; shapes with more duplicate columns are not given this form.
+constexpr int HG_COLS = 4;
+struct HgLive { int cum[HG_COLS + 2], td0[HG_COLS + 2], live_tiles; };
+// live tile u < live_tiles of a sample -> (td, th, tw): the run (a select chain over the descriptor's words -- in the kernel they are
+// kernel arguments and u is wave-uniform, so all of it sits in scalar registers and nothing is fetched from memory), then the tile in it.
+// One definition for the kernel and the host query (snvc_hgdedup_live_tile) that the host test walks against the predicate.
+__host__ __device__ __forceinline__ void hg_live_tile(const HgLive &lv, int tiles_h, int tiles_w, int u, int &td, int &th, int &tw) {
+    int base = 0, t0 = 0, k = 0;
+#pragma unroll
+    for (int s = 1; s < HG_COLS + 2; ++s) {
+        const bool in = u >= lv.cum[s - 1];
+        base = in ? lv.cum[s - 1] : base;
+        t0 = in ? lv.td0[s] : t0;
+        k = in ? (s == HG_COLS + 1 ? 0 : s) : k;
+    }
+    const int v = u - base, wl = tiles_w - k, slab = tiles_h * wl, rem = v % slab;
+    td = t0 + v / slab; th = rem / wl; tw = k + rem % wl;
+}
+// conv3d_x3s2q_kernel<2>: <1>'s aliased read, and the duplicate tiles of the OUTPUT are no jobs of the walk (their rows stay unwritten)
+struct F16LiveArgs : F16AliasArgs {
+    HgLive live;
 };
 constexpr int SRC_NO_COPY = 1 << 29;    // F16SrcArgs::v_flags, internal, with SRC_DEDUP: no wedge_copy_kernel behind the launch (the readers alias)
 
@@ -830,9 +877,12 @@ __device__ __forceinline__ const F16SrcArgs &src_args_of(const A &a) {
     else return *reinterpret_cast<const F16SrcArgs *>(&a);
 }
 
+// SRC 2 (include/snvc_hgdedup.h): the input pair is the hourglass's first stride-2 layer's, written without its duplicate tiles
+// (a.in_alias, the descriptor of THAT layer's input): a piece of such a row is fetched from the representative's plane -- whole 128-byte
+// lines of another plane, decided once per workgroup in the fill geometry and nowhere else.
 template <int EPI, int SRC = 0>      // EPI 0: split C8 output; 3: + the side head (Cout == 32); 2 (r6): float32 NCDHW output (+ float32 residual, + statistics)
 __global__ void __launch_bounds__(256, 2)
-conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
+conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, std::conditional_t<SRC == 2, F16AliasArgs, F16Args>> a) {
     using Cfg = X3QCfg;
     constexpr int NB = Cfg::NB, TH = Cfg::TH, IN_H = Cfg::IN_H, IN_W = Cfg::IN_W, VOX = Cfg::VOX, NIT = Cfg::NIT, NQ = Cfg::NQ;
     constexpr int ITEMS = Cfg::ITEMS, PF = Cfg::PF;
@@ -871,7 +921,9 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
         const int hh = r2 / IN_W, ww = r2 - hh * IN_W;
         const int gd = id0 + dd, gh = ih0 + hh, gw = iw0 + ww;
         const bool ok = i < ITEMS && (unsigned)gd < (unsigned)a.Din && (unsigned)gh < (unsigned)a.Hin && (unsigned)gw < (unsigned)a.Win;
-        off[it] = ok ? (unsigned)(gd * in_hw + gh * a.Win + gw) : 0u;
+        int sd = gd;      // the plane that holds the piece
+        if constexpr (SRC == 2) sd = hg_alias_depth(a.in_alias, gd, gw);
+        off[it] = ok ? (unsigned)(sd * in_hw + gh * a.Win + gw) : 0u;
         vmask |= (ok ? 1u : 0u) << it;
     }
     const _Float16 *xn = a.x + n * a.x_bs, *xn_lo = a.x_lo + n * a.x_bs;
@@ -1026,7 +1078,7 @@ conv3d_x3q_kernel(const std::conditional_t<SRC == 1, F16SrcArgs, F16Args> a) {
                     // every weight fragment in flight lands first: none is waited for between here and the barrier
 #pragma unroll
                     for (int i = 0; i < PF; ++i) asm volatile("" ::"v"(q_[i][0]), "v"(q_[i][1]), "v"(q_[i][2]), "v"(q_[i][3]));
-                    if constexpr (!LAST && SRC == 0) issue(chunk + 1, (chunk + 1) & 1);
+                    if constexpr (!LAST && SRC != 1) issue(chunk + 1, (chunk + 1) & 1);
                 }
 #pragma unroll
                 for (int m = 0; m < 4; ++m) af[m] = q_[0][m];
@@ -1508,9 +1560,11 @@ __device__ __forceinline__ void wait_lgkm_for4(h8 (&b)[4]) {
 
 // ALIAS: the input pair's duplicate wedge tiles were not written (a.in_alias, include/snvc_alias.h): a piece of such a row is fetched
 // from the representative's plane -- the same 128-byte lines of another plane, decided in geometry() and nowhere else.
+// ALIAS 2 (include/snvc_hgdedup.h): <1>'s read, and the walk runs over the LIVE jobs only -- total_jobs is their count and decode() maps
+// a live index to its tile (a.live); the step pipeline never sees a duplicate, whose rows of the output pair stay unwritten.
 template <int ALIAS = 0>
 __global__ void __launch_bounds__(512, 1)
-conv3d_x3s2q_kernel(const std::conditional_t<ALIAS == 1, F16AliasArgs, F16Args> a, const int total_jobs) {
+conv3d_x3s2q_kernel(const std::conditional_t<ALIAS == 2, F16LiveArgs, std::conditional_t<ALIAS == 1, F16AliasArgs, F16Args>> a, const int total_jobs) {
     using Cfg = X3S2Cfg;
     constexpr int NB = Cfg::NB, TH = Cfg::TH, IN_H = Cfg::IN_H, IN_W = Cfg::IN_W, VOX = Cfg::VOX, NIT = Cfg::NIT, NQ = Cfg::NQ;
     extern __shared__ __attribute__((aligned(16))) char lds[];
@@ -1531,8 +1585,16 @@ conv3d_x3s2q_kernel(const std::conditional_t<ALIAS == 1, F16AliasArgs, F16Args> 
     struct Job { int od0, oh0, ow0, cb; int64_t n; };
     auto decode = [&](int b) {
         const int j = xcd_remap16(b, total_jobs);
-        const int cb = j % cblocks, r = j / cblocks, t = r % ntiles;
         Job jb;
+        if constexpr (ALIAS == 2) {
+            const int cb = j % cblocks, r = j / cblocks, u = r % a.live.live_tiles;      // wave-uniform: scalar registers throughout
+            jb.n = r / a.live.live_tiles; jb.cb = cb;
+            int td, th, tw;
+            hg_live_tile(a.live, a.tiles_h, a.tiles_w, u, td, th, tw);
+            jb.od0 = td * Cfg::TD; jb.oh0 = th * TH; jb.ow0 = tw * 32;
+            return jb;
+        }
+        const int cb = j % cblocks, r = j / cblocks, t = r % ntiles;
         jb.n = r / ntiles; jb.cb = cb;
         const int tw = t % a.tiles_w, th = (t / a.tiles_w) % a.tiles_h, td = t / (a.tiles_w * a.tiles_h);
         jb.od0 = td * Cfg::TD; jb.oh0 = th * TH; jb.ow0 = tw * 32;
@@ -2418,6 +2480,54 @@ void launch_x3s2q_alias(const F16AliasArgs &a, const F16Geom &g, hipStream_t st)
     launch_lds<conv3d_x3s2q_kernel<1>>(dim3((unsigned)x3s2q_workgroups(g)), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)g.jobs);
 }
 
+// The hourglass's duplicates (include/snvc_hgdedup.h) of the stride-2 layer behind a [D][.][W] tensor written under g, on the 2 x 4 x 32
+// tiling of its output, by the closed forms: per tile column tw < max_tw the representative's and the last duplicate's depth tile
+// (-1 / -1 without duplicates).  dups: the duplicates of one (n, th); ncols: the columns with duplicates (the leading ones).
+struct HgRange { int64_t dups; int ncols, last_td; };
+HgRange hg_ranges(const WedgeDesc &g, int64_t *first_td, int64_t *last_td, int max_tw) {
+    HgRange r{0, 0, -1};
+    for (int tw = 0; tw < max_tw; ++tw) first_td[tw] = last_td[tw] = -1;
+    if (g.D < 10) return r;                              // od0 >= 2 and 2 od0 + 4 <= D - 2
+    const int last = ((g.D - 6) >> 1) & ~1;              // the last pure od0 of every column that has one
+    r.last_td = last / X3S2Cfg::TD;
+    for (int tw = 0; 2 * (32 * tw) + 64 < g.W - 1; ++tw) {
+        const int first = hg_first_pure(g, 32 * tw);
+        if (first >= last) break;                        // none, or a lone pure tile: no duplicate here nor in any later column
+        if (tw < max_tw) { first_td[tw] = first / X3S2Cfg::TD; last_td[tw] = r.last_td; }
+        r.dups += (last - first) / X3S2Cfg::TD;
+        r.ncols = tw + 1;
+    }
+    return r;
+}
+// HgLive of a launch with tiles_d x tiles_h x tiles_w tiles per sample; false: no duplicates, or more duplicate columns than the walk has runs
+bool hg_live_walk(const WedgeDesc &g, int tiles_d, int tiles_h, int tiles_w, HgLive &lv) {
+    int64_t first[HG_COLS], last[HG_COLS];
+    const HgRange r = hg_ranges(g, first, last, HG_COLS);
+    if (r.dups == 0 || r.ncols > HG_COLS) return false;
+    int end[HG_COLS + 2];                                // the last depth tile of every run
+    for (int c = 0; c < HG_COLS; ++c) end[c] = c < r.ncols ? (int)first[c] : r.last_td;
+    end[HG_COLS] = r.last_td;
+    end[HG_COLS + 1] = tiles_d - 1;
+    int cum = 0, td0 = 0;
+    for (int s = 0; s < HG_COLS + 2; ++s) {
+        const int k = s == HG_COLS + 1 ? 0 : s;
+        lv.td0[s] = td0;
+        cum += (end[s] + 1 - td0) * tiles_h * (tiles_w - k);
+        lv.cum[s] = cum;
+        td0 = end[s] + 1;
+    }
+    lv.live_tiles = cum;
+    return cum == (int64_t)tiles_d * tiles_h * tiles_w - r.dups * tiles_h;
+}
+// launch_x3s2q_alias whose walk leaves the output's duplicate tiles out (snvc_hgdedup_f16x3_conv3d_forward): g.jobs counts the live jobs
+void launch_x3s2q_live(const F16LiveArgs &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_x3s2q_kernel<2>>(dim3((unsigned)x3s2q_workgroups(g)), X3S2Cfg::THREADS, X3S2Cfg::LDS_BYTES, st, a, (int)g.jobs);
+}
+// launch_x3q<0> on an input pair written that way (snvc_hgdedup_reader_f16x3_conv3d_forward)
+void launch_x3q_hg_alias(const F16AliasArgs &a, const F16Geom &g, hipStream_t st) {
+    launch_lds<conv3d_x3q_kernel<0, 2>>(g.grid, 256, X3QCfg::LDS_BYTES, st, a);
+}
+
 // a 32x32x16 form: everything but its class mode and its statistics bit follows from the Cfg; EPI 0 C8, 1 plane, 2 float32, 3 side head, 4 tail
 template <class Cfg, int... EPI>
 constexpr F16Form f16_form(int cls_mode, bool stats = false) {
@@ -2771,6 +2881,8 @@ struct F16x3Call {
     const float *x_mul = nullptr;
     const snvc::F16SrcArgs *src = nullptr;                // the fused sheared first layer: the image's producer
     const snvc_wedge_desc *in_alias = nullptr;            // the input pair's duplicate wedge tiles were not written (snvc_alias.h)
+    bool hg_skip = false;                                 // with in_alias: the result's own duplicate tiles are not computed (snvc_hgdedup.h)
+    const snvc_wedge_desc *hg_in = nullptr;               // the input pair is such a result; hg_in: the descriptor its producer was given
     void *stream = nullptr;
 };
 
@@ -2869,6 +2981,42 @@ static int f16x3_forward(const snvc_conv3d_desc *d, const F16x3Call &c) {
     if ((b.v_flags & SRC_DEDUP) && ((!(b.v_flags & SRC_NO_COPY) && c.y_head && (d->Wout % 4 || (reinterpret_cast<uintptr_t>(c.y_head) & 15))) ||
                                     wedge_ranges(a.Din, a.Win, b.v_q, b.v_m0, b.v_off, nullptr, nullptr, 0).dups == 0))
         b.v_flags &= ~SRC_DEDUP;
+    if (c.hg_skip) {            // the stride-2 layer behind conv2: <1>'s read, and its own duplicate tiles are no jobs of the walk
+        if (!c.in_alias || &f != &FORM_K3S2XQ || call != TO_C8)
+            return fail(SNVC_ERR_UNSUPPORTED, "snvc_hgdedup_f16x3_conv3d_forward: built for the stride-2 3x3x3 layer on the 16x16x32 form (SNVC_ALGO_X3_Q16) with a split C8 result");
+        if (c.in_alias->D != d->Din || c.in_alias->W != d->Win || (c.in_alias->q != 1 && c.in_alias->q != 2))
+            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_f16x3_conv3d_forward: in_alias describes a [Din][.][Win] tensor, q = 1 | 2");
+        int64_t first[1], last[1];
+        if (hg_ranges(*c.in_alias, first, last, 0).ncols > HG_COLS)
+            return fail(SNVC_ERR_UNSUPPORTED, "snvc_hgdedup_f16x3_conv3d_forward: more tile columns with duplicates than the live walk has runs (snvc_hgdedup_max_columns)");
+        F16LiveArgs lv{};
+        static_cast<F16Args &>(lv) = a;
+        lv.in_alias = *c.in_alias;
+        if (!hg_live_walk(lv.in_alias, a.tiles_d, a.tiles_h, a.tiles_w, lv.live)) {      // no duplicate: the aliased launch itself
+            launch_x3s2q_alias(lv, g, st);
+        } else {
+            F16Geom gl = g;
+            gl.jobs = (int64_t)lv.live.live_tiles * p.cblocks * d->N;
+            launch_x3s2q_live(lv, gl, st);
+        }
+        return check_launch("snvc_hgdedup_f16x3_conv3d_forward");
+    }
+    if (c.hg_in) {              // the stride-1 layer behind it: the remap sits in the image fill's geometry, every tile is computed and written
+        if (&f != &FORM_K3XQ || call != TO_C8 || resflags)
+            return fail(SNVC_ERR_UNSUPPORTED, "snvc_hgdedup_reader_f16x3_conv3d_forward: built for the stride-1 3x3x3 layer on the 16x16x32 form (SNVC_ALGO_X3_Q16) with a split C8 result, no residual");
+        if ((c.hg_in->D - 1) / 2 + 1 != d->Din || (c.hg_in->W - 1) / 2 + 1 != d->Win || c.hg_in->D < 1 || c.hg_in->W < 1 || (c.hg_in->q != 1 && c.hg_in->q != 2))
+            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_reader_f16x3_conv3d_forward: in_desc describes the [2 Din][.][2 Win] tensor in front of the stride-2 layer, q = 1 | 2");
+        int64_t first[1], last[1];
+        if (hg_ranges(*c.hg_in, first, last, 0).dups == 0) {      // every row was written
+            f.launch[call](b, g, st);
+        } else {
+            F16AliasArgs al{};
+            static_cast<F16Args &>(al) = a;
+            al.in_alias = *c.hg_in;
+            launch_x3q_hg_alias(al, g, st);
+        }
+        return check_launch("snvc_hgdedup_reader_f16x3_conv3d_forward");
+    }
     if (c.in_alias) {           // one reader form is built; the aliased rows are whole rows of the representative's plane: nothing else moves
         if (&f != &FORM_K3S2XQ || call != TO_C8)
             return fail(SNVC_ERR_UNSUPPORTED, "snvc_alias_f16x3_conv3d_forward: built for the stride-2 3x3x3 layer on the 16x16x32 form (SNVC_ALGO_X3_Q16) with a split C8 result");
@@ -2985,6 +3133,77 @@ int snvc_alias_f16x3_conv3d_forward(const snvc_conv3d_desc *d, const void *x_hi,
     F16x3Call c;
     c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias;
     c.y_hi = y_hi; c.y_lo = y_lo; c.head_mul = 1.0f; c.res_mul = 1.0f; c.overflow = overflow; c.in_alias = in_alias; c.stream = stream;
+    return f16x3_forward(d, c);
+}
+
+// ---- include/snvc_hgdedup.h: the hourglass's first stride-2 layer does not compute its own duplicates; the stride-1 layer behind it aliases
+int snvc_hgdedup_abi_version(void) { return 1; }
+int snvc_hgdedup_max_columns(void) { return snvc::HG_COLS; }
+
+static bool hgdedup_desc_ok(const snvc_wedge_desc *w) { return w && w->D >= 1 && w->W >= 1 && (w->q == 1 || w->q == 2); }
+
+int snvc_hgdedup_tile_pure(const snvc_wedge_desc *w, int64_t od0, int64_t ow0) {
+    using namespace snvc;
+    if (!hgdedup_desc_ok(w) || od0 < 0 || od0 >= (w->D - 1) / 2 + 1 || (od0 & 1) || ow0 < 0 || ow0 >= (w->W - 1) / 2 + 1 || (ow0 & 31)) {
+        fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_tile_pure: a desc with q = 1 | 2 and a tile origin (od0 % 2 == 0, ow0 % 32 == 0) inside the stride-2 result");
+        return -1;
+    }
+    return hg_tile_pure(*w, (int)od0, (int)ow0) ? 1 : 0;
+}
+
+int64_t snvc_hgdedup_tiles(const snvc_wedge_desc *w, int64_t *first_td, int64_t *last_td, int max_tw) {
+    using namespace snvc;
+    if (!hgdedup_desc_ok(w) || max_tw < 0 || (max_tw > 0 && (!first_td || !last_td))) {
+        fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_tiles: a desc with q = 1 | 2, and max_tw entries to write");
+        return -1;
+    }
+    return hg_ranges(*w, first_td, last_td, max_tw).dups;
+}
+
+int64_t snvc_hgdedup_depth(const snvc_wedge_desc *w, int64_t od, int64_t ow) {
+    using namespace snvc;
+    if (!hgdedup_desc_ok(w) || od < 0 || od >= (w->D - 1) / 2 + 1 || ow < 0 || ow >= (w->W - 1) / 2 + 1) {
+        fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_depth: a desc with q = 1 | 2 and (od, ow) inside the stride-2 result [(D - 1) / 2 + 1) x [(W - 1) / 2 + 1)");
+        return -1;
+    }
+    return hg_alias_depth(*w, (int)od, (int)ow);
+}
+
+int64_t snvc_hgdedup_live_tile(const snvc_wedge_desc *w, int64_t tiles_h, int64_t index, int64_t *td, int64_t *th, int64_t *tw) {
+    using namespace snvc;
+    HgLive lv{};
+    if (!hgdedup_desc_ok(w) || tiles_h < 1 || tiles_h > 65535) {
+        fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_live_tile: a desc with q = 1 | 2 and 1 .. 65535 tile rows");
+        return -1;
+    }
+    const int tiles_d = ceil_div((w->D - 1) / 2 + 1, X3S2Cfg::TD), tiles_w = ceil_div((w->W - 1) / 2 + 1, 32);
+    if (!hg_live_walk(*w, tiles_d, (int)tiles_h, tiles_w, lv)) return 0;
+    if (index >= 0 && index < lv.live_tiles && td && th && tw) {
+        int a, b, c;
+        hg_live_tile(lv, (int)tiles_h, tiles_w, (int)index, a, b, c);
+        *td = a; *th = b; *tw = c;
+    }
+    return lv.live_tiles;
+}
+
+int snvc_hgdedup_f16x3_conv3d_forward(const snvc_conv3d_desc *d,const void *x_hi, const void *x_lo, const void *packed_weight,
+                                      const float *scale, const float *bias, void *y_hi, void *y_lo, int *overflow,
+                                      const snvc_wedge_desc *in_alias, void *stream) {
+    if (!in_alias) return snvc::fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_f16x3_conv3d_forward: null in_alias");
+    F16x3Call c;
+    c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias;
+    c.y_hi = y_hi; c.y_lo = y_lo; c.head_mul = 1.0f; c.res_mul = 1.0f; c.overflow = overflow; c.in_alias = in_alias; c.hg_skip = true;
+    c.stream = stream;
+    return f16x3_forward(d, c);
+}
+
+int snvc_hgdedup_reader_f16x3_conv3d_forward(const snvc_conv3d_desc *d, const void *x_hi, const void *x_lo, const void *packed_weight,
+                                             const float *scale, const float *bias, void *y_hi, void *y_lo, int *overflow,
+                                             const snvc_wedge_desc *in_desc, void *stream) {
+    if (!in_desc) return snvc::fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_hgdedup_reader_f16x3_conv3d_forward: null in_desc");
+    F16x3Call c;
+    c.x_hi = x_hi; c.x_lo = x_lo; c.packed_weight = packed_weight; c.scale = scale; c.bias = bias;
+    c.y_hi = y_hi; c.y_lo = y_lo; c.head_mul = 1.0f; c.res_mul = 1.0f; c.overflow = overflow; c.hg_in = in_desc; c.stream = stream;
     return f16x3_forward(d, c);
 }
 

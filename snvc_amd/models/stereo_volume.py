@@ -185,6 +185,10 @@ class GlobalStack(SplitModePolicy, nn.Module):
     # bits.  Taken only with dedup_wedge and fused_first on the fused-tail route, where that stride-2 layer runs on its persistent
     # 16x16x32 form and the shape has duplicates; anything else is the copy route.  False: the copy route.
     alias_wedge = True
+    # on the alias route the hourglass's first stride-2 layer does not compute its own duplicate tiles either (include/snvc_hgdedup.h:
+    # 144 of its 2 880 jobs at cfg2), and hg conv2 -- the one reader of its result -- reads the representative's rows.  Same bits.  Taken
+    # only where the shape has such tiles and both layers run on their 16x16x32 forms; anything else is the alias route's own calls.
+    dedup_hourglass = True
     split_prep = True    # split mode: the sheared first layer's depth-1 3 x 7 layers (G, G') on the half pipe too (False: fp32 MFMA, as r4)
     fused_tail = True    # split mode: conv5's epilogue contracts its result with the folded one-channel tail (False: r4's two launches)
 
@@ -290,11 +294,19 @@ class GlobalStack(SplitModePolicy, nn.Module):
                                  out=v2_out)
         _mark(timing, "conv2", 1)
         _ROUTES["side_head"] += 1
-        if alias is not None:
+        hg_dedup = alias is not None and self._hg_dedup_route(st, n, (d, h, w), alias)
+        _ROUTES["hg_dedup"] += hg_dedup
+        if hg_dedup:
+            # its duplicate tiles are not computed (include/snvc_hgdedup.h); hg conv2, the result's one reader, aliases their rows
+            o = L["h1"].forward_hg_dedup(v2s, alias, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)
+        elif alias is not None:
             o = L["h1"].forward_aliased(v2s, alias, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)
         else:
             o = L["h1"](v2s, E["conv2"], *A["h1"], flags=EPI_RELU, out_exp=E["h1"], overflow=flag)              # 1/2 res, 2C channels
-        pre = L["h2"](o, E["h1"], *A["h2"], flags=EPI_RELU, out_exp=E["h2"], overflow=flag)                     # relu(bn(conv))   :153-156
+        if hg_dedup:
+            pre = L["h2"].forward_hg_reader(o, alias, E["h1"], *A["h2"], flags=EPI_RELU, out_exp=E["h2"], overflow=flag)
+        else:
+            pre = L["h2"](o, E["h1"], *A["h2"], flags=EPI_RELU, out_exp=E["h2"], overflow=flag)                 # relu(bn(conv))   :153-156
         o = L["h3"](pre, E["h2"], *A["h3"], flags=EPI_RELU, out_exp=E["h3"], overflow=flag)                     # 1/4 res
         o = L["h4"](o, E["h3"], *A["h4"], flags=EPI_RELU, out_exp=E["h4"], overflow=flag)
         st["guard"].post()      # the last layer that can clamp (conv5's exponent is a hard bound, see _x3_state): the flag leaves for the host here
@@ -323,6 +335,14 @@ class GlobalStack(SplitModePolicy, nn.Module):
         if not st["layers"]["h1"].aliased_form(n, sp):
             return False
         return ops.fused_first_wedge_dups(int(sp[0]), int(sp[2]), int(src["q"]), int(src["m0"]), int(src["off"])) > 0
+
+    def _hg_dedup_route(self, st, n, sp, alias) -> bool:
+        """True when, on the alias route, the hourglass's first stride-2 layer may leave ITS duplicate tiles out: the shape has some and
+        both layers report the form -- hg conv1 the live walk, hg conv2 (the result's one reader) the aliased fill."""
+        if not self.dedup_hourglass:
+            return False
+        L = st["layers"]
+        return L["h1"].hg_dedup_form(n, sp, alias) and L["h2"].hg_reader_form(n, L["h1"].out_spatial(tuple(int(v) for v in sp)))
 
     def _tail(self, v, hv=None):
         """v + hourglass(v)[0] -> classifier.  The hourglass's last transposed layer has no activation

@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _alias, _dedup, _derived, _fused, _lib
+from . import _alias, _dedup, _derived, _fused, _hgdedup, _lib
 from ._lib import (EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID, EPI_STREAM_OUT, F32, F64, Conv3dDesc,
                    Unsupported, check)
 
@@ -1677,6 +1677,62 @@ def wedge_alias_depth(desc: "_alias.WedgeDesc", d: int, w: int) -> int:
     return got
 
 
+def hg_dedup_tiles(desc: "_alias.WedgeDesc"):
+    """The duplicate tiles of the stride-2 layer behind a tensor written under ``desc``, on the 2 x 4 x 32 tiling of its result
+    (snvc_hgdedup_tiles: the closed form the kernels use; include/snvc_hgdedup.h).  Returns (duplicates per (n, th), first, last): per
+    32-column tile column the depth tile index of the representative and of the last duplicate, -1 / -1 where the column has none.
+    Host only."""
+    ntw = (((int(desc.W) - 1) // 2 + 1) + 31) // 32
+    first, last = (ctypes.c_int64 * ntw)(), (ctypes.c_int64 * ntw)()
+    dups = int(_hgdedup.lib().snvc_hgdedup_tiles(ctypes.byref(desc), first, last, ntw))
+    if dups < 0:
+        raise ValueError(_lib.lib().snvc_last_error_string().decode())
+    return dups, list(first), list(last)
+
+
+@functools.lru_cache(maxsize=64)
+def hg_dedup_columns(d: int, w: int, q: int, m0: int, off: int) -> int:
+    """Tile columns with duplicates of ``hg_dedup_tiles(wedge_desc(d, w, q, m0, off))``, remembered per shape (a step asks it on every
+    call)."""
+    return sum(1 for f in hg_dedup_tiles(wedge_desc(d, w, q, m0, off))[1] if f >= 0)
+
+
+def hg_dedup_max_columns() -> int:
+    """The most tile columns with duplicates that ``forward_hg_dedup`` can leave out (snvc_hgdedup_max_columns)."""
+    return int(_hgdedup.lib().snvc_hgdedup_max_columns())
+
+
+def hg_live_tiles(desc: "_alias.WedgeDesc", tiles_h: int):
+    """The (td, th, tw) of every tile that ``forward_hg_dedup`` computes per sample, in the order of its walk
+    (snvc_hgdedup_live_tile: the function the kernel uses); [] where no walk is built.  Host only."""
+    td, th, tw = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
+    fn = _hgdedup.lib().snvc_hgdedup_live_tile
+    live = int(fn(ctypes.byref(desc), int(tiles_h), -1, None, None, None))
+    if live < 0:
+        raise ValueError(_lib.lib().snvc_last_error_string().decode())
+    out = []
+    for i in range(live):
+        fn(ctypes.byref(desc), int(tiles_h), i, ctypes.byref(td), ctypes.byref(th), ctypes.byref(tw))
+        out.append((td.value, th.value, tw.value))
+    return out
+
+
+def hg_tile_pure(desc: "_alias.WedgeDesc", od0: int, ow0: int) -> bool:
+    """The rule itself for tile (od0, ow0) of the stride-2 result (snvc_hgdedup_tile_pure).  Host only."""
+    got = int(_hgdedup.lib().snvc_hgdedup_tile_pure(ctypes.byref(desc), int(od0), int(ow0)))
+    if got < 0:
+        raise ValueError(_lib.lib().snvc_last_error_string().decode())
+    return bool(got)
+
+
+def hg_alias_depth(desc: "_alias.WedgeDesc", od: int, ow: int) -> int:
+    """The plane of the stride-2 result that holds its voxel (od, ., ow) (snvc_hgdedup_depth: the remap the kernels use).  Host only."""
+    got = int(_hgdedup.lib().snvc_hgdedup_depth(ctypes.byref(desc), int(od), int(ow)))
+    if got < 0:
+        raise ValueError(_lib.lib().snvc_last_error_string().decode())
+    return got
+
+
 def sheared_prep_x3_il(right, q: int, wu: int, off: int, wu_col: int, off_col: int, lay_g: "Conv2dLayerX3", lay_col: "Conv2dLayerX3", ws: dict,
                        pitch: int, lp: int):
     """``sheared_prep_x3`` whose two 3 x 7 layers also write G | G' as the channel-interleaved buffer ``gi`` [N,6,C/8,H,pitch,8]
@@ -2002,6 +2058,52 @@ class Conv3dLayerX3(_ConvGeometry):
                                                                _lo_ptr(out), _ptr(overflow), ctypes.byref(in_alias), _stream(x)),
                   "snvc_alias_f16x3_conv3d_forward")
         return out
+
+    def hg_dedup_form(self, n: int, sp, desc: "_alias.WedgeDesc") -> bool:
+        """True when ``forward_hg_dedup`` on a [n, Cin, *sp] pair written under ``desc`` would leave duplicates out: ``aliased_form`` and
+        a shape whose duplicates sit in 1 .. ``hg_dedup_max_columns()`` tile columns."""
+        return (self.aliased_form(n, sp)
+                and 0 < hg_dedup_columns(int(desc.D), int(desc.W), int(desc.q), int(desc.m0), int(desc.off)) <= hg_dedup_max_columns())
+
+    def hg_reader_form(self, n: int, sp) -> bool:
+        """True when a plain launch (split result, no residual, no side head) on a [n, Cin, *sp] input would take the form that can read
+        a pair written by ``forward_hg_dedup`` (``forward_hg_reader``): the stride-1 3x3x3 layer on the 16x16x32 form.  Asks ``x3_form``
+        what ``forward_hg_reader``'s own ``_launch`` asks."""
+        sp = tuple(int(v) for v in sp)
+        return (self.ksize == 3 and self.stride == 1 and not self.transposed and self.w_mul_dev is None
+                and x3_form(self.cout, self.ksize, self.stride, self.dilation, self.transposed, n, self.out_spatial(sp), True, True,
+                            self.forced_algo) == _lib.ALGO_X3_Q16)
+
+    def _forward_hg(self, entry: str, x, desc, x_exp, scale, bias, flags, out, out_exp, overflow):
+        _split_check(x, "x")
+        if x.size(2) * 8 != self.cin:
+            raise RuntimeError(f"conv3d input must have {self.cin} channels (split C8), got {x.size(2) * 8}")
+        n, in_sp, out_sp, algo, packed = self._launch(x, plain=True, split_out=True)
+        out = _result(out, (n, 2, self.cout // 8) + out_sp + (8,), torch.float16, x.device,
+                      "conv3d `out` must be a split C8 tensor of the output shape", _split_check)
+        sc, bi = self.folded(scale, bias, x_exp, out_exp)
+        if n == 0:
+            return out
+        d = self._desc(n, in_sp, flags, algo, _batch_stride(x), _batch_stride(out), 0)
+        with torch.cuda.device(x.device):
+            check(getattr(_hgdedup.lib(), entry)(ctypes.byref(d), _ptr(x), _lo_ptr(x), _ptr(packed), _ptr(sc), _ptr(bi), _ptr(out), _lo_ptr(out),
+                                                 _ptr(overflow), ctypes.byref(desc), _stream(x)), entry)
+        return out
+
+    def forward_hg_dedup(self, x, in_alias: "_alias.WedgeDesc", x_exp: int = 0, scale=None, bias=None, flags: int = 0, out=None,
+                         out_exp: int = 0, overflow=None):
+        """``forward_aliased`` whose own duplicate tiles (``hg_dedup_tiles(in_alias)``) are not computed
+        (snvc_hgdedup_f16x3_conv3d_forward): their rows of the result keep what they held, and only ``forward_hg_reader`` with the same
+        descriptor may take it.  Everything written is what the plain launch writes.  Raises Unsupported for a layer, kernel form or
+        shape it is not built for."""
+        return self._forward_hg("snvc_hgdedup_f16x3_conv3d_forward", x, in_alias, x_exp, scale, bias, flags, out, out_exp, overflow)
+
+    def forward_hg_reader(self, x, in_desc: "_alias.WedgeDesc", x_exp: int = 0, scale=None, bias=None, flags: int = 0, out=None,
+                          out_exp: int = 0, overflow=None):
+        """``self(x, x_exp, ...)`` (split C8 result, no residual, no side head) on a pair ``x`` that ``forward_hg_dedup`` wrote under
+        ``in_desc``: the duplicates' rows are read at their representative's (snvc_hgdedup_reader_f16x3_conv3d_forward).  Same bits
+        as on the fully populated pair; every tile is computed and written."""
+        return self._forward_hg("snvc_hgdedup_reader_f16x3_conv3d_forward", x, in_desc, x_exp, scale, bias, flags, out, out_exp, overflow)
 
     def forward_f32(self, x, x_mul_dev, residual_f32: Optional[torch.Tensor] = None, relu: bool = False):
         """r6 (training): the plain convolution of a device-scaled layer with a float32 NCDHW result (snvc_f16x3_conv3d_forward_f32):

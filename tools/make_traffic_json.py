@@ -55,7 +55,7 @@ F32_MFMA_LAYERS = ("conv1_factored", "conv2_side", "hg_s2")
 # The markers follow the kernels' CURRENT signatures: a hash taken now is of the text as it stands (conv3d_x3s2q_kernel has been a template
 # with an aliased-input instance since profiles/wedge_alias), not of the text the recorded r5 / r6 counters were collected on -- those
 # files keep their own hashes.  The x3_conv2 / x3_hg2 marker predates conv3d_x3q_kernel's conditional_t signature and matches nothing.
-SOURCE_OF = {"x3_s2": ("snvc_amd/csrc/conv3d_f16.hip", "conv3d_x3s2q_kernel(const std::conditional_t<ALIAS == 1, F16AliasArgs, F16Args> a, const int total_jobs) {"),
+SOURCE_OF = {"x3_s2": ("snvc_amd/csrc/conv3d_f16.hip", "conv3d_x3s2q_kernel(const std::conditional_t<ALIAS == 2, F16LiveArgs, std::conditional_t<ALIAS == 1, F16AliasArgs, F16Args>> a, const int total_jobs) {"),
              "x3_conv2": ("snvc_amd/csrc/conv3d_f16.hip", "conv3d_x3q_kernel(const F16Args a) {"),
              "x3_hg2": ("snvc_amd/csrc/conv3d_f16.hip", "conv3d_x3q_kernel(const F16Args a) {")}
 
