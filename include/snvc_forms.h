@@ -1,8 +1,9 @@
 /*
  * snvc_forms.h -- which kernel form the geometry launchers of libsnvc_hip.so take: the cost volume (csrc/cost_volume.hip) and the
  * feature -> voxel gather in both directions (csrc/voxel_gather.hip, csrc/voxel_gather_bwd.hip); and which form the weight
- * gradient of the 3D convolutions takes (csrc/conv3d_bwd.hip) and which form their fp32 forward takes (csrc/conv3d.hip; last
- * section).  Kept apart from snvc_hip.h,
+ * gradient of the 3D convolutions takes (csrc/conv3d_bwd.hip), which form their fp32 forward takes (csrc/conv3d.hip) and which
+ * rows per workgroup, depth chunks and column chunks the first-layer kernels take (csrc/sheared_conv.hip; last section).  Kept apart
+ * from snvc_hip.h,
  * whose declaration set and ABI number are pinned; this header versions itself through snvc_forms_abi_version().
  *
  * Every launcher decides its form in one host function, from the sizes, the element type, the alignment of its operands and the
@@ -191,6 +192,44 @@ enum snvc_conv3d_forward_form_id {
 };
 SNVC_API int snvc_conv3d_forward_form(const snvc_conv3d_desc *desc_host, int entry, int x_align, int y_align, int res_align,
                                       int planes_align, int y_head_align, int64_t *info);
+
+/* The first-layer family (csrc/sheared_conv.hip): the sheared and the any-shift first convolution.  entry: which entry point is
+ * meant; the sizes are the entry point's own (WG / WG2: row lengths of g and gcol; entries that do not take q, m0, WG, WG2 or flags
+ * ignore them).  The form id names the kernel instantiation.  Every launcher takes its rows per workgroup, chunks and LDS bytes from
+ * one host function, and the query reports what that function returns.
+ * info: [0] RB rows per workgroup, [1] row blocks (the last one holds H - (blocks - 1) * RB rows), [2] depth chunks (split
+ *       producers; chunk k holds planes k * per_chunk .. min(D, (k + 1) * per_chunk) - 1, none when k * per_chunk >= D) or column
+ *       chunks (weight gradient), [3] planes per chunk, columns per chunk (weight gradient) or the row width in threads
+ *       (warped_expand_backward), [4] grid.x, [5] grid.y * grid.z, [6] threads per workgroup, [7] dynamic LDS bytes. */
+enum snvc_first_layer_entry {
+    SNVC_FLE_SHEARED_EXPAND = 0,            /* snvc_sheared_expand, snvc_sheared_expand_amax without amax words */
+    SNVC_FLE_SHEARED_EXPAND_AMAX = 1,       /* snvc_sheared_expand_amax with amax words */
+    SNVC_FLE_SHEARED_EXPAND_STATS = 2,      /* snvc_sheared_expand_stats */
+    SNVC_FLE_SHEARED_EXPAND_SPLIT = 3,      /* snvc_sheared_expand_split */
+    SNVC_FLE_SHEARED_BACKWARD_REDUCE = 4,   /* snvc_sheared_backward_reduce */
+    SNVC_FLE_SHEARED_REDUCE = 5,            /* snvc_sheared_reduce */
+    SNVC_FLE_WARPED_EXPAND = 6,             /* snvc_warped_expand; flags & SNVC_WARPED_EXPAND_R3 selects the r3 kernel */
+    SNVC_FLE_WARPED_EXPAND_SPLIT = 7,       /* snvc_warped_expand_split */
+    SNVC_FLE_WARPED_EXPAND_BACKWARD = 8     /* snvc_warped_expand_backward */
+};
+enum snvc_first_layer_form_id {
+    SNVC_FL_EXPAND_Q1 = 1, SNVC_FL_EXPAND_Q2 = 2, SNVC_FL_EXPAND_Q4 = 3,                  /* sheared_expand_kernel<Q, 0> */
+    SNVC_FL_EXPAND_AMAX_Q1 = 4, SNVC_FL_EXPAND_AMAX_Q2 = 5, SNVC_FL_EXPAND_AMAX_Q4 = 6,   /* sheared_expand_kernel<Q, 2> */
+    SNVC_FL_STATS_Q1 = 7, SNVC_FL_STATS_Q2 = 8,                                           /* sheared_expand_kernel<Q, 1> + the norm finalize */
+    SNVC_FL_SPLIT_Q1 = 9, SNVC_FL_SPLIT_Q2 = 10, SNVC_FL_SPLIT_Q4 = 11,                   /* sheared_expand_split_kernel<Q> */
+    SNVC_FL_BWD_Q1 = 12, SNVC_FL_BWD_Q2 = 13,                                             /* sheared_bwd_kernel<Q> + sheared_fold_kernel */
+    SNVC_FL_REDUCE_Q1 = 14, SNVC_FL_REDUCE_Q2 = 15,                                       /* sheared_reduce_kernel<Q> */
+    SNVC_FL_WARPED_WIN = 16,                /* warped_expand_win_kernel */
+    SNVC_FL_WARPED_R3 = 17,                 /* warped_expand_kernel (SNVC_WARPED_EXPAND_R3) */
+    SNVC_FL_WARPED_SPLIT = 18,              /* warped_expand_split_kernel */
+    SNVC_FL_WARPED_BWD = 19,                /* warped_expand_bwd_kernel */
+    SNVC_FL_WGRAD = 20                      /* sheared_wgrad_kernel + sheared_wgrad_reduce_kernel */
+};
+SNVC_API int snvc_first_layer_form(int entry, int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int64_t WG2,
+                                   int flags, int64_t *info);
+/* snvc_sheared_wgrad.  info: [2] column chunks, [3] columns per chunk (the last chunk holds WU - (chunks - 1) * cols), [4] grid.x =
+ * H * chunks, [5] channel groups * N, [6] threads per workgroup. */
+SNVC_API int snvc_sheared_wgrad_form(int64_t N, int64_t C, int64_t CO, int64_t H, int64_t WU, int64_t *info);
 
 #ifdef __cplusplus
 }

@@ -11,7 +11,7 @@ from typing import Tuple
 
 from . import _lib
 
-_ABI = 3   # snvc_forms_abi_version() this binding was written against
+_ABI = 4   # snvc_forms_abi_version() this binding was written against
 
 c_i64 = ctypes.c_int64
 c_p = ctypes.c_void_p
@@ -31,6 +31,8 @@ SIGNATURES = {
     "snvc_voxel_gather_backward_form": (c_int, [c_i64] * 5 + [c_int, c_p]),
     "snvc_conv3d_wgrad_form": (c_int, [ctypes.POINTER(_lib.Conv3dDesc), c_int, c_int, c_p]),
     "snvc_conv3d_forward_form": (c_int, [ctypes.POINTER(_lib.Conv3dDesc)] + [c_int] * 6 + [c_p]),
+    "snvc_first_layer_form": (c_int, [c_int] + [c_i64] * 5 + [c_int, c_int, c_i64, c_i64, c_int, c_p]),
+    "snvc_sheared_wgrad_form": (c_int, [c_i64] * 5 + [c_p]),
 }
 
 # info slot names per query (the header's comments)
@@ -43,6 +45,11 @@ WGRAD_INFO = ("piece_bytes", "ws_bytes", "parts", "per_part", "grid_x", "grid_yz
 # slot 2 by family: tiles (direct, transposed), jobs (Winograd), 16-byte pieces per channel (streaming)
 CONV_FWD_INFO = ("piece_bytes", "epi", "tiles", "groups", "grid_x", "grid_yz", "threads", "lds")
 ENTRY_FORWARD, ENTRY_HEAD, ENTRY_SIDE_HEAD, ENTRY_STATS = 0, 1, 2, 3
+# the first-layer family: slot 2 / 3 are depth chunks / planes per chunk (split producers), column chunks / columns per chunk (weight
+# gradient); slot 3 of warped_expand_backward is the row width in threads
+FIRST_LAYER_INFO = ("RB", "blocks", "chunks", "per_chunk", "grid_x", "grid_yz", "threads", "lds")
+(FLE_SHEARED_EXPAND, FLE_SHEARED_EXPAND_AMAX, FLE_SHEARED_EXPAND_STATS, FLE_SHEARED_EXPAND_SPLIT, FLE_SHEARED_BACKWARD_REDUCE,
+ FLE_SHEARED_REDUCE, FLE_WARPED_EXPAND, FLE_WARPED_EXPAND_SPLIT, FLE_WARPED_EXPAND_BACKWARD) = range(9)
 
 _bound = None
 
@@ -105,6 +112,16 @@ def conv3d_forward(desc, entry=ENTRY_FORWARD, x_align=16, y_align=16, res_align=
     ``_lib.Conv3dDesc``.  Each ``*_align`` is the largest of 16 / 8 / 4 that divides the operand's address, 0 for NULL."""
     return _query(lambda *a: lib().snvc_conv3d_forward_form(ctypes.byref(desc), *a), CONV_FWD_INFO, entry, x_align, y_align, res_align,
                   planes_align, y_head_align)
+
+
+def first_layer(entry, n, c, d, h, w, q=1, m0=0, wg=1, wg2=1, flags=0):
+    """(form id, or 0 for no launch, or -status; info; error text) of the first-layer entry point ``entry`` (FLE_*) for these sizes;
+    ``wg`` / ``wg2``: the row lengths of g and gcol.  Entries that do not take q, m0, wg, wg2 or flags ignore them."""
+    return _query(lib().snvc_first_layer_form, FIRST_LAYER_INFO, entry, n, c, d, h, w, int(q), int(m0), wg, wg2, int(flags))
+
+
+def sheared_wgrad(n, c, co, h, wu):
+    return _query(lib().snvc_sheared_wgrad_form, FIRST_LAYER_INFO, n, c, co, h, wu)
 
 
 def address_align(ptr) -> int:

@@ -643,7 +643,7 @@ int snvc_cost_volume_backward(const void *grad, const void *shift, void *grad_le
     return fail(SNVC_ERR_UNSUPPORTED, "snvc_cost_volume_backward: dtype must be f32 or f64");
 }
 
-int snvc_forms_abi_version(void) { return 3; }
+int snvc_forms_abi_version(void) { return 4; }
 
 int snvc_cost_volume_forward_form(int64_t N, int64_t C, int64_t Hi, int64_t Wi, int64_t D, int64_t downsample, int dtype, int right_only,
                                   int aligned, int64_t *info) {

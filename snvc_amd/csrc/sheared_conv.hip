@@ -24,6 +24,7 @@
 // the factored path's (tests/test_gpu_parity.py::test_sheared_first_conv_*), fp32 summation order aside.
 #include "common.hpp"
 #include "elementwise_internal.hpp"
+#include "snvc_forms.h"
 
 namespace snvc {
 namespace {
@@ -1426,13 +1427,244 @@ int snvc_sheared_upsample(const float *right, float *out, int64_t N, int64_t C, 
     return check_launch("snvc_sheared_upsample");
 }
 
+// Launch geometry of the family: every launcher below takes it from one of the functions that follow, and the form queries at the
+// end of the file (include/snvc_forms.h) report what the same functions return.
+struct FirstLayerGeom {
+    int RB = 0, blocks = 0;              // rows per workgroup, row blocks
+    int chunks = 0, per_chunk = 0;       // depth chunks and planes per chunk (the weight gradient: column chunks, columns per chunk)
+    int64_t gx = 0, gyz = 0;             // grid.x, grid.y * grid.z
+    int threads = 0;
+    size_t lds = 0;                      // dynamic LDS bytes
+};
+
 // Launch geometry of sheared_expand_kernel, shared by the forward statistics pass
 static int sheared_expand_rows(int64_t N, int64_t C, int64_t H, int quads, size_t lds_floats_per_row) {
     int RB = 512 / quads;                       // rows per workgroup: as many as 512 threads cover ...
     if (RB > 8) RB = 8;
     while (RB > 1 && snvc::ceil_div<int64_t>(H, RB) * C * N < 4 * 256) RB = (RB + 1) / 2;      // ... while the chip stays covered
     while (RB > 1 && sizeof(float) * RB * lds_floats_per_row > 150 * 1024) --RB;              // ... and the rows fit the LDS
-    return RB;
+    return RB;                                  // (lds_floats_per_row = 0: the caller's LDS need is not linear in RB and it steps down itself)
+}
+
+// sheared_expand_kernel<Q, MODE>: snvc_sheared_expand[_amax] and snvc_sheared_expand_stats.  The caller refuses lds > 150 KiB.
+static FirstLayerGeom sheared_expand_geometry(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int64_t WG) {
+    using snvc::ceil_div;
+    FirstLayerGeom p;
+    const int quads = (int)(W / 4);
+    const int LW = (int)((WG + q - 1) / q) + 4;
+    p.RB = sheared_expand_rows(N, C, H, quads, (size_t)q * LW + (size_t)D);
+    p.blocks = (int)ceil_div<int64_t>(H, p.RB);
+    p.threads = ceil_div(p.RB * quads, 64) * 64;
+    p.lds = sizeof(float) * ((size_t)p.RB * q * LW + (size_t)p.RB * D);
+    p.gx = p.blocks;
+    p.gyz = C * N;
+    return p;
+}
+
+// Depth chunks of the two split producers: doubled while the launch has fewer than `per_cu` workgroups per CU and every chunk keeps at
+// least 8 planes, 16 at the most.  `lds_floats` is what a workgroup needs beside its 8 * DC plane values.
+static FirstLayerGeom split_expand_geometry(int64_t N, int64_t G, int64_t D, int64_t H, int64_t W, int per_cu, size_t lds_floats) {
+    using snvc::ceil_div;
+    FirstLayerGeom p;
+    int DCH = 1;
+    while (DCH < 16 && H * G * N * DCH < per_cu * 256 && D / (2 * DCH) >= 8) DCH *= 2;
+    p.RB = 1;
+    p.blocks = (int)H;
+    p.chunks = DCH;
+    p.per_chunk = (int)ceil_div<int64_t>(D, DCH);
+    p.lds = sizeof(float) * (lds_floats + 8 * (size_t)p.per_chunk);
+    p.threads = ceil_div((int)W, 64) * 64;
+    p.gx = H;
+    p.gyz = G * DCH * N;
+    return p;
+}
+
+// warped_expand_win_kernel, or warped_expand_kernel with SNVC_WARPED_EXPAND_R3: the row blocks of sheared_expand_rows with the
+// form's own LDS need per row.  The caller refuses lds > 150 KiB.
+static FirstLayerGeom warped_expand_geometry(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, bool r3) {
+    using snvc::ceil_div;
+    FirstLayerGeom p;
+    const int quads = (int)(W / 4);
+    int RB = sheared_expand_rows(N, C, H, quads, 0);
+    auto lds_of = [&](int rb) {
+        return r3 ? sizeof(float) * (2 * 3 * (size_t)rb * (2 * W + 8) + 3 * (size_t)rb * D)
+                  : sizeof(float) * (2 * 3 * (size_t)rb * (W + 16) + (size_t)rb * D + 4 + 4 * (size_t)(D + 2));
+    };
+    while (RB > 1 && lds_of(RB) > 150 * 1024) --RB;
+    p.RB = RB;
+    p.blocks = (int)ceil_div<int64_t>(H, RB);
+    p.threads = ceil_div(RB * quads, 64) * 64;
+    p.lds = lds_of(RB);
+    p.gx = p.blocks;
+    p.gyz = C * N;
+    return p;
+}
+
+// warped_expand_bwd_kernel: RB rows of TW = W rounded up to whole waves.  info reports TW as the columns per chunk.
+static FirstLayerGeom warped_expand_backward_geometry(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W) {
+    using snvc::ceil_div;
+    FirstLayerGeom p;
+    const int TW = ceil_div((int)W, 64) * 64;
+    int RB = 512 / TW;
+    if (RB < 1) RB = 1;
+    if (RB > H) RB = (int)H;
+    auto lds_of = [&](int rb) { return sizeof(float) * ((((size_t)rb * 16 * (W + 4) + 3) & ~(size_t)3) + 4 * (size_t)D); };
+    while (RB > 1 && lds_of(RB) > 150 * 1024) --RB;
+    p.RB = RB;
+    p.blocks = (int)ceil_div<int64_t>(H, RB);
+    p.chunks = 1;
+    p.per_chunk = TW;
+    p.threads = RB * TW;
+    p.lds = lds_of(RB);
+    p.gx = p.blocks;
+    p.gyz = C * N;
+    return p;
+}
+
+// sheared_bwd_kernel<Q>: four rows per workgroup, one lane per 8 columns.
+static FirstLayerGeom sheared_backward_geometry(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int64_t WG, int64_t WG2) {
+    FirstLayerGeom p;
+    const int LW = (int)((WG + q - 1) / q) + 4;
+    p.RB = 4;
+    p.blocks = (int)snvc::ceil_div<int64_t>(H, 4);
+    p.threads = 256;
+    p.lds = sizeof(float) * (4 * ((size_t)q * LW + D + 2 * WG + 2 * WG2));
+    p.gx = p.blocks;
+    p.gyz = C * N;
+    return p;
+}
+
+// sheared_reduce_kernel<Q>: one workgroup of 256 threads per row.
+static FirstLayerGeom sheared_reduce_geometry(int64_t N, int64_t C, int64_t H) {
+    FirstLayerGeom p;
+    p.RB = 1;
+    p.blocks = (int)H;
+    p.threads = 256;
+    p.gx = H;
+    p.gyz = C * N;
+    return p;
+}
+
+// The size checks of the entry points and the refusals that follow their pointer checks (*_plan), for the launcher and its query alike.
+static int sheared_expand_size_checks(bool stats, int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int64_t WG2) {
+    using namespace snvc;
+    if (stats) {
+        if (N <= 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || W % 4 != 0 || (q != 1 && q != 2) || m0 < 0 || WG <= 0 || WG2 <= 0)
+            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_stats: bad sizes (W % 4 == 0, q in {1,2}, D >= 2)");
+        return SNVC_OK;
+    }
+    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || W % 4 != 0 || (q != 1 && q != 2 && q != 4) || m0 < 0 || WG <= 0 || WG2 <= 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand: bad sizes (W % 4 == 0, q in {1,2,4}, D >= 2)");
+    return SNVC_OK;
+}
+
+static int sheared_expand_plan(bool stats, int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int64_t WG, FirstLayerGeom &p) {
+    using namespace snvc;
+    if (W / 4 > 512 || C > 65535 || N > 65535)
+        return fail(SNVC_ERR_UNSUPPORTED, stats ? "snvc_sheared_expand_stats: row too wide or too many channels"
+                                                : "snvc_sheared_expand: row too wide or too many channels");
+    p = sheared_expand_geometry(N, C, D, H, W, q, WG);
+    if (p.lds > 150 * 1024)
+        return fail(SNVC_ERR_UNSUPPORTED, stats ? "snvc_sheared_expand_stats: rows do not fit the LDS" : "snvc_sheared_expand: rows do not fit the LDS");
+    return SNVC_OK;
+}
+
+static int sheared_expand_split_size_checks(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int64_t WG2) {
+    using namespace snvc;
+    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || (q != 1 && q != 2 && q != 4) || m0 < 0 || WG <= 0 || WG2 <= 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_split: bad sizes (q in {1,2,4}, D >= 2)");
+    return SNVC_OK;
+}
+
+static int sheared_expand_split_plan(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int64_t WG, FirstLayerGeom &p) {
+    using namespace snvc;
+    const int64_t G = ceil_div<int64_t>(C, 8);
+    if (W > 512 || G > 4095 || N > 65535 || H >= ((int64_t)1 << 31))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_split: row too wide (W <= 512) or too many channels");
+    const int LW = (int)((WG + q - 1) / q) + 4;
+    // depth chunks: at least two workgroups per CU, at least 8 planes each -- and no more: all of the launch's workgroups resident at
+    // once (five fit a CU) and long walks measure best (r5, cfg2's 96 rows x 4 groups: 1 chunk 166 us, 2: 156, 4: 169, 8: 171, 16: 180)
+    p = split_expand_geometry(N, G, D, H, W, 2, 8 * (size_t)q * LW);
+    if (p.lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_split: the row does not fit the LDS");
+    return SNVC_OK;
+}
+
+static int sheared_backward_size_checks(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int64_t WG2) {
+    using namespace snvc;
+    if (N <= 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || W % 8 != 0 || W > 512 || (q != 1 && q != 2) || m0 < 0 || WG <= 0 || WG2 <= 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_backward_reduce: bad sizes (W % 8 == 0, W <= 512, q in {1,2}, D >= 2)");
+    return SNVC_OK;
+}
+
+static int sheared_backward_plan(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int64_t WG, int64_t WG2, FirstLayerGeom &p) {
+    using namespace snvc;
+    if (C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_backward_reduce: too many channels or samples");
+    p = sheared_backward_geometry(N, C, D, H, W, q, WG, WG2);
+    if (p.lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_backward_reduce: rows do not fit the LDS");
+    return SNVC_OK;
+}
+
+static int warped_expand_size_checks(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W) {
+    using namespace snvc;
+    if (N < 0 || C <= 0 || D < 1 || H <= 0 || W <= 0 || W % 4 != 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand: bad sizes (W % 4 == 0)");
+    return SNVC_OK;
+}
+
+static int warped_expand_plan(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int flags, FirstLayerGeom &p) {
+    using namespace snvc;
+    if (W / 4 > 512 || C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: row too wide or too many channels");
+    p = warped_expand_geometry(N, C, D, H, W, (flags & SNVC_WARPED_EXPAND_R3) != 0);
+    if (p.lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: rows do not fit the LDS");
+    return SNVC_OK;
+}
+
+static int warped_expand_backward_size_checks(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W) {
+    using namespace snvc;
+    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W <= 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand_backward: bad sizes (D >= 2)");
+    return SNVC_OK;
+}
+
+static int warped_expand_backward_plan(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, FirstLayerGeom &p) {
+    using namespace snvc;
+    if (W > 1024 || C > 65535 || N > 65535 || H * W >= ((int64_t)1 << 31))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_backward: W <= 1024, C and N <= 65535");
+    p = warped_expand_backward_geometry(N, C, D, H, W);
+    if (p.lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_backward: rows do not fit the LDS");
+    return SNVC_OK;
+}
+
+static int warped_expand_split_size_checks(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W) {
+    using namespace snvc;
+    if (N < 0 || C <= 0 || D < 1 || H <= 0 || W <= 0 || W % 4 != 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand_split: bad sizes (W % 4 == 0)");
+    return SNVC_OK;
+}
+
+static int warped_expand_split_plan(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, FirstLayerGeom &p) {
+    using namespace snvc;
+    const int64_t G = ceil_div<int64_t>(C, 8);
+    if (W > 512 || G > 4095 || N > 65535 || H >= ((int64_t)1 << 31))
+        return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_split: row too wide (W <= 512) or too many channels");
+    // depth chunks: about three workgroups per CU (four fit; every workgroup re-stages its 24 rows).  r5, cfg2: 1 chunk 251 us, 2 chunks
+    // 185, 4 chunks 225
+    p = split_expand_geometry(N, G, D, H, W, 3, 24 * (size_t)(W + 16) + 96 + 4 + 4 * (size_t)(D + 2));
+    if (p.lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_split: the row does not fit the LDS");
+    return SNVC_OK;
+}
+
+static int sheared_reduce_size_checks(int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int64_t WG2) {
+    using namespace snvc;
+    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W < 2 || (q != 1 && q != 2) || m0 < 0 || WG <= 0 || WG2 <= 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_reduce: bad sizes (q in {1,2}, D >= 2, W >= 2)");
+    return SNVC_OK;
+}
+
+static int sheared_reduce_plan(int64_t N, int64_t C, int64_t H, FirstLayerGeom &p) {
+    using namespace snvc;
+    if (C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_reduce: too many channels or samples");
+    p = sheared_reduce_geometry(N, C, H);
+    return SNVC_OK;
 }
 
 int snvc_sheared_expand(const float *g, const float *gcol, const float *planes, const float *scale, const float *bias, float *y,
@@ -1445,8 +1677,7 @@ int snvc_sheared_expand_amax(const float *g, const float *gcol, const float *pla
                              int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int off, int64_t WG2,
                              int off2, int flags, uint32_t *amax, void *stream) {
     using namespace snvc;
-    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || W % 4 != 0 || (q != 1 && q != 2 && q != 4) || m0 < 0 || WG <= 0 || WG2 <= 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand: bad sizes (W % 4 == 0, q in {1,2,4}, D >= 2)");
+    if (const int rc = sheared_expand_size_checks(false, N, C, D, H, W, q, m0, WG, WG2)) return rc;
     if ((scale == nullptr) != (bias == nullptr))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand: scale and bias must both be given or both be NULL");
     if (flags & ~SNVC_EPI_RELU) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand: only SNVC_EPI_RELU");
@@ -1454,14 +1685,11 @@ int snvc_sheared_expand_amax(const float *g, const float *gcol, const float *pla
     if (!g || !gcol || !y) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand: null pointer");
     if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(planes)) & 15)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand: y and planes must be 16-byte aligned");
-    const int quads = (int)(W / 4);
-    if (quads > 512 || C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand: row too wide or too many channels");
-    const int LW = (int)((WG + q - 1) / q) + 4;
-    const int RB = sheared_expand_rows(N, C, H, quads, (size_t)q * LW + (size_t)D);
-    const int threads = ceil_div(RB * quads, 64) * 64;
-    const size_t lds = sizeof(float) * ((size_t)RB * q * LW + (size_t)RB * D);
-    if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand: rows do not fit the LDS");
-    const dim3 grid((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N);
+    FirstLayerGeom p;
+    if (const int rc = sheared_expand_plan(false, N, C, D, H, W, q, WG, p)) return rc;
+    const int RB = p.RB, threads = p.threads;
+    const size_t lds = p.lds;
+    const dim3 grid((unsigned)p.blocks, (unsigned)C, (unsigned)N);
     if (q == 4) {      // r6: four phases (downsample 2 with half-pixel planes, downsample 4 with whole-pixel planes: index 4 w - m0 - d)
         if (!amax)
             launch_lds<sheared_expand_kernel<4, 0>>(grid, threads, lds, as_stream(stream), g, gcol, planes, scale, bias, y, nullptr, (int)C, (int)D, (int)H,
@@ -1491,8 +1719,7 @@ int snvc_sheared_expand_split(const float *g, const float *gcol, const float *pl
                               void *y_lo, int *overflow, int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG,
                               int off, int64_t WG2, int off2, int64_t y_batch_stride, int flags, void *stream) {
     using namespace snvc;
-    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || (q != 1 && q != 2 && q != 4) || m0 < 0 || WG <= 0 || WG2 <= 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_split: bad sizes (q in {1,2,4}, D >= 2)");
+    if (const int rc = sheared_expand_split_size_checks(N, C, D, H, W, q, m0, WG, WG2)) return rc;
     if ((scale == nullptr) != (bias == nullptr))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_split: scale and bias must both be given or both be NULL");
     if (flags & ~(SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_split: only SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT");
@@ -1501,17 +1728,10 @@ int snvc_sheared_expand_split(const float *g, const float *gcol, const float *pl
     if ((reinterpret_cast<uintptr_t>(y_hi) | reinterpret_cast<uintptr_t>(y_lo)) & 15)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_split: y must be 16-byte aligned");
     const int64_t G = ceil_div<int64_t>(C, 8);
-    if (W > 512 || G > 4095 || N > 65535 || H >= ((int64_t)1 << 31))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_split: row too wide (W <= 512) or too many channels");
-    const int LW = (int)((WG + q - 1) / q) + 4;
-    // depth chunks: at least two workgroups per CU, at least 8 planes each -- and no more: all of the launch's workgroups resident at
-    // once (five fit a CU) and long walks measure best (r5, cfg2's 96 rows x 4 groups: 1 chunk 166 us, 2: 156, 4: 169, 8: 171, 16: 180)
-    int DCH = 1;
-    while (DCH < 16 && H * G * N * DCH < 2 * 256 && D / (2 * DCH) >= 8) DCH *= 2;
-    const int DC = (int)ceil_div<int64_t>(D, DCH);
-    const size_t lds = sizeof(float) * (8 * (size_t)q * LW + 8 * (size_t)DC);
-    if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_split: the row does not fit the LDS");
-    const int threads = ceil_div((int)W, 64) * 64;
+    FirstLayerGeom p;
+    if (const int rc = sheared_expand_split_plan(N, C, D, H, W, q, WG, p)) return rc;
+    const int DCH = p.chunks, DC = p.per_chunk, threads = p.threads;
+    const size_t lds = p.lds;
     const dim3 grid((unsigned)H, (unsigned)(G * DCH), (unsigned)N);
     const int64_t y_bs = y_batch_stride ? y_batch_stride : 2 * G * 8 * D * H * W;
     _Float16 *yh = reinterpret_cast<_Float16 *>(y_hi), *yl = reinterpret_cast<_Float16 *>(y_lo);
@@ -1537,18 +1757,14 @@ int snvc_sheared_expand_stats(const float *g, const float *gcol, const float *pl
                               int64_t H, int64_t W, int q, int m0, int64_t WG, int off, int64_t WG2, int off2, float eps,
                               void *stream) {
     using namespace snvc;
-    if (N <= 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || W % 4 != 0 || (q != 1 && q != 2) || m0 < 0 || WG <= 0 || WG2 <= 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_stats: bad sizes (W % 4 == 0, q in {1,2}, D >= 2)");
+    if (const int rc = sheared_expand_size_checks(true, N, C, D, H, W, q, m0, WG, WG2)) return rc;
     if (!g || !gcol || !scale || !shift || !workspace) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_stats: null pointer");
     if (reinterpret_cast<uintptr_t>(planes) & 15) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_expand_stats: planes must be 16-byte aligned");
-    const int quads = (int)(W / 4);
-    if (quads > 512 || C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_stats: row too wide or too many channels");
-    const int LW = (int)((WG + q - 1) / q) + 4;
-    const int RB = sheared_expand_rows(N, C, H, quads, (size_t)q * LW + (size_t)D);
-    const int threads = ceil_div(RB * quads, 64) * 64;
-    const size_t lds = sizeof(float) * ((size_t)RB * q * LW + (size_t)RB * D);
-    if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_stats: rows do not fit the LDS");
-    const dim3 grid((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N);
+    FirstLayerGeom p;
+    if (const int rc = sheared_expand_plan(true, N, C, D, H, W, q, WG, p)) return rc;
+    const int RB = p.RB, threads = p.threads;
+    const size_t lds = p.lds;
+    const dim3 grid((unsigned)p.blocks, (unsigned)C, (unsigned)N);
     double *partial = static_cast<double *>(workspace);
     if (q == 1)
         launch_lds<sheared_expand_kernel<1, 1>>(grid, threads, lds, as_stream(stream), g, gcol, planes, nullptr, nullptr, nullptr, partial, (int)C, (int)D,
@@ -1572,22 +1788,20 @@ int snvc_sheared_backward_reduce(const float *g, const float *gcol, const float 
                                  int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int off, int64_t WG2, int off2,
                                  void *stream) {
     using namespace snvc;
-    if (N <= 0 || C <= 0 || D < 2 || H <= 0 || W <= 0 || W % 8 != 0 || W > 512 || (q != 1 && q != 2) || m0 < 0 || WG <= 0 || WG2 <= 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_backward_reduce: bad sizes (W % 8 == 0, W <= 512, q in {1,2}, D >= 2)");
+    if (const int rc = sheared_backward_size_checks(N, C, D, H, W, q, m0, WG, WG2)) return rc;
     if (!g || !gcol || !planes || !scale || !shift || !gy || !line || !colsum || !lastc || !sums || !workspace)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_backward_reduce: null pointer");
     if (reinterpret_cast<uintptr_t>(gy) & 15) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_backward_reduce: gy must be 16-byte aligned");
-    if (C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_backward_reduce: too many channels or samples");
-    const int LW = (int)((WG + q - 1) / q) + 4;
-    const size_t lds = sizeof(float) * (4 * ((size_t)q * LW + D + 2 * WG + 2 * WG2));
-    if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_backward_reduce: rows do not fit the LDS");
-    const dim3 grid((unsigned)ceil_div<int64_t>(H, 4), (unsigned)C, (unsigned)N);
+    FirstLayerGeom p;
+    if (const int rc = sheared_backward_plan(N, C, D, H, W, q, WG, WG2, p)) return rc;
+    const size_t lds = p.lds;
+    const dim3 grid((unsigned)p.blocks, (unsigned)C, (unsigned)N);
     double *partial = static_cast<double *>(workspace);
     if (q == 1)
-        launch_lds<sheared_bwd_kernel<1>>(grid, 256, lds, as_stream(stream), g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
+        launch_lds<sheared_bwd_kernel<1>>(grid, p.threads, lds, as_stream(stream), g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
                                           (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2);
     else
-        launch_lds<sheared_bwd_kernel<2>>(grid, 256, lds, as_stream(stream), g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
+        launch_lds<sheared_bwd_kernel<2>>(grid, p.threads, lds, as_stream(stream), g, gcol, planes, scale, shift, gy, line, colsum, lastc, partial, (int)N, (int)C,
                                           (int)D, (int)H, (int)W, m0, (int)WG, off, (int)WG2, off2);
     int rc = check_launch("snvc_sheared_backward_reduce");
     if (rc) return rc;
@@ -1598,8 +1812,7 @@ int snvc_sheared_backward_reduce(const float *g, const float *gcol, const float 
 int snvc_warped_expand(const float *p, const float *q, const float *e, const float *planes, const float *shift, const float *scale,
                        const float *bias, float *y, int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int flags, void *stream) {
     using namespace snvc;
-    if (N < 0 || C <= 0 || D < 1 || H <= 0 || W <= 0 || W % 4 != 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand: bad sizes (W % 4 == 0)");
+    if (const int rc = warped_expand_size_checks(N, C, D, H, W)) return rc;
     if ((scale == nullptr) != (bias == nullptr))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand: scale and bias must both be given or both be NULL");
     if (flags & ~(SNVC_EPI_RELU | SNVC_WARPED_EXPAND_R3)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: only SNVC_EPI_RELU");
@@ -1607,48 +1820,29 @@ int snvc_warped_expand(const float *p, const float *q, const float *e, const flo
     if (!p || !q || !e || !shift || !y) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand: null pointer");
     if ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(planes) | reinterpret_cast<uintptr_t>(p)) & 15)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand: p, y and planes must be 16-byte aligned");
-    const int quads = (int)(W / 4);
-    if (quads > 512 || C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: row too wide or too many channels");
-    int RB = 512 / quads;
-    if (RB > 8) RB = 8;
-    while (RB > 1 && ceil_div<int64_t>(H, RB) * C * N < 4 * 256) RB = (RB + 1) / 2;
+    FirstLayerGeom g;
+    if (const int rc = warped_expand_plan(N, C, D, H, W, flags, g)) return rc;
+    const dim3 grid((unsigned)g.blocks, (unsigned)C, (unsigned)N);
     if (flags & SNVC_WARPED_EXPAND_R3) {        // the r3 form (four 16-byte LDS reads per kd and plane): kept for A/B tests
-        while (RB > 1 && sizeof(float) * (2 * 3 * (size_t)RB * (2 * W + 8) + 3 * (size_t)RB * D) > 150 * 1024) --RB;
-        const int threads = ceil_div(RB * quads, 64) * 64;
-        const size_t lds = sizeof(float) * (2 * 3 * (size_t)RB * (2 * W + 8) + 3 * (size_t)RB * D);
-        if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: rows do not fit the LDS");
-        launch_lds<warped_expand_kernel>(dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), threads, lds, as_stream(stream), p, q, e, planes,
-                                         shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W, RB, flags & SNVC_EPI_RELU);
+        launch_lds<warped_expand_kernel>(grid, g.threads, g.lds, as_stream(stream), p, q, e, planes, shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W,
+                                         g.RB, flags & SNVC_EPI_RELU);
         return check_launch("snvc_warped_expand");
     }
-    auto lds_of = [&](int rb) { return sizeof(float) * (2 * 3 * (size_t)rb * (W + 16) + (size_t)rb * D + 4 + 4 * (size_t)(D + 2)); };
-    while (RB > 1 && lds_of(RB) > 150 * 1024) --RB;
-    const int threads = ceil_div(RB * quads, 64) * 64;
-    const size_t lds = lds_of(RB);
-    if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: rows do not fit the LDS");
-    launch_lds<warped_expand_win_kernel>(dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), threads, lds, as_stream(stream), p, q, e, planes,
-                                         shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W, RB, flags);
+    launch_lds<warped_expand_win_kernel>(grid, g.threads, g.lds, as_stream(stream), p, q, e, planes, shift, scale, bias, y, (int)C, (int)D, (int)H, (int)W,
+                                         g.RB, flags);
     return check_launch("snvc_warped_expand");
 }
 
 int snvc_warped_expand_backward(const float *dy, const float *shift, float *a, float *dplanes, int64_t N, int64_t C, int64_t D,
                                 int64_t H, int64_t W, void *stream) {
     using namespace snvc;
-    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W <= 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand_backward: bad sizes (D >= 2)");
+    if (const int rc = warped_expand_backward_size_checks(N, C, D, H, W)) return rc;
     if (N == 0) return SNVC_OK;
     if (!dy || !shift || !a) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand_backward: null pointer");
-    if (W > 1024 || C > 65535 || N > 65535 || H * W >= ((int64_t)1 << 31))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_backward: W <= 1024, C and N <= 65535");
-    const int TW = ceil_div((int)W, 64) * 64;
-    int RB = 512 / TW;
-    if (RB < 1) RB = 1;
-    if (RB > H) RB = (int)H;
-    auto lds_of = [&](int rb) { return sizeof(float) * ((((size_t)rb * 16 * (W + 4) + 3) & ~(size_t)3) + 4 * (size_t)D); };
-    while (RB > 1 && lds_of(RB) > 150 * 1024) --RB;
-    const size_t lds = lds_of(RB);
-    if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_backward: rows do not fit the LDS");
-    launch_lds<warped_expand_bwd_kernel>(dim3((unsigned)ceil_div<int64_t>(H, RB), (unsigned)C, (unsigned)N), RB * TW, lds, as_stream(stream), dy, shift, a,
-                                         dplanes, (int)C, (int)D, (int)H, (int)W, RB, TW);
+    FirstLayerGeom g;
+    if (const int rc = warped_expand_backward_plan(N, C, D, H, W, g)) return rc;
+    launch_lds<warped_expand_bwd_kernel>(dim3((unsigned)g.blocks, (unsigned)C, (unsigned)N), g.threads, g.lds, as_stream(stream), dy, shift, a, dplanes,
+                                         (int)C, (int)D, (int)H, (int)W, g.RB, g.per_chunk);
     return check_launch("snvc_warped_expand_backward");
 }
 
@@ -1656,8 +1850,7 @@ int snvc_warped_expand_split(const float *p, const float *q, const float *e, con
                              const float *bias, void *y_hi, void *y_lo, int *overflow, int64_t N, int64_t C, int64_t D, int64_t H,
                              int64_t W, int64_t y_batch_stride, int flags, void *stream) {
     using namespace snvc;
-    if (N < 0 || C <= 0 || D < 1 || H <= 0 || W <= 0 || W % 4 != 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand_split: bad sizes (W % 4 == 0)");
+    if (const int rc = warped_expand_split_size_checks(N, C, D, H, W)) return rc;
     if ((scale == nullptr) != (bias == nullptr))
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand_split: scale and bias must both be given or both be NULL");
     if (flags & ~(SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_split: only SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT");
@@ -1666,15 +1859,10 @@ int snvc_warped_expand_split(const float *p, const float *q, const float *e, con
     if ((reinterpret_cast<uintptr_t>(y_hi) | reinterpret_cast<uintptr_t>(y_lo) | reinterpret_cast<uintptr_t>(p)) & 15)
         return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_warped_expand_split: p and y must be 16-byte aligned");
     const int64_t G = ceil_div<int64_t>(C, 8);
-    if (W > 512 || G > 4095 || N > 65535 || H >= ((int64_t)1 << 31))
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_split: row too wide (W <= 512) or too many channels");
-    int DCH = 1;         // depth chunks: about three workgroups per CU (four fit; every workgroup re-stages its 24 rows).  r5, cfg2: 1 chunk
-                         // 251 us, 2 chunks 185, 4 chunks 225
-    while (DCH < 16 && H * G * N * DCH < 3 * 256 && D / (2 * DCH) >= 8) DCH *= 2;
-    const int DC = (int)ceil_div<int64_t>(D, DCH);
-    const size_t lds = sizeof(float) * (24 * (size_t)(W + 16) + 96 + 8 * (size_t)DC + 4 + 4 * (size_t)(D + 2));
-    if (lds > 150 * 1024) return fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_split: the row does not fit the LDS");
-    const int threads = ceil_div((int)W, 64) * 64;
+    FirstLayerGeom g;
+    if (const int rc = warped_expand_split_plan(N, C, D, H, W, g)) return rc;
+    const int DCH = g.chunks, DC = g.per_chunk, threads = g.threads;
+    const size_t lds = g.lds;
     const dim3 grid((unsigned)H, (unsigned)(G * DCH), (unsigned)N);
     const int64_t y_bs = y_batch_stride ? y_batch_stride : 2 * G * 8 * D * H * W;
     launch_lds<warped_expand_split_kernel>(grid, threads, lds, as_stream(stream), p, q, e, planes, shift, scale, bias, reinterpret_cast<_Float16 *>(y_hi),
@@ -1694,17 +1882,17 @@ int snvc_shift_structure(const float *shift, float *out4, int64_t N, int64_t D, 
 int snvc_sheared_reduce(const float *dy, float *dg, float *dgcol, int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q,
                         int m0, int64_t WG, int off, int64_t WG2, int off2, void *stream) {
     using namespace snvc;
-    if (N < 0 || C <= 0 || D < 2 || H <= 0 || W < 2 || (q != 1 && q != 2) || m0 < 0 || WG <= 0 || WG2 <= 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_reduce: bad sizes (q in {1,2}, D >= 2, W >= 2)");
+    if (const int rc = sheared_reduce_size_checks(N, C, D, H, W, q, m0, WG, WG2)) return rc;
     if (N == 0) return SNVC_OK;
     if (!dy || !dg || !dgcol) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_reduce: null pointer");
-    if (C > 65535 || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_reduce: too many channels or samples");
-    const dim3 grid((unsigned)H, (unsigned)C, (unsigned)N);
+    FirstLayerGeom p;
+    if (const int rc = sheared_reduce_plan(N, C, H, p)) return rc;
+    const dim3 grid((unsigned)p.gx, (unsigned)C, (unsigned)N);
     if (q == 1)
-        sheared_reduce_kernel<1><<<grid, 256, 0, as_stream(stream)>>>(dy, dg, dgcol, (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off,
+        sheared_reduce_kernel<1><<<grid, p.threads, 0, as_stream(stream)>>>(dy, dg, dgcol, (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off,
                                                                      (int)WG2, off2);
     else
-        sheared_reduce_kernel<2><<<grid, 256, 0, as_stream(stream)>>>(dy, dg, dgcol, (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off,
+        sheared_reduce_kernel<2><<<grid, p.threads, 0, as_stream(stream)>>>(dy, dg, dgcol, (int)C, (int)D, (int)H, (int)W, m0, (int)WG, off,
                                                                      (int)WG2, off2);
     return check_launch("snvc_sheared_reduce");
 }
@@ -1713,6 +1901,26 @@ static void sheared_wgrad_geometry(int64_t WU, int &col_chunks, int &chunk_cols)
     using snvc::ceil_div;
     col_chunks = WU > 320 ? 2 : 1;                                     // two workgroups per row on the wide grid
     chunk_cols = (int)((ceil_div<int64_t>(WU, col_chunks) + snvc::SW_IC - 1) / snvc::SW_IC * snvc::SW_IC);
+}
+
+static int sheared_wgrad_size_checks(int64_t N, int64_t C, int64_t CO, int64_t H, int64_t WU) {
+    using namespace snvc;
+    if (N <= 0 || C <= 0 || C > 32 || CO <= 0 || H <= 0 || WU <= 0)
+        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_wgrad: bad sizes (1 <= C <= 32)");
+    return SNVC_OK;
+}
+
+// sheared_wgrad_kernel: one workgroup per (row, column chunk), channel group and sample
+static int sheared_wgrad_plan(int64_t N, int64_t CO, int64_t H, int64_t WU, FirstLayerGeom &p) {
+    using namespace snvc;
+    sheared_wgrad_geometry(WU, p.chunks, p.per_chunk);
+    if (N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_wgrad: too many samples");
+    p.RB = 1;
+    p.blocks = (int)H;
+    p.gx = H * p.chunks;
+    p.gyz = ((CO + 31) / 32) * N;
+    p.threads = 256;
+    return SNVC_OK;
 }
 
 int64_t snvc_sheared_wgrad_workspace_bytes(int64_t N, int64_t CO, int64_t H, int64_t WU) {
@@ -1725,14 +1933,12 @@ int64_t snvc_sheared_wgrad_workspace_bytes(int64_t N, int64_t CO, int64_t H, int
 int snvc_sheared_wgrad(const float *x, const float *dy, float *dk, void *workspace, int64_t N, int64_t C, int64_t CO, int64_t H,
                        int64_t WU, void *stream) {
     using namespace snvc;
-    if (N <= 0 || C <= 0 || C > 32 || CO <= 0 || H <= 0 || WU <= 0)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_wgrad: bad sizes (1 <= C <= 32)");
+    if (const int rc = sheared_wgrad_size_checks(N, C, CO, H, WU)) return rc;
     if (!x || !dy || !dk || !workspace) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_wgrad: null pointer");
-    int cc, cols;
-    sheared_wgrad_geometry(WU, cc, cols);
-    const int groups = (int)((CO + 31) / 32), nwg = (int)(H * cc);
-    if (N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_wgrad: too many samples");
-    sheared_wgrad_kernel<<<dim3((unsigned)nwg, (unsigned)groups, (unsigned)N), 256, 0, as_stream(stream)>>>(
+    FirstLayerGeom p;
+    if (const int rc = sheared_wgrad_plan(N, CO, H, WU, p)) return rc;
+    const int cc = p.chunks, cols = p.per_chunk, groups = (int)((CO + 31) / 32), nwg = (int)p.gx;
+    sheared_wgrad_kernel<<<dim3((unsigned)nwg, (unsigned)groups, (unsigned)N), p.threads, 0, as_stream(stream)>>>(
         x, dy, static_cast<float *>(workspace), (int)C, (int)CO, (int)H, (int)WU, cc, cols);
     sheared_wgrad_reduce_kernel<<<(unsigned)ceil_div(groups * 21 * 1024, 256), 256, 0, as_stream(stream)>>>(
         static_cast<const float *>(workspace), dk, (int)C, (int)CO, (int)N, groups, nwg);
@@ -1750,6 +1956,82 @@ int snvc_sheared_upsample_backward(const float *drq, float *dright, int64_t N, i
     sheared_upsample_bwd_kernel<<<(unsigned)ceil_div<int64_t>(total, 256), 256, 0, as_stream(stream)>>>(drq, dright, (int)W, q, (int)WU,
                                                                                                          off, rows);
     return check_launch("snvc_sheared_upsample_backward");
+}
+
+// ---- form queries (include/snvc_forms.h): the checks and the geometry functions of the launchers above, nothing launched ----
+static int first_layer_info(int form, const FirstLayerGeom &p, int64_t *info) {
+    const int64_t v[SNVC_FORMS_INFO] = {p.RB, p.blocks, p.chunks, p.per_chunk, p.gx, p.gyz, p.threads, (int64_t)p.lds};
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = v[i];
+    return form;
+}
+
+int snvc_first_layer_form(int entry, int64_t N, int64_t C, int64_t D, int64_t H, int64_t W, int q, int m0, int64_t WG, int64_t WG2, int flags,
+                          int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_first_layer_form: info is NULL");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    FirstLayerGeom p;
+    switch (entry) {
+    case SNVC_FLE_SHEARED_EXPAND:
+    case SNVC_FLE_SHEARED_EXPAND_AMAX: {
+        if (const int rc = sheared_expand_size_checks(false, N, C, D, H, W, q, m0, WG, WG2)) return -rc;
+        if (flags & ~SNVC_EPI_RELU) return -fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand: only SNVC_EPI_RELU");
+        if (N == 0) return 0;
+        if (const int rc = sheared_expand_plan(false, N, C, D, H, W, q, WG, p)) return -rc;
+        const int base = entry == SNVC_FLE_SHEARED_EXPAND ? SNVC_FL_EXPAND_Q1 : SNVC_FL_EXPAND_AMAX_Q1;
+        return first_layer_info(base + (q == 1 ? 0 : q == 2 ? 1 : 2), p, info);
+    }
+    case SNVC_FLE_SHEARED_EXPAND_STATS:
+        if (const int rc = sheared_expand_size_checks(true, N, C, D, H, W, q, m0, WG, WG2)) return -rc;
+        if (const int rc = sheared_expand_plan(true, N, C, D, H, W, q, WG, p)) return -rc;
+        return first_layer_info(q == 1 ? SNVC_FL_STATS_Q1 : SNVC_FL_STATS_Q2, p, info);
+    case SNVC_FLE_SHEARED_EXPAND_SPLIT:
+        if (const int rc = sheared_expand_split_size_checks(N, C, D, H, W, q, m0, WG, WG2)) return -rc;
+        if (flags & ~(SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT))
+            return -fail(SNVC_ERR_UNSUPPORTED, "snvc_sheared_expand_split: only SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT");
+        if (N == 0) return 0;
+        if (const int rc = sheared_expand_split_plan(N, C, D, H, W, q, WG, p)) return -rc;
+        return first_layer_info(q == 1 ? SNVC_FL_SPLIT_Q1 : q == 2 ? SNVC_FL_SPLIT_Q2 : SNVC_FL_SPLIT_Q4, p, info);
+    case SNVC_FLE_SHEARED_BACKWARD_REDUCE:
+        if (const int rc = sheared_backward_size_checks(N, C, D, H, W, q, m0, WG, WG2)) return -rc;
+        if (const int rc = sheared_backward_plan(N, C, D, H, W, q, WG, WG2, p)) return -rc;
+        return first_layer_info(q == 1 ? SNVC_FL_BWD_Q1 : SNVC_FL_BWD_Q2, p, info);
+    case SNVC_FLE_SHEARED_REDUCE:
+        if (const int rc = sheared_reduce_size_checks(N, C, D, H, W, q, m0, WG, WG2)) return -rc;
+        if (N == 0) return 0;
+        if (const int rc = sheared_reduce_plan(N, C, H, p)) return -rc;
+        return first_layer_info(q == 1 ? SNVC_FL_REDUCE_Q1 : SNVC_FL_REDUCE_Q2, p, info);
+    case SNVC_FLE_WARPED_EXPAND:
+        if (const int rc = warped_expand_size_checks(N, C, D, H, W)) return -rc;
+        if (flags & ~(SNVC_EPI_RELU | SNVC_WARPED_EXPAND_R3)) return -fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand: only SNVC_EPI_RELU");
+        if (N == 0) return 0;
+        if (const int rc = warped_expand_plan(N, C, D, H, W, flags, p)) return -rc;
+        return first_layer_info((flags & SNVC_WARPED_EXPAND_R3) ? SNVC_FL_WARPED_R3 : SNVC_FL_WARPED_WIN, p, info);
+    case SNVC_FLE_WARPED_EXPAND_SPLIT:
+        if (const int rc = warped_expand_split_size_checks(N, C, D, H, W)) return -rc;
+        if (flags & ~(SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT))
+            return -fail(SNVC_ERR_UNSUPPORTED, "snvc_warped_expand_split: only SNVC_EPI_RELU | SNVC_EPI_STREAM_OUT");
+        if (N == 0) return 0;
+        if (const int rc = warped_expand_split_plan(N, C, D, H, W, p)) return -rc;
+        return first_layer_info(SNVC_FL_WARPED_SPLIT, p, info);
+    case SNVC_FLE_WARPED_EXPAND_BACKWARD:
+        if (const int rc = warped_expand_backward_size_checks(N, C, D, H, W)) return -rc;
+        if (N == 0) return 0;
+        if (const int rc = warped_expand_backward_plan(N, C, D, H, W, p)) return -rc;
+        return first_layer_info(SNVC_FL_WARPED_BWD, p, info);
+    default:
+        return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_first_layer_form: unknown entry");
+    }
+}
+
+int snvc_sheared_wgrad_form(int64_t N, int64_t C, int64_t CO, int64_t H, int64_t WU, int64_t *info) {
+    using namespace snvc;
+    if (!info) return -fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_sheared_wgrad_form: info is NULL");
+    for (int i = 0; i < SNVC_FORMS_INFO; ++i) info[i] = 0;
+    if (const int rc = sheared_wgrad_size_checks(N, C, CO, H, WU)) return -rc;
+    FirstLayerGeom p;
+    if (const int rc = sheared_wgrad_plan(N, CO, H, WU, p)) return -rc;
+    return first_layer_info(SNVC_FL_WGRAD, p, info);
 }
 
 }  // extern "C"

@@ -134,7 +134,7 @@ def test_binding_matches_the_header():
     from snvc_amd import _forms
     params = re.search(r"SNVC_API[^;(]*\bsnvc_conv3d_forward_form\s*\(([^)]*)\)", HEADER).group(1)
     assert len(_forms.SIGNATURES["snvc_conv3d_forward_form"][1]) == params.count(",") + 1 == 8
-    assert len(_forms.CONV_FWD_INFO) == _forms.INFO and _forms.lib().snvc_forms_abi_version() == _forms._ABI == 3
+    assert len(_forms.CONV_FWD_INFO) == _forms.INFO and _forms.lib().snvc_forms_abi_version() == _forms._ABI == 4
     entries = _forms.enum_names(HEADER, "CFE")
     assert entries == {"FORWARD": _forms.ENTRY_FORWARD, "HEAD": _forms.ENTRY_HEAD, "SIDE_HEAD": _forms.ENTRY_SIDE_HEAD,
                        "STATS": _forms.ENTRY_STATS} and {k.upper(): v for k, v in CC.ENTRIES.items()} == entries

@@ -63,6 +63,10 @@ def _table():
     t += [("warped_expand_bwd_beyond_the_image", P, "test_warped_expand_backward_vs_oracle", dict(case="beyond_the_image"), 16, {}),
           ("warped_expand_bwd_odd_width", P, "test_warped_expand_backward_vs_oracle", dict(case="odd_width"), 4, {})]
     t += [("shift_structure", P, "test_shift_structure_flags", {}, 4, {})]
+    # the any-shift first layer with more than one row per workgroup (tests/test_gpu_first_layer_forms.py, run unchanged): RB 8 with a
+    # short last block, RB 2 with a single row left; p, y and planes must stay 16-byte aligned
+    t += [(f"forms_warped_expand_{n}", "test_gpu_first_layer_forms", "warped_expand_case", dict(name=n), 16, {})
+          for n in ("rb8_short_block", "rb2_one_row_left")]
     # ------------------------------------------------------------------------------------------------------------------ gather
     t += [("gather_edges", P, "test_voxel_gather_vs_torch_ref_edge_cases", {}, 4, {}),                       # (2, 5, 7 x 9, V 30, (28, 36))
           ("gather_lds", P, "test_voxel_gather_lds_path_bit_exact_with_edge_coordinates", dict(res=(64, 128)), 4, {}),   # fp32 and f16

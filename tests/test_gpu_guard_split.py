@@ -129,6 +129,21 @@ CASES += [(f"sheared_expand_split_q{q}_{'planes' if pl else 'no_planes'}", SPLIT
           for q, pl in ((1, True), (2, False))]
 CASES += [(f"warped_expand_split_{'planes' if pl else 'no_planes'}", SPLIT, "warped_expand_split_case", dict(with_planes=pl), 16, {})
           for pl in (True, False)]
+# one row per row / chunk form of the first-layer kernels (tests/test_gpu_first_layer_forms.py, each case run unchanged -- it asserts its form
+# through the query first): RB 8 with a short last block, RB 3 and RB 2 with idle threads in the last wave; both statistics workspaces
+# (the forward partials with fewer row blocks than rows, the fused backward's at 64 lanes and at one); 16 depth chunks with a short one
+# and one without planes, and the end plane alone in its chunk; the weight gradient's two column chunks; the adjoint's second trip
+FORMS = "test_gpu_first_layer_forms"
+CASES += [(f"forms_sheared_expand_{n}_{m}", FORMS, "sheared_expand_case", dict(name=n, mode=m), 16, dict(arena_bytes=512 << 20) if "w320" in n else {})
+          for n, m in (("rb8_short_block", "plain"), ("rb8_short_block", "amax"), ("rb3_w320", "affine"), ("rb2_w44", "plain"))]
+CASES += [(f"forms_sheared_stats_{n}", FORMS, "sheared_stats_case", dict(name=n), 16, dict(arena_bytes=512 << 20) if "w320" in n else {})
+          for n in ("rb8_short_block", "rb3_w320")]
+CASES += [(f"forms_sheared_backward_{n}", FORMS, "sheared_backward_case", dict(name=n), 16, {}) for n in ("w512_q2", "w8_q1")]
+CASES += [(f"forms_sheared_split_{n}_q{q}", FORMS, "sheared_expand_split_case", dict(name=n, q=q), 16, {})
+          for n, q in (("d131", 4), ("d131", 1), ("d241_end_plane_alone", 2))]
+CASES += [(f"forms_warped_split_{n}", FORMS, "warped_expand_split_case", dict(name=n), 16, {}) for n in ("d131", "d241_end_plane_alone")]
+CASES += [(f"forms_sheared_wgrad_{n}_c{c}", FORMS, "sheared_wgrad_case", dict(name=n, cin=c), 4, {}) for n, c in (("wu321", 5), ("wu388", 32))]
+CASES += [(f"forms_sheared_reduce_{n}", FORMS, "sheared_reduce_case", dict(name=n), 4, {}) for n in ("slots_308", "wg2_260")]
 
 RUNS = [(c, off) for c in CASES for off in (0, c[4]) if off is not None]          # the two placements back to back: one unguarded run
 

@@ -1425,7 +1425,9 @@ def test_commuted_first_conv_any_shift_vs_oracle_and_built_volume(case):
     from snvc_amd.models.stereo_volume import GlobalStack
     r = np.random.default_rng(161 + len(case))
     C, D = 32, 12
-    H, W = (12, 44) if case == "ragged_rows" else (8, 40)      # 12 rows over row blocks of 8 (the hourglass needs multiples of 4)
+    # 12 rows of 11 quads; like every shape here one row per workgroup (RB = 1: 12 * 32 * 2 workgroups stay below 1024) -- the larger row
+    # blocks are in tests/test_gpu_first_layer_forms.py (the hourglass needs multiples of 4)
+    H, W = (12, 44) if case == "ragged_rows" else (8, 40)
     L = r.standard_normal((2, C, H, W)).astype(np.float32)
     R = r.standard_normal((2, C, H, W)).astype(np.float32)
     s = r.uniform(0, 20, (2, D))
@@ -1728,7 +1730,9 @@ def test_first_layer_backward_runs_on_the_layers_of_its_own_forward(fused_bn):
 def test_sheared_fused_batchnorm_entry_points_vs_numpy(q, m0):
     """snvc_sheared_expand_stats against the statistics of the expanded tensor, and snvc_sheared_backward_reduce against the
     same sums formed in numpy from the expanded tensor and a random gy: per-channel fp64 sums, shear-line sums, last-column
-    slots and depth-class sums of both the masked gradient and raw.  Two samples, a ragged row block (H = 6), W = 24."""
+    slots and depth-class sums of both the masked gradient and raw.  Two samples, W = 24.  With C = 3 and H = 6 the forward kernels run
+    one row per workgroup (RB = 1; tests/test_gpu_first_layer_forms.py has the larger row blocks and their short last block); the
+    backward kernel's four-row blocks leave a last block of two rows."""
     from snvc_amd import ops
     from snvc_amd.models.submodule import sheared_geometry
     r = np.random.default_rng(211 + q + m0)

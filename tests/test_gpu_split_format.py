@@ -453,53 +453,65 @@ def test_every_split_form_with_more_than_one_channel_is_in_the_list():
 # ---------------------------------------------------------------------------------------------------- first-layer producers
 FL_C, FL_D, FL_H, FL_W = 12, 17, 2, 68       # D = 17: two depth chunks of 9 and 8 planes in both launchers (H * G * N = 8 workgroups);
 FL_AT = (1, 11, 1, 5)                         # W = 68: two waves, the second partial.  Flag voxel: sample, channel, row, column
-FL_ROWS = list(BOUNDARY)
+FL = (N, FL_C, FL_H, FL_W, FL_D)              # the shape of the tests of this file; tests/test_gpu_first_layer_forms.py passes the shapes of
+FL_ROWS = list(BOUNDARY)                      # tests/first_layer_cases.SPLIT (more depth chunks, a short one, one without planes)
+FL_WG = {1: 60, 2: 100}                       # G's row length at the shape FL
 
 
-def first_layer_affine(r):
-    scale = (r.choice([-1.0, 1.0], FL_C) * np.exp2(r.integers(-2, 3, FL_C))).astype(np.float32)
-    bias = (r.integers(-64, 65, FL_C) / 8.0).astype(np.float32)
+def flag_at(shape):
+    """The flag voxel (sample, channel, row, column) and the exact channel's sample: the last sample, channel 11, the last row."""
+    return (shape[0] - 1, 11, shape[2] - 1, 5)
+
+
+def first_layer_affine(r, c=FL_C):
+    scale = (r.choice([-1.0, 1.0], c) * np.exp2(r.integers(-2, 3, c))).astype(np.float32)
+    bias = (r.integers(-64, 65, c) / 8.0).astype(np.float32)
     scale[11], bias[11] = 1.0, 0.0
     return scale, bias
 
 
-def sheared_inputs(q, with_planes, row):
+def sheared_inputs(q, with_planes, row, shape=FL):
     """g / gcol / planes on a 2^-6 grid, scale +-2^k: raw + pe and fma(raw + pe, sc, bi) are exact.  WG and the offsets are such that
-    i = q w - d - m0 + off leaves [0, WG) on both sides and the last column's i2 leaves [0, WG2) on both sides.  Channel 11 of sample 1
-    has g = gcol = 0, scale 1, bias 0: what is stored there is its depth-class plane."""
-    r = np.random.default_rng(70 + q)
-    m0, off = 3, 5
-    wg, wg2 = (60, 12) if q == 1 else (100, 12)
-    off_col = -q * (FL_W - 1) + m0 + 13                    # i2 = 13 - d: 13, 12 (out), 11 .. 0, -1 .. -3 (out)
+    i = q w - d - m0 + off leaves [0, WG) on both sides and the last column's i2 leaves [0, WG2) on both sides.  Channel 11 of the last
+    sample has g = gcol = 0, scale 1, bias 0: what is stored there is its depth-class plane.  At D = 17 (the shape FL): off = 5, WG = 60
+    or 100, WG2 = 12, i2 = 13 - d; deeper shapes move off, WG and WG2 along with D, so that every plane still has columns inside G."""
+    n, c, h, w, d = shape
+    r = np.random.default_rng(70 + q + (0 if shape == FL else sum(shape)))
+    m0, off = 3, d - 12
+    wg = FL_WG[q] if shape == FL else q * (w - 2) + d - 23           # the largest i is q (W - 2) + D - 15: 8 columns past the row
+    wg2 = d - 5
+    off_col = -q * (w - 1) + m0 + d - 4                    # i2 = D - 4 - d: D - 4, D - 5 (out), D - 6 .. 0, -1 .. -3 (out)
     grid = lambda shape: (r.integers(-512, 513, shape) / 64.0).astype(np.float32)      # noqa: E731
-    g, gcol = grid((N, 3 * FL_C, FL_H, wg)), grid((N, 3 * FL_C, FL_H, wg2))
-    planes = grid((N, FL_C, 3, FL_H, FL_W))
+    g, gcol = grid((n, 3 * c, h, wg)), grid((n, 3 * c, h, wg2))
+    planes = grid((n, c, 3, h, w))
+    at = flag_at(shape)
     for cls in range(3):
-        g[1, cls * FL_C + 11] = 0
-        gcol[1, cls * FL_C + 11] = 0
+        g[at[0], cls * c + 11] = 0
+        gcol[at[0], cls * c + 11] = 0
     if BOUNDARY[row] is not None:
-        planes[FL_AT[0], FL_AT[1], 1, FL_AT[2], FL_AT[3]] = BOUNDARY[row]
+        planes[at[0], at[1], 1, at[2], at[3]] = BOUNDARY[row]
     elif not with_planes:
         planes = None
-    scale, bias = first_layer_affine(r)
+    scale, bias = first_layer_affine(r, c)
     return g, gcol, planes, scale, bias, m0, off, off_col
 
 
-def sheared_reference(g, gcol, planes, scale, bias, q, m0, off, off_col, relu):
+def sheared_reference(g, gcol, planes, scale, bias, q, m0, off, off_col, relu, shape=FL):
     """A restatement of the kernel's ``emit``: class 0 / 1 / 2 by plane, raw = G[cls][i] with i = q w - d - m0 + off (0 outside
     [0, WG)), the last column from G' at i2 = q (W - 1) - d - m0 + off_col; t = fma(raw + planes, scale, bias); clamp_pair."""
+    n, c, h, w, depth = shape
     wg, wg2 = g.shape[3], gcol.shape[3]
-    raw = np.zeros((N, FL_C, FL_D, FL_H, FL_W), np.float32)
+    raw = np.zeros((n, c, depth, h, w), np.float32)
     pe = np.zeros_like(raw)
-    for d in range(FL_D):
-        cls = 0 if d == 0 else (2 if d == FL_D - 1 else 1)
-        for w in range(FL_W - 1):
-            i = q * w - d - m0 + off
+    for d in range(depth):
+        cls = 0 if d == 0 else (2 if d == depth - 1 else 1)
+        for col in range(w - 1):
+            i = q * col - d - m0 + off
             if 0 <= i < wg:
-                raw[:, :, d, :, w] = g[:, cls * FL_C:(cls + 1) * FL_C, :, i]
-        i2 = q * (FL_W - 1) - d - m0 + off_col
+                raw[:, :, d, :, col] = g[:, cls * c:(cls + 1) * c, :, i]
+        i2 = q * (w - 1) - d - m0 + off_col
         if 0 <= i2 < wg2:
-            raw[:, :, d, :, FL_W - 1] = gcol[:, cls * FL_C:(cls + 1) * FL_C, :, i2]
+            raw[:, :, d, :, w - 1] = gcol[:, cls * c:(cls + 1) * c, :, i2]
         if planes is not None:
             pe[:, :, d] = planes[:, :, cls]
     s = (raw + pe).astype(np.float32)
@@ -507,27 +519,31 @@ def sheared_reference(g, gcol, planes, scale, bias, q, m0, off, off_col, relu):
     return SF.clamp_pair(f32(t64), relu), raw
 
 
-def flag_voxels(hi, lo):
+def flag_voxels(hi, lo, shape=FL):
     """hi + lo at the flag voxel of the interior planes."""
-    return (hi.astype(np.float64) + lo.astype(np.float64))[FL_AT[0], FL_AT[1], 1:FL_D - 1, FL_AT[2], FL_AT[3]]
+    at = flag_at(shape)
+    return (hi.astype(np.float64) + lo.astype(np.float64))[at[0], at[1], 1:shape[4] - 1, at[2], at[3]]
 
 
-def sheared_expand_split_case(q, with_planes, row="none", relu=True):
+def sheared_expand_split_case(q, with_planes, row="none", relu=True, shape=FL):
+    """The output starts as NaN in every half: a voxel that no depth chunk writes stays one and fails the comparison."""
     from snvc_amd import ops
-    g, gcol, planes, scale, bias, m0, off, off_col = sheared_inputs(q, with_planes, row)
-    (hi, lo, flag), raw = sheared_reference(g, gcol, planes, scale, bias, q, m0, off, off_col, relu)
-    outside = (raw[0, 0, :, 0, :FL_W - 1] == 0)
-    assert outside[:, 0].any() and outside[:, FL_W - 2].any() and not outside.all()           # i leaves [0, WG) on both sides
+    n, c, h, w, d = shape
+    g, gcol, planes, scale, bias, m0, off, off_col = sheared_inputs(q, with_planes, row, shape)
+    (hi, lo, flag), raw = sheared_reference(g, gcol, planes, scale, bias, q, m0, off, off_col, relu, shape)
+    outside = (raw[0, 0, :, 0, :w - 1] == 0)
+    assert outside[:, 0].any() and outside[:, w - 2].any() and not outside.all()           # i leaves [0, WG) on both sides
+    assert not outside.all(axis=1).any(), "every plane has columns inside G"
     stored, eflag = boundary_expectation(row, relu)
-    assert flag == eflag and (stored is None or (flag_voxels(hi, lo) == stored).all())
+    assert flag == eflag and (stored is None or (flag_voxels(hi, lo, shape) == stored).all())
     want = SF.pair_tensor(hi, lo)
     gd, gcd, pd, sd, bd = dev(g), dev(gcol), dev(planes) if planes is not None else None, dev(scale), dev(bias)
     for stream_out in (0, ops.EPI_STREAM_OUT):
-        out = torch.empty(want.shape, dtype=torch.float16, device=DEV)
+        out = torch.full(want.shape, float("nan"), dtype=torch.float16, device=DEV)
         word = torch.zeros(1, dtype=torch.int32, device=DEV)
         ops.sheared_expand_split(gd, gcd, pd, sd, bd, out, q, m0, off, off_col, (ops.EPI_RELU if relu else 0) | stream_out, word)
-        assert_bits(out, want, f"sheared_expand_split(q={q}, planes={with_planes}, row={row}, stream_out={bool(stream_out)})")
-        assert_ragged_zero(out, FL_C, "sheared_expand_split")
+        assert_bits(out, want, f"sheared_expand_split(q={q}, planes={with_planes}, row={row}, stream_out={bool(stream_out)}, shape={shape})")
+        assert_ragged_zero(out, c, "sheared_expand_split")
         assert int(word.item()) == int(flag), f"flag {int(word.item())}, the stored values say {int(flag)}"
 
 
@@ -550,29 +566,44 @@ WARPED_SHIFTS = np.array([
     [5.0, 5.5, 6.0, 6.5, 7.0, 7.5, 8.0, 8.5, 9.0, np.e, 3 ** 0.5, 0.25, 0.0, 0.0, 40.75, 41.0, 1e-3]], np.float32)
 
 
-def warped_inputs(with_planes, row):
-    r = np.random.default_rng(90)
-    p = r.standard_normal((N, 3 * FL_C, FL_H, FL_W)).astype(np.float32)
-    q = r.standard_normal((N, 3 * FL_C, FL_H, FL_W)).astype(np.float32)
-    e = r.standard_normal((N, 9 * FL_C, FL_H, 4)).astype(np.float32)
-    planes = r.standard_normal((N, FL_C, 3, FL_H, FL_W)).astype(np.float32)
-    for kd in range(3):                                    # channel 11 of sample 1: nothing but its planes
-        p[1, kd * FL_C + 11] = 0
-        q[1, kd * FL_C + 11] = 0
+def warped_shifts(shape):
+    """WARPED_SHIFTS at the shape FL; for a deeper shape the same kinds of rows (whole, half, irrational, zero, at and beyond W) from
+    tests/first_layer_cases.warped_shifts, with runs of equal and of half-pixel steps so that the register windows stand and move."""
+    if shape == FL:
+        return WARPED_SHIFTS
+    import first_layer_cases as FC
+    n, c, h, w, d = shape
+    s = FC.warped_shifts(n, d, w)
+    s[0, 4:12] = np.float32(3.0) + np.float32(0.5) * np.arange(8, dtype=np.float32)
+    s[-1, d // 2:d // 2 + 4] = np.float32(2.0 ** 0.5)
+    return s
+
+
+def warped_inputs(with_planes, row, shape=FL):
+    n, c, h, w, d = shape
+    r = np.random.default_rng(90 if shape == FL else 90 + sum(shape))
+    p = r.standard_normal((n, 3 * c, h, w)).astype(np.float32)
+    q = r.standard_normal((n, 3 * c, h, w)).astype(np.float32)
+    e = r.standard_normal((n, 9 * c, h, 4)).astype(np.float32)
+    planes = r.standard_normal((n, c, 3, h, w)).astype(np.float32)
+    at = flag_at(shape)
+    for kd in range(3):                                    # channel 11 of the last sample: nothing but its planes
+        p[at[0], kd * c + 11] = 0
+        q[at[0], kd * c + 11] = 0
         for kw in range(3):
-            e[1, (kd * 3 + kw) * FL_C + 11] = 0
-    planes[1, 11] = (r.integers(-512, 513, (3, FL_H, FL_W)) / 64.0).astype(np.float32)
+            e[at[0], (kd * 3 + kw) * c + 11] = 0
+    planes[at[0], 11] = (r.integers(-512, 513, (3, h, w)) / 64.0).astype(np.float32)
     if BOUNDARY[row] is not None:
-        planes[FL_AT[0], FL_AT[1], 1, FL_AT[2], FL_AT[3]] = BOUNDARY[row]
+        planes[at[0], at[1], 1, at[2], at[3]] = BOUNDARY[row]
     elif not with_planes:
         planes = None
-    scale = r.uniform(0.5, 2.0, FL_C).astype(np.float32) * r.choice([-1.0, 1.0], FL_C).astype(np.float32)
-    bias = r.standard_normal(FL_C).astype(np.float32)
+    scale = r.uniform(0.5, 2.0, c).astype(np.float32) * r.choice([-1.0, 1.0], c).astype(np.float32)
+    bias = r.standard_normal(c).astype(np.float32)
     scale[11], bias[11] = 1.0, 0.0
     return p, q, e, planes, scale, bias
 
 
-def warped_expand_split_case(with_planes, row="none", relu=True):
+def warped_expand_split_case(with_planes, row="none", relu=True, shape=FL):
     """ops.warped_expand_split against ops.warped_expand (float32, held to the C oracle by test_gpu_parity) on the same operands.
 
     Bound.  Both kernels evaluate, per voxel, t = fma(o, sc, bi) with o = pe + sum over kd of (f F_kd + g G_kd) [- tas at the last column],
@@ -586,40 +617,45 @@ def warped_expand_split_case(with_planes, row="none", relu=True):
 
         |pair_value - clamp(y32)| <= 2^-22 |y| + 2^-25 + 43 u M.
 
-    Channel 11 of sample 1 has p = q = e = 0, scale 1, bias 0 and planes on a grid: its stored pair is clamp_pair(planes), bit for
-    bit, which is where the flag rows sit."""
+    Channel 11 of the last sample has p = q = e = 0, scale 1, bias 0 and planes on a grid: its stored pair is clamp_pair(planes), bit for
+    bit, which is where the flag rows sit.  The output starts as NaN in every half, and EPI_STREAM_OUT on and off give equal bits."""
     from snvc_amd import ops
-    p, q, e, planes, scale, bias = warped_inputs(with_planes, row)
+    n, c, h, w, d = shape
+    p, q, e, planes, scale, bias = warped_inputs(with_planes, row, shape)
     flags = ops.EPI_RELU if relu else 0
-    pd_, qd, ed, pld, shd, sd, bd = dev(p), dev(q), dev(e), dev(planes) if planes is not None else None, dev(WARPED_SHIFTS), dev(scale), dev(bias)
-    y32 = torch.empty((N, FL_C, FL_D, FL_H, FL_W), dtype=torch.float32, device=DEV)
+    pd_, qd, ed, pld, shd, sd, bd = dev(p), dev(q), dev(e), dev(planes) if planes is not None else None, dev(warped_shifts(shape)), dev(scale), dev(bias)
+    y32 = torch.empty((n, c, d, h, w), dtype=torch.float32, device=DEV)
     ops.warped_expand(pd_, qd, ed, pld, shd, sd, bd, y32, flags)
-    out = torch.empty((N, 2, 2, FL_D, FL_H, FL_W, 8), dtype=torch.float16, device=DEV)
+    out = torch.full((n, 2, (c + 7) // 8, d, h, w, 8), float("nan"), dtype=torch.float16, device=DEV)
     word = torch.zeros(1, dtype=torch.int32, device=DEV)
     ops.warped_expand_split(pd_, qd, ed, pld, shd, sd, bd, out, flags, word)
+    streamed = torch.full(out.shape, float("nan"), dtype=torch.float16, device=DEV)
+    ops.warped_expand_split(pd_, qd, ed, pld, shd, sd, bd, streamed, flags | ops.EPI_STREAM_OUT, None)
     pair = host(out)
-    assert_ragged_zero(out, FL_C, "warped_expand_split")
-    hi, lo = SF.from_c8(pair[:, 0], FL_C), SF.from_c8(pair[:, 1], FL_C)
+    assert_bits(streamed, pair, "warped_expand_split, EPI_STREAM_OUT")
+    assert_ragged_zero(out, c, "warped_expand_split")
+    hi, lo = SF.from_c8(pair[:, 0], c), SF.from_c8(pair[:, 1], c)
     assert np.isfinite(hi).all() and np.isfinite(lo).all()
     SF.lo_within_half_ulp(hi, lo)
     y = np.clip(host(y32).astype(np.float64), -65504.0, 65504.0)
-    amax = lambda t, k: np.abs(t).reshape(N, k, FL_C, -1).max(axis=(1, 3))                   # noqa: E731  [N, C]
-    pl = amax(planes.transpose(0, 2, 1, 3, 4).reshape(N, 3 * FL_C, FL_H, FL_W), 3) if planes is not None else 0.0
+    amax = lambda t, k: np.abs(t).reshape(n, k, c, -1).max(axis=(1, 3))                   # noqa: E731  [N, C]
+    pl = amax(planes.transpose(0, 2, 1, 3, 4).reshape(n, 3 * c, h, w), 3) if planes is not None else 0.0
     M = np.abs(scale)[None] * (pl + 3 * (amax(p, 3) + amax(e, 9)) + 3 * amax(q, 3)) + np.abs(bias)[None]
-    bound = 2.0 ** -22 * np.abs(y) + 2.0 ** -25 + 43 * U * M.reshape(N, FL_C, 1, 1, 1)
+    bound = 2.0 ** -22 * np.abs(y) + 2.0 ** -25 + 43 * U * M.reshape(n, c, 1, 1, 1)
     err = np.abs(SF.pair_value(hi, lo, 1.0).astype(np.float64) - y)
     worst = np.unravel_index(np.argmax(err / bound), err.shape)
-    print(f"warped_expand_split(planes={with_planes}, row={row}): max |pair - y32| / bound = {float((err / bound).max()):.3f} at {worst}")
+    print(f"warped_expand_split(planes={with_planes}, row={row}, shape={shape}): max |pair - y32| / bound = {float((err / bound).max()):.3f} at {worst}")
     assert (err <= bound).all(), (worst, float(err[worst]), float(bound[worst]))
-    # channel 11 of sample 1: exact
-    cls = np.array([0] + [1] * (FL_D - 2) + [2])
-    src = planes[1, 11][cls] if planes is not None else np.zeros((FL_D, FL_H, FL_W), np.float32)
+    # channel 11 of the last sample: exact
+    at = flag_at(shape)
+    cls = np.array([0] + [1] * (d - 2) + [2])
+    src = planes[at[0], 11][cls] if planes is not None else np.zeros((d, h, w), np.float32)
     ehi, elo, _ = SF.clamp_pair(src, relu)
-    assert_bits(hi[1, 11], ehi, "warped_expand_split, the exact channel (hi)")
-    assert_bits(lo[1, 11], elo, "warped_expand_split, the exact channel (lo)")
+    assert_bits(hi[at[0], 11], ehi, "warped_expand_split, the exact channel (hi)")
+    assert_bits(lo[at[0], 11], elo, "warped_expand_split, the exact channel (lo)")
     stored, eflag = boundary_expectation(row, relu)
     if stored is not None:
-        assert (flag_voxels(hi, lo) == stored).all()
+        assert (flag_voxels(hi, lo, shape) == stored).all()
     assert int(word.item()) == int(eflag), f"flag {int(word.item())}, the stored values say {int(eflag)}"
 
 

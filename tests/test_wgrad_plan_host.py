@@ -152,4 +152,4 @@ def test_binding_matches_the_header():
     from snvc_amd import _forms
     params = re.search(r"SNVC_API[^;(]*\bsnvc_conv3d_wgrad_form\s*\(([^)]*)\)", HEADER).group(1)
     assert len(_forms.SIGNATURES["snvc_conv3d_wgrad_form"][1]) == params.count(",") + 1 == 4
-    assert len(_forms.WGRAD_INFO) == _forms.INFO and _forms.lib().snvc_forms_abi_version() == _forms._ABI == 3
+    assert len(_forms.WGRAD_INFO) == _forms.INFO and _forms.lib().snvc_forms_abi_version() == _forms._ABI == 4
