@@ -29,7 +29,9 @@
 
 #include "common.hpp"
 #include "elementwise_internal.hpp"
+#include "prep_bodies.hpp"
 #include "snvc_fused.h"
+#include "snvc_prep.h"
 #include "snvc_dedup.h"
 #include "snvc_alias.h"
 #include "snvc_hgdedup.h"
@@ -94,6 +96,11 @@ __host__ __device__ __forceinline__ I il_index(int mode, I oc, I C, I H, I pitch
     const I cls = mode ? oc % 3 : oc / C, co = mode ? oc / 3 : oc % C, groups = (C + 7) / 8;
     return ((((cls0 + cls) * groups + (co >> 3)) * H + h) * pitch + lp + x) * 8 + (co & 7);
 }
+
+// il_mode 2: the layer's rows are class-major (row r = cls * C + co, written interleaved as mode 0) while its plain result stays
+// class-minor: row r goes to plane co * 3 + cls.  One definition for the epilogue and the host query (snvc_prep_plain_plane).
+template <class I>
+__host__ __device__ __forceinline__ I il_plain_plane(I r, I C) { return (r % C) * 3 + r / C; }
 
 // conv2d_x3q_kernel<Cfg, 1>: the fp32 result is written a second time, channel-interleaved
 struct F16IlArgs : F16Args {
@@ -1345,15 +1352,16 @@ struct X2QCfg {
 };
 
 // IL 1: the result is written a second time in the channel-interleaved layout (il_index) the fused first layer reads.
-template <class Cfg, int IL = 0>
-__global__ void __launch_bounds__(256, 2)
-conv2d_x3q_kernel(const std::conditional_t<IL == 1, F16IlArgs, F16Args> a) {
+// The body of conv2d_x3q_kernel<Cfg, IL> for workgroup `bx` of the layer's (tile, channel block) jobs: the layer's own launch passes its
+// blockIdx.x, the pooled launch (conv2d_x3q_pool_kernel) the index inside the layer's block range.
+template <class Cfg, int IL>
+__device__ __forceinline__ void conv2d_x3q_body(const std::conditional_t<IL == 1, F16IlArgs, F16Args> a, const int bx) {
     constexpr int NB = Cfg::NB, IN_W = Cfg::IN_W, VOX = Cfg::VOX, NIT = Cfg::NIT, NQ = Cfg::NQ;
     constexpr int ITEMS = Cfg::ITEMS, PF = Cfg::PF;
     extern __shared__ __attribute__((aligned(16))) char lds[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, kb = lane >> 4, col = lane & 15;
     const int ntiles = a.tiles_h * a.tiles_w, cblocks = a.Cout >> 5;
-    const int job = xcd_remap16(blockIdx.x, ntiles * cblocks);
+    const int job = xcd_remap16(bx, ntiles * cblocks);
     const int t = job / cblocks, cb = job - t * cblocks;
     const int tw = t % a.tiles_w, th = t / a.tiles_w;
     const int64_t n = blockIdx.z;
@@ -1489,7 +1497,15 @@ conv2d_x3q_kernel(const std::conditional_t<IL == 1, F16IlArgs, F16Args> a) {
         sc[e] = (a.scale ? a.scale[c0 + e] : 1.0f) * xm;
         bi[e] = a.scale ? a.bias[c0 + e] : 0.0f;
     }
-    float *yn = a.y_f32 + n * a.yf_bs + (int64_t)c0 * out_hw;
+    // il_mode 2 (class-major rows of a layer whose plain result is class-minor): row c0 + e is channel co * 3 + cls of the plain result
+    int64_t yc0 = c0, ystep = out_hw;
+    if constexpr (IL == 1) {
+        if (a.il_mode == 2) {
+            yc0 = il_plain_plane(c0, a.il_C);
+            ystep = 3 * out_hw;
+        }
+    }
+    float *yn = a.y_f32 + n * a.yf_bs + yc0 * out_hw;
 #pragma unroll
     for (int nb = 0; nb < NB; ++nb) {
         const int phh = oh0 + wave * NB + nb;
@@ -1503,12 +1519,12 @@ conv2d_x3q_kernel(const std::conditional_t<IL == 1, F16IlArgs, F16Args> a) {
                 for (int e = 0; e < 8; ++e) {
                     float v = __builtin_fmaf(acc[nb][ph][e >> 2][e & 3], sc[e], bi[e]);
                     if (relu) v = __builtin_fmaxf(v, 0.0f);
-                    yp[e * out_hw] = v;
+                    yp[e * ystep] = v;
                     v8[e] = v;
                 }
                 if constexpr (IL == 1) {
                     float *il = a.y_il + n * a.il_bs;
-                    if (a.il_mode == 0) {      // class-major, C % 8 == 0: the lane's 8 channels are one channel group
+                    if (a.il_mode != 1) {      // class-major rows (0, 2), C % 8 == 0: the lane's 8 channels are one channel group
                         float *dst = il + il_index<int>(0, c0, a.il_C, a.Hout, a.il_pitch, a.il_lp, a.il_cls0, phh, pw);
                         *reinterpret_cast<f32x4q *>(dst) = f32x4q{v8[0], v8[1], v8[2], v8[3]};
                         *reinterpret_cast<f32x4q *>(dst + 4) = f32x4q{v8[4], v8[5], v8[6], v8[7]};
@@ -1520,6 +1536,41 @@ conv2d_x3q_kernel(const std::conditional_t<IL == 1, F16IlArgs, F16Args> a) {
             }
         }
     }
+}
+
+template <class Cfg, int IL = 0>
+__global__ void __launch_bounds__(256, 2)
+conv2d_x3q_kernel(const std::conditional_t<IL == 1, F16IlArgs, F16Args> a) {
+    conv2d_x3q_body<Cfg, IL>(a, blockIdx.x);
+}
+
+// The first layer's three depth-1 layers of a step in ONE launch (include/snvc_prep.h): blockIdx.x runs over G's jobs, then G''s, then the
+// left planes' (long jobs first); a block finds its layer from the two cumulative job counts -- wave-uniform, no table in memory -- and
+// runs that layer's own kernel body on that layer's own argument record with its LOCAL job index (xcd_remap16 sees the local index
+// and the layer's own job count, as in the layer's own launch).  Each of the three launches alone holds less than one resident
+// round of workgroups (512 slots on 256 CUs); together they fill it.  The records travel by value and are chosen by uniform
+// branches -- the 3x3 body on its own, the 3x7 body once for G and G' with the record picked between the two arguments (one inlined
+// body per range took 235 VGPRs, this takes the 3x7 kernel's 232) -- never by an index into an array of records, which may be moved
+// to scratch.
+struct X2QPoolArgs {
+    F16IlArgs g, gcol, left;
+    int end_g, end_gcol;       // jobs of G; of G and G': the first block of the next range
+};
+static_assert(sizeof(X2QPoolArgs) <= 4096, "the kernel argument segment");
+
+__host__ __device__ __forceinline__ int pool_range3(int b, int end0, int end1, int &local) {
+    if (b < end0) { local = b; return 0; }
+    if (b < end1) { local = b - end0; return 1; }
+    local = b - end1;
+    return 2;
+}
+
+__global__ void __launch_bounds__(256, 2)
+conv2d_x3q_pool_kernel(const X2QPoolArgs p) {
+    int local;
+    const int sub = pool_range3((int)blockIdx.x, p.end_g, p.end_gcol, local);
+    if (sub == 2) conv2d_x3q_body<X2QCfg<3, 3>, 1>(p.left, local);
+    else conv2d_x3q_body<X2QCfg<3, 7>, 1>(sub == 0 ? p.g : p.gcol, local);      // one of two records, not an index: both stay kernel arguments
 }
 
 // ------------------------------------------------------------------------- 16x16x32 form of the stride-2 3x3x3 split layer (r5)
@@ -2346,24 +2397,25 @@ deconv_tail_gather_alias_kernel(const float *__restrict__ t, const float *__rest
 // only known from the data -- in ONE launch (r5; the torch expression it replaces was ten small launches): every workgroup folds its
 // share into scratch[0] (float bits of a non-negative maximum order like unsigned integers), the last one to arrive (scratch[1]) turns
 // the maximum into the scale and leaves both words zero for the next call.  NaNs do not take part (fmaxf drops them), +-inf gives 1.
-__global__ void __launch_bounds__(256)
-split_scale_kernel(const float *__restrict__ x, int64_t n, unsigned *__restrict__ scratch, float *__restrict__ out) {
+// (the body: workgroup `bx` of `nblocks` that fold x into scratch[0 .. 1]; split_scale_pair_kernel runs it for two tensors in one grid)
+__device__ __forceinline__ void split_scale_body(const float *x, int64_t n, unsigned *scratch, float *out,
+                                                 const unsigned bx, const unsigned nblocks) {
     float m = 0.0f;
-    const int64_t stride = (int64_t)gridDim.x * 256 * 4;
+    const int64_t stride = (int64_t)nblocks * 256 * 4;
     const int64_t n4 = n & ~(int64_t)3;
     auto amax4 = [](const f32x4 v) {
         return __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v[0]), __builtin_fabsf(v[1])), __builtin_fmaxf(__builtin_fabsf(v[2]), __builtin_fabsf(v[3])));
     };
     // few workgroups, four independent 16-byte loads in flight per thread: the launch's time is the chain of same-address atomics
     // at its end (r5: 234 workgroups 9.1 us for 3.8 MB; <= 48 workgroups: see profiles/r5)
-    int64_t i = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
+    int64_t i = ((int64_t)bx * 256 + threadIdx.x) * 4;
     for (; i + 3 * stride < n4; i += 4 * stride) {
         const f32x4 v0 = *reinterpret_cast<const f32x4 *>(x + i), v1 = *reinterpret_cast<const f32x4 *>(x + i + stride);
         const f32x4 v2 = *reinterpret_cast<const f32x4 *>(x + i + 2 * stride), v3 = *reinterpret_cast<const f32x4 *>(x + i + 3 * stride);
         m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fmaxf(amax4(v0), amax4(v1)), __builtin_fmaxf(amax4(v2), amax4(v3))));
     }
     for (; i < n4; i += stride) m = __builtin_fmaxf(m, amax4(*reinterpret_cast<const f32x4 *>(x + i)));
-    if (blockIdx.x == 0 && threadIdx.x < (int)(n - n4)) m = __builtin_fmaxf(m, __builtin_fabsf(x[n4 + threadIdx.x]));
+    if (bx == 0 && threadIdx.x < (int)(n - n4)) m = __builtin_fmaxf(m, __builtin_fabsf(x[n4 + threadIdx.x]));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) m = __builtin_fmaxf(m, __shfl_xor(m, o, 64));
     __shared__ float part[4];
@@ -2373,13 +2425,57 @@ split_scale_kernel(const float *__restrict__ x, int64_t n, unsigned *__restrict_
         m = __builtin_fmaxf(__builtin_fmaxf(part[0], part[1]), __builtin_fmaxf(part[2], part[3]));
         atomicMax(scratch, __builtin_bit_cast(unsigned, m));
         __threadfence();
-        if (atomicAdd(scratch + 1, 1u) == gridDim.x - 1) {
+        if (atomicAdd(scratch + 1, 1u) == nblocks - 1) {
             const float amax = __builtin_bit_cast(float, atomicExch(scratch, 0u));
             atomicExch(scratch + 1, 0u);
             float e = floorf(log2f(16384.0f / amax));          // amax = 0 -> +inf, amax = inf -> -inf: "not finite" below
             e = (e == e && __builtin_fabsf(e) < 3.0e38f) ? __builtin_fminf(__builtin_fmaxf(e, -24.0f), 40.0f) : 0.0f;
             out[0] = exp2f(e);
         }
+    }
+}
+
+__global__ void __launch_bounds__(256)
+split_scale_kernel(const float *__restrict__ x, int64_t n, unsigned *__restrict__ scratch, float *__restrict__ out) {
+    split_scale_body(x, n, scratch, out, blockIdx.x, gridDim.x);
+}
+
+// Stage A of the pooled first-layer prep (include/snvc_prep.h): two tensors' scales in one grid.  Workgroups [0, nb0) fold x0 into
+// scratch words (0, 1) and leave out0, workgroups [nb0, gridDim.x) fold x1 into words (2, 3) and leave out1 -- each half is
+// split_scale_kernel with its own workgroup count, last-arrival rule and zeroing; the halves share nothing.
+__global__ void __launch_bounds__(256)
+split_scale_pair_kernel(const float *__restrict__ x0, int64_t n0, float *__restrict__ out0, const float *__restrict__ x1, int64_t n1,
+                        float *__restrict__ out1, unsigned *__restrict__ scratch4, const unsigned nb0) {
+    int local;
+    const bool second = pool_range3((int)blockIdx.x, (int)nb0, (int)gridDim.x, local) != 0;       // workgroup-uniform
+    split_scale_body(second ? x1 : x0, second ? n1 : n0, scratch4 + (second ? 2 : 0), second ? out1 : out0, (unsigned)local,
+                     second ? gridDim.x - nb0 : nb0);
+}
+
+// Stage B: the three split pairs the pooled layers read, in one 1D grid of three block ranges: Rq (sheared_upsample_split_kernel's
+// body with (WU, off)), Rq' (the same with (WU2, off2)) and the left feature's pair (ncdhw_f32_to_c8_split_kernel's body, its
+// (blocks per row, channel groups, samples) grid flattened, x fastest).
+struct SplitProducersArgs {
+    const float *right, *left, *mul_right, *mul_left;
+    _Float16 *rq_hi, *rq_lo, *rq2_hi, *rq2_lo, *l_hi, *l_lo;
+    int C, H, W, q, WU, off, WU2, off2;
+    int64_t total, total2, S;      // items of Rq, of Rq'; positions of one (sample, channel group) of the left feature
+    int end_rq, end_rq2;           // blocks of Rq; of Rq and Rq'
+    int row_blocks, groups;        // the left pair's grid: ceil(S / 256) blocks per (sample, channel group), C / 8 groups
+};
+
+__global__ void __launch_bounds__(256)
+split_producers_kernel(const SplitProducersArgs p) {
+    int local;
+    const int sub = pool_range3((int)blockIdx.x, p.end_rq, p.end_rq2, local);
+    if (sub == 0) {
+        prep::sheared_upsample_split_body(p.right, p.rq_hi, p.rq_lo, p.mul_right, p.C, p.H, p.W, p.q, p.WU, p.off, p.total, (unsigned)local);
+    } else if (sub == 1) {
+        prep::sheared_upsample_split_body(p.right, p.rq2_hi, p.rq2_lo, p.mul_right, p.C, p.H, p.W, p.q, p.WU2, p.off2, p.total2, (unsigned)local);
+    } else {
+        const int bx = local % p.row_blocks, r = local / p.row_blocks, g = r % p.groups, n = r / p.groups;
+        prep::ncdhw_f32_to_c8_split_body(p.left, p.l_hi, p.l_lo, p.C, p.S, (int64_t)p.C * p.S, 2 * (int64_t)p.C * p.S, 1.0f, p.mul_left,
+                                         (int64_t)bx * 256 + threadIdx.x, g, n);
     }
 }
 
@@ -3255,13 +3351,18 @@ int snvc_f16x3_conv3d_forward_stats(const snvc_conv3d_desc *d, const void *x_hi,
     return check_launch("snvc_f16x3_conv3d_forward_stats(finalize)");
 }
 
+// workgroups of a scale launch over n floats (split_scale_kernel: few workgroups, the launch's time is its chain of atomics)
+static int split_scale_blocks(int64_t n) {
+    const int64_t blocks = snvc::ceil_div<int64_t>(n > 0 ? n : 1, 256 * 4 * 16);
+    return (int)(blocks < 1 ? 1 : (blocks > 48 ? 48 : blocks));
+}
+
 int snvc_f16x3_split_scale(const float *x, int64_t n, void *scratch8, float *out_mul, void *stream) {
     using namespace snvc;
     if (n < 0) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_split_scale: negative size");
     if (!out_mul || !scratch8 || (n > 0 && !x)) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_split_scale: null pointer");
     if (reinterpret_cast<uintptr_t>(x) & 15) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_split_scale: x must be 16-byte aligned");
-    int blocks = (int)ceil_div<int64_t>(n > 0 ? n : 1, 256 * 4 * 16);
-    blocks = blocks < 1 ? 1 : (blocks > 48 ? 48 : blocks);
+    const int blocks = split_scale_blocks(n);
     split_scale_kernel<<<blocks, 256, 0, as_stream(stream)>>>(x, n, reinterpret_cast<unsigned *>(scratch8), out_mul);
     return check_launch("snvc_f16x3_split_scale");
 }
@@ -3295,21 +3396,32 @@ struct snvc_il_out {
     int mode;
 };
 
-static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
-                                float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
-                                const float *x_mul_dev, int flags, void *stream, const snvc_il_out *il) {
+static int fail_as(int code, const char *who, const char *what) {
+    char msg[256];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return snvc::fail(code, msg);
+}
+
+// Checks a depth-1 layer's call and fills its argument record (b; the il fields only with `il`) and its jobs per sample (0: N == 0,
+// nothing to launch) -- no launch: f16x3_conv2d_forward queues the layer's own launch behind it, snvc_prep_pooled_x3 pools three
+// records.  `who` / `who_il` name the entry point in the messages.
+static int f16x3_conv2d_setup(const char *who, const char *who_il, const void *x_hi, const void *x_lo, const void *packed_weight,
+                              const float *scale, const float *bias, float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh,
+                              int kw, float out_mul, const float *x_mul_dev, int flags, const snvc_il_out *il, snvc::F16IlArgs &b,
+                              int64_t &jobs) {
     using namespace snvc;
+    jobs = 0;
     if (N < 0 || H <= 0 || W <= 0 || snvc_f16x3_conv2d_packed_weight_bytes((int)Cout, (int)Cin, kh, kw) < 0)
-        return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv2d_forward: 3x7 or 3x3 kernels, Cin % 8 == 0, Cout % 32 == 0");
+        return fail_as(SNVC_ERR_UNSUPPORTED, who, "3x7 or 3x3 kernels, Cin % 8 == 0, Cout % 32 == 0");
     if (N == 0) return SNVC_OK;
-    if (!x_hi || !x_lo || !packed_weight || !y) return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv2d_forward: null pointer");
+    if (!x_hi || !x_lo || !packed_weight || !y) return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "null pointer");
     if ((scale == nullptr) != (bias == nullptr))
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv2d_forward: scale and bias must both be given or both be NULL");
-    if (flags & ~SNVC_EPI_RELU) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv2d_forward: only SNVC_EPI_RELU");
+        return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "scale and bias must both be given or both be NULL");
+    if (flags & ~SNVC_EPI_RELU) return fail_as(SNVC_ERR_UNSUPPORTED, who, "only SNVC_EPI_RELU");
     if ((reinterpret_cast<uintptr_t>(x_hi) | reinterpret_cast<uintptr_t>(x_lo) | reinterpret_cast<uintptr_t>(packed_weight)) & 15)
-        return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_f16x3_conv2d_forward: C8 tensors must be 16-byte aligned");
+        return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "C8 tensors must be 16-byte aligned");
     const int64_t hw = H * W;
-    if ((Cin / 8 + 2) * hw >= ((int64_t)1 << 31) || N > 65535) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv2d_forward: tensor too large");
+    if ((Cin / 8 + 2) * hw >= ((int64_t)1 << 31) || N > 65535) return fail_as(SNVC_ERR_UNSUPPORTED, who, "tensor too large");
     F16Args a{};
     a.x = reinterpret_cast<const _Float16 *>(x_hi); a.x_lo = reinterpret_cast<const _Float16 *>(x_lo);
     a.wp = reinterpret_cast<const _Float16 *>(packed_weight);
@@ -3320,19 +3432,35 @@ static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *
     a.pad_d = 0; a.pad_h = (kh - 1) / 2; a.pad_w = (kw - 1) / 2;
     a.tiles_d = 1; a.tiles_h = (int)ceil_div<int64_t>(H, 16); a.tiles_w = (int)ceil_div<int64_t>(W, 32);
     a.x_bs = 2 * Cin * hw; a.yf_bs = Cout * hw; a.N = (int)N;
-    const int64_t jobs = (int64_t)a.tiles_h * a.tiles_w * (Cout / 32);
-    if (jobs >= ((int64_t)1 << 30)) return fail(SNVC_ERR_UNSUPPORTED, "snvc_f16x3_conv2d_forward: too many tiles");
+    const int64_t nj = (int64_t)a.tiles_h * a.tiles_w * (Cout / 32);
+    if (nj >= ((int64_t)1 << 30)) return fail_as(SNVC_ERR_UNSUPPORTED, who, "too many tiles");
+    b = F16IlArgs{};
+    static_cast<F16Args &>(b) = a;
+    if (il) {
+        const int64_t C = Cout / 3, need = il->classes * ((C + 7) / 8) * H * il->pitch * 8;
+        if (!il->y_il || Cout % 3 || il->mode < 0 || il->mode > 2 || (il->mode != 1 && C % 8) || il->lp < 0 || il->lp + W > il->pitch || il->cls0 < 0 || il->cls0 + 3 > il->classes ||
+            need > il->bs || need >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(il->y_il) & 31) || il->bs % 8)
+            return fail_as(SNVC_ERR_INVALID_ARGUMENT, who_il, "the interleaved output does not hold the layer's result");
+        b.y_il = il->y_il; b.il_bs = il->bs; b.il_mode = il->mode; b.il_C = (int)C; b.il_pitch = (int)il->pitch; b.il_lp = (int)il->lp;
+        b.il_cls0 = (int)il->cls0;
+    }
+    jobs = nj;
+    return SNVC_OK;
+}
+
+static int f16x3_conv2d_forward(const void *x_hi, const void *x_lo, const void *packed_weight, const float *scale, const float *bias,
+                                float *y, int64_t N, int64_t Cin, int64_t Cout, int64_t H, int64_t W, int kh, int kw, float out_mul,
+                                const float *x_mul_dev, int flags, void *stream, const snvc_il_out *il) {
+    using namespace snvc;
+    F16IlArgs b;
+    int64_t jobs;
+    const int rc = f16x3_conv2d_setup("snvc_f16x3_conv2d_forward", "snvc_fused", x_hi, x_lo, packed_weight, scale, bias, y, N, Cin, Cout, H, W, kh, kw,
+                                      out_mul, x_mul_dev, flags, il, b, jobs);
+    if (rc || !jobs) return rc;
+    const F16Args &a = b;
     const dim3 grid((unsigned)jobs, 1, (unsigned)N);
     hipStream_t st = as_stream(stream);
     if (il) {
-        const int64_t C = Cout / 3, need = il->classes * ((C + 7) / 8) * H * il->pitch * 8;
-        if (!il->y_il || Cout % 3 || (il->mode == 0 && C % 8) || il->lp < 0 || il->lp + W > il->pitch || il->cls0 < 0 || il->cls0 + 3 > il->classes ||
-            need > il->bs || need >= ((int64_t)1 << 31) || (reinterpret_cast<uintptr_t>(il->y_il) & 31) || il->bs % 8)
-            return fail(SNVC_ERR_INVALID_ARGUMENT, "snvc_fused: the interleaved output does not hold the layer's result");
-        F16IlArgs b{};
-        static_cast<F16Args &>(b) = a;
-        b.y_il = il->y_il; b.il_bs = il->bs; b.il_mode = il->mode; b.il_C = (int)C; b.il_pitch = (int)il->pitch; b.il_lp = (int)il->lp;
-        b.il_cls0 = (int)il->cls0;
         if (kw == 7) {
             using C7 = X2QCfg<3, 7>;
             launch_lds<conv2d_x3q_kernel<C7, 1>>(grid, 256, C7::LDS_BYTES, st, b);
@@ -3421,6 +3549,128 @@ int snvc_fused_planes_from_f32(const float *x, int64_t N, int64_t C, int64_t H, 
     if (rc) return rc;
     const snvc_il_out il{p_il, 3 * (C / 8) * H * W * 8, W, 0, 0, 3, 1};
     return f16x3_conv2d_forward(a, a + C * H * W, packed, nullptr, nullptr, y, N, C, cout, H, W, 3, 3, out_mul, mul_dev, 0, stream, &il);
+}
+
+// ---- the pooled prep (include/snvc_prep.h)
+int snvc_prep_abi_version(void) { return 1; }
+
+int snvc_prep_pool_plan(int64_t N, int64_t C, int64_t H, int64_t W, int64_t WU, int64_t WU2, snvc_prep_pool_plan_t *plan) {
+    using namespace snvc;
+    const char *who = "snvc_prep_pool_plan";
+    if (!plan) return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "null pointer");
+    if (N <= 0 || C <= 0 || C % 8 || (3 * C) % 32) return fail_as(SNVC_ERR_UNSUPPORTED, who, "N > 0, C % 8 == 0, 3 * C % 32 == 0");
+    if (H <= 0 || W <= 0 || WU <= 0 || WU2 <= 0) return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "bad sizes");
+    const int64_t G = C / 8, widths[3] = {WU, WU2, W};
+    if (N > 65535 || G > 65535 || N * C * H * (WU > W ? (WU > WU2 ? WU : WU2) : (W > WU2 ? W : WU2)) >= ((int64_t)1 << 40))
+        return fail_as(SNVC_ERR_UNSUPPORTED, who, "tensor too large");
+    snvc_prep_pool_plan_t p{};
+    p.a_blocks[0] = p.a_blocks[1] = split_scale_blocks(N * C * H * W);
+    p.b_row_blocks = ceil_div<int64_t>(H * W, 256);
+    for (int i = 0; i < 3; ++i) {
+        p.b_items[i] = N * G * H * widths[i];
+        p.b_blocks[i] = i < 2 ? ceil_div<int64_t>(p.b_items[i], 256) : N * G * p.b_row_blocks;
+        p.c_jobs[i] = ceil_div<int64_t>(H, 16) * ceil_div<int64_t>(widths[i], 32) * (3 * C / 32);
+    }
+    p.c_samples = N;
+    if (p.b_blocks[0] + p.b_blocks[1] + p.b_blocks[2] >= ((int64_t)1 << 31) || p.c_jobs[0] + p.c_jobs[1] + p.c_jobs[2] >= ((int64_t)1 << 30))
+        return fail_as(SNVC_ERR_UNSUPPORTED, who, "too many blocks");
+    *plan = p;
+    return SNVC_OK;
+}
+
+int64_t snvc_prep_plain_plane(int64_t row, int64_t C) {
+    return C > 0 && row >= 0 && row < 3 * C ? snvc::il_plain_plane<int64_t>(row, C) : -1;
+}
+
+int snvc_prep_pool_locate(const snvc_prep_pool_plan_t *plan, int stage, int64_t block, int64_t *local) {
+    if (!plan || !local || stage < 0 || stage > 2 || block < 0) return -1;
+    const int64_t *cnt = stage == 0 ? plan->a_blocks : stage == 1 ? plan->b_blocks : plan->c_jobs;
+    const int64_t end0 = cnt[0], end1 = cnt[0] + cnt[1], end = end1 + (stage == 0 ? 0 : cnt[2]);
+    if (block >= end) return -1;
+    int l;
+    const int sub = snvc::pool_range3((int)block, (int)end0, (int)end1, l);
+    *local = l;
+    return sub;
+}
+
+int snvc_prep_pooled_x3(const float *right, int64_t N, int64_t C, int64_t H, int64_t W, int q, int64_t WU, int off, int64_t WU2, int off2,
+                        const void *packed_g, const void *packed_col, int64_t Cout3, float out_mul_g, float out_mul_col, void *rq_split,
+                        void *rq2_split, float *mul_right, float *g, float *gcol, float *gi, int64_t pitch, int64_t lp, const float *left,
+                        const void *packed_left, int64_t cout_left, float out_mul_left, float *planes, float *p_il, void *left_split,
+                        float *mul_left, void *scratch16, int left_rows, int pool, void *stream) {
+    using namespace snvc;
+    const char *who = "snvc_prep_pooled_x3";
+    // every check of snvc_fused_sheared_prep_x3 and snvc_fused_planes_from_f32 and of the calls they make, before the first launch
+    if (!right || !packed_g || !packed_col || !rq_split || !rq2_split || !mul_right || !g || !gcol || !left || !packed_left || !planes || !p_il ||
+        !left_split || !mul_left || !scratch16)
+        return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "null pointer");
+    if (!gi || Cout3 != 3 * C) return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "gi is NULL or Cout3 != 3 * C");
+    if (N <= 0 || C <= 0 || C % 8 || Cout3 % 32 || cout_left != 3 * C)
+        return fail_as(SNVC_ERR_UNSUPPORTED, who, "N > 0, C % 8 == 0, 3 * C % 32 == 0, cout_left == 3 * C");
+    if (H <= 0 || W <= 0 || (q != 1 && q != 2) || WU <= 0 || WU2 <= 0) return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "bad sizes (q in {1,2})");
+    if (pool & ~(SNVC_PREP_POOL_AB | SNVC_PREP_POOL_C)) return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "unknown pool bits");
+    if (left_rows != 0 && left_rows != 1) return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "left_rows is 0 (class-minor) or 1 (class-major)");
+    if ((reinterpret_cast<uintptr_t>(right) | reinterpret_cast<uintptr_t>(left)) & 15)
+        return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "right / left must be 16-byte aligned");
+    if ((reinterpret_cast<uintptr_t>(rq_split) | reinterpret_cast<uintptr_t>(rq2_split) | reinterpret_cast<uintptr_t>(left_split)) & 15)
+        return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "the split workspaces must be 16-byte aligned");
+    snvc_prep_pool_plan_t plan;
+    int rc = snvc_prep_pool_plan(N, C, H, W, WU, WU2, &plan);
+    if (rc) return fail_as(rc, who, "C % 8 == 0, 3 * C % 32 == 0, a shape whose three grids stay below their limits");
+    const int64_t G = C / 8, S = H * W, n = N * C * S;
+    _Float16 *a = reinterpret_cast<_Float16 *>(rq_split), *b = reinterpret_cast<_Float16 *>(rq2_split), *l = reinterpret_cast<_Float16 *>(left_split);
+    _Float16 *a_lo = a + G * H * WU * 8, *b_lo = b + G * H * WU2 * 8, *l_lo = l + C * S;
+    const int64_t gi_bs = 6 * G * H * pitch * 8;
+    const snvc_il_out il_g{gi, gi_bs, pitch, lp, 0, 6, 0}, il_col{gi, gi_bs, pitch, lp, 3, 6, 0}, il_left{p_il, 3 * G * S * 8, W, 0, 0, 3, left_rows ? 2 : 1};
+    X2QPoolArgs pa;
+    int64_t jobs[3];
+    rc = f16x3_conv2d_setup(who, who, a, a_lo, packed_g, nullptr, nullptr, g, N, C, Cout3, H, WU, 3, 7, out_mul_g, mul_right, 0, &il_g, pa.g, jobs[0]);
+    if (rc) return rc;
+    rc = f16x3_conv2d_setup(who, who, b, b_lo, packed_col, nullptr, nullptr, gcol, N, C, Cout3, H, WU2, 3, 7, out_mul_col, mul_right, 0, &il_col,
+                            pa.gcol, jobs[1]);
+    if (rc) return rc;
+    rc = f16x3_conv2d_setup(who, who, l, l_lo, packed_left, nullptr, nullptr, planes, N, C, cout_left, H, W, 3, 3, out_mul_left, mul_left, 0, &il_left,
+                            pa.left, jobs[2]);
+    if (rc) return rc;
+    if (jobs[0] != plan.c_jobs[0] || jobs[1] != plan.c_jobs[1] || jobs[2] != plan.c_jobs[2])
+        return fail_as(SNVC_ERR_INVALID_ARGUMENT, who, "internal: the plan and the layers disagree on their jobs");
+    hipStream_t st = as_stream(stream);
+    unsigned *scratch = reinterpret_cast<unsigned *>(scratch16);
+    if (pool & SNVC_PREP_POOL_AB) {
+        split_scale_pair_kernel<<<(unsigned)(plan.a_blocks[0] + plan.a_blocks[1]), 256, 0, st>>>(right, n, mul_right, left, n, mul_left, scratch,
+                                                                                                 (unsigned)plan.a_blocks[0]);
+        rc = check_launch("snvc_prep_pooled_x3(scales)");
+        if (rc) return rc;
+        SplitProducersArgs sp{};
+        sp.right = right; sp.left = left; sp.mul_right = mul_right; sp.mul_left = mul_left;
+        sp.rq_hi = a; sp.rq_lo = a_lo; sp.rq2_hi = b; sp.rq2_lo = b_lo; sp.l_hi = l; sp.l_lo = l_lo;
+        sp.C = (int)C; sp.H = (int)H; sp.W = (int)W; sp.q = q; sp.WU = (int)WU; sp.off = off; sp.WU2 = (int)WU2; sp.off2 = off2;
+        sp.total = plan.b_items[0]; sp.total2 = plan.b_items[1]; sp.S = S;
+        sp.end_rq = (int)plan.b_blocks[0]; sp.end_rq2 = (int)(plan.b_blocks[0] + plan.b_blocks[1]);
+        sp.row_blocks = (int)plan.b_row_blocks; sp.groups = (int)G;
+        split_producers_kernel<<<(unsigned)(plan.b_blocks[0] + plan.b_blocks[1] + plan.b_blocks[2]), 256, 0, st>>>(sp);
+        rc = check_launch("snvc_prep_pooled_x3(split pairs)");
+        if (rc) return rc;
+    } else {
+        rc = snvc_f16x3_split_scale(right, n, scratch, mul_right, stream);
+        if (!rc) rc = snvc_f16x3_split_scale(left, n, scratch + 2, mul_left, stream);
+        if (!rc) rc = snvc_sheared_upsample_split(right, a, a_lo, mul_right, N, C, H, W, q, WU, off, stream);
+        if (!rc) rc = snvc_sheared_upsample_split(right, b, b_lo, mul_right, N, C, H, W, q, WU2, off2, stream);
+        if (!rc) rc = snvc_f16x3_from_ncdhw(left, l, l_lo, N, C, S, 0, 0, 1.0f, mul_left, stream);
+        if (rc) return rc;
+    }
+    using C7 = X2QCfg<3, 7>;
+    using C3 = X2QCfg<3, 3>;
+    if (pool & SNVC_PREP_POOL_C) {
+        pa.end_g = (int)jobs[0]; pa.end_gcol = (int)(jobs[0] + jobs[1]);
+        constexpr int lds_bytes = C7::LDS_BYTES > C3::LDS_BYTES ? C7::LDS_BYTES : C3::LDS_BYTES;
+        launch_lds<conv2d_x3q_pool_kernel>(dim3((unsigned)(jobs[0] + jobs[1] + jobs[2]), 1, (unsigned)N), 256, lds_bytes, st, pa);
+    } else {
+        launch_lds<conv2d_x3q_kernel<C7, 1>>(dim3((unsigned)jobs[0], 1, (unsigned)N), 256, C7::LDS_BYTES, st, pa.g);
+        launch_lds<conv2d_x3q_kernel<C7, 1>>(dim3((unsigned)jobs[1], 1, (unsigned)N), 256, C7::LDS_BYTES, st, pa.gcol);
+        launch_lds<conv2d_x3q_kernel<C3, 1>>(dim3((unsigned)jobs[2], 1, (unsigned)N), 256, C3::LDS_BYTES, st, pa.left);
+    }
+    return check_launch("snvc_prep_pooled_x3(layers)");
 }
 
 // n_layers depth-1 split layers of ONE fp32 [N][C][H][W] input in one host call: its scale, its split pair (ws: N*2*C*H*W halves), then

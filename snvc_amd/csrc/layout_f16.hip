@@ -4,6 +4,7 @@
 // All of them are single-pass HBM streams: one 16-byte piece per thread on the C8 side, rows of one channel
 // coalesced across the wave on the NCDHW side.
 #include "common.hpp"
+#include "prep_bodies.hpp"
 
 namespace snvc {
 namespace {
@@ -40,21 +41,8 @@ c8_to_ncdhw_f32_kernel(const _Float16 *__restrict__ x, float *__restrict__ y, in
 __global__ void __launch_bounds__(256)
 ncdhw_f32_to_c8_split_kernel(const float *__restrict__ x, _Float16 *__restrict__ yh, _Float16 *__restrict__ yl, int C, int64_t S,
                              int64_t x_bs, int64_t y_bs, float mul, const float *__restrict__ mul_dev) {
-    const int64_t s = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (s >= S) return;
-    if (mul_dev) mul = *mul_dev;             // the scale chosen on the device (no host round trip): a power of two
-    const int g = blockIdx.y;
-    const int64_t n = blockIdx.z;
-    const float *xp = x + n * x_bs + (int64_t)g * 8 * S + s;
-    h8 o, ol;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) {
-        const float v = (g * 8 + e < C) ? xp[(int64_t)e * S] * mul : 0.0f;
-        o[e] = (_Float16)v;
-        ol[e] = (_Float16)(v - (float)o[e]);
-    }
-    *reinterpret_cast<h8 *>(yh + n * y_bs + ((int64_t)g * S + s) * 8) = o;
-    *reinterpret_cast<h8 *>(yl + n * y_bs + ((int64_t)g * S + s) * 8) = ol;
+    prep::ncdhw_f32_to_c8_split_body(x, yh, yl, C, S, x_bs, y_bs, mul, mul_dev, (int64_t)blockIdx.x * blockDim.x + threadIdx.x, blockIdx.y,
+                                     blockIdx.z);      // prep_bodies.hpp
 }
 
 // GroupNorm layers in split mode (r5): the layer's raw fp32 NCDHW result -> the split C8 pair of  act(scale * raw + shift [+ res]) [+ res],

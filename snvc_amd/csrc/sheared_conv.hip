@@ -24,6 +24,7 @@
 // the factored path's (tests/test_gpu_parity.py::test_sheared_first_conv_*), fp32 summation order aside.
 #include "common.hpp"
 #include "elementwise_internal.hpp"
+#include "prep_bodies.hpp"
 #include "snvc_forms.h"
 
 namespace snvc {
@@ -52,39 +53,10 @@ sheared_upsample_kernel(const float *__restrict__ r, float *__restrict__ out, in
 
 // sheared_upsample_kernel with the result written as a split C8 pair [N][2][C/8][H][WU][8] (r5: the 3x7 layer that reads it runs in
 // split mode): value * *mul_dev = hi + lo.  A thread = one position of one 8-channel group.
-typedef _Float16 h8u __attribute__((ext_vector_type(8)));
 __global__ void __launch_bounds__(256)
 sheared_upsample_split_kernel(const float *__restrict__ r, _Float16 *__restrict__ yh, _Float16 *__restrict__ yl, const float *__restrict__ mul_dev,
                               int C, int H, int W, int q, int WU, int off, int64_t total) {
-    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;          // ((n * G + g) * H + h) * WU + i
-    if (idx >= total) return;
-    const int i = (int)(idx % WU), u = i - off;
-    const int64_t t = idx / WU;
-    const int h = (int)(t % H);
-    const int64_t ng = t / H;
-    const int G = (C + 7) >> 3, g = (int)(ng % G);
-    const int64_t n = ng / G;
-    const float mul = mul_dev[0];
-    h8u hi, lo;
-    const bool in = u >= 0 && u <= q * (W - 1);
-    const int j = in ? u / q : 0;
-    const bool whole = u - j * q == 0;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        float v = 0.0f;
-        const int co = g * 8 + c;
-        if (in && co < C) {
-            const float *rr = r + ((n * C + co) * (int64_t)H + h) * W;
-            v = whole ? rr[j] : 0.5f * rr[j] + 0.5f * rr[j + 1];
-        }
-        v *= mul;
-        hi[c] = (_Float16)v;
-        lo[c] = (_Float16)(v - (float)hi[c]);
-    }
-    // [N][2 (hi | lo)][G][H][WU] pieces: a sample's two planes sit next to each other
-    const int64_t pos = ((n * 2 * G + g) * (int64_t)H + h) * WU + i;
-    *reinterpret_cast<h8u *>(yh + pos * 8) = hi;
-    *reinterpret_cast<h8u *>(yl + pos * 8) = lo;
+    prep::sheared_upsample_split_body(r, yh, yl, mul_dev, C, H, W, q, WU, off, total, blockIdx.x);      // prep_bodies.hpp
 }
 
 // One workgroup = RB rows of one (n, co) plane; thread = (row, quad of 4 columns) and walks d = 1 .. D-2.

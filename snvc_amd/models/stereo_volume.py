@@ -31,6 +31,7 @@ from .submodule import (_ROUTES, SCRATCH_ATTRS, WORKSPACE_ATTRS, X3_GROUP_NORM, 
 
 _PREP_EPOCH = itertools.count(1)      # stamps of the per-model first-layer prep buffers (see _factored_pair_steps)
 _X3_KEY = {ops.Conv3dLayer: "", ops.Conv2dLayerX3: "_x3"}      # plan-dict key suffix of a depth-1 layer kind (GlobalStack._layers)
+POOLED_PREP_CALLS = 0                 # pooled first-layer preps queued (GlobalStack.pooled_prep): counted here, _ROUTES' key set is pinned
 _ASK = object()                       # _conv2_tail: the caller has not resolved the split-mode state
 
 
@@ -189,6 +190,13 @@ class GlobalStack(SplitModePolicy, nn.Module):
     # 144 of its 2 880 jobs at cfg2), and hg conv2 -- the one reader of its result -- reads the representative's rows.  Same bits.  Taken
     # only where the shape has such tiles and both layers run on their 16x16x32 forms; anything else is the alias route's own calls.
     dedup_hourglass = True
+    # the fused first layer's 2D prep -- both features' scales, the three split pairs, G / G' / the left planes -- is queued as three pooled
+    # launches instead of eight (include/snvc_prep.h) wherever the sheared inputs are queued anyway (spacing known, or guessed for this
+    # shape).  Same bits.  False, or any other case: the two calls' own launches.
+    pooled_prep = True
+    # ... with the left planes' layer packed class-major (il_mode 2): the interleaved copy leaves as two 16-byte stores per lane
+    # instead of eight 4-byte ones.  Same bits.
+    planes_class_major = True
     split_prep = True    # split mode: the sheared first layer's depth-1 3 x 7 layers (G, G') on the half pipe too (False: fp32 MFMA, as r4)
     fused_tail = True    # split mode: conv5's epilogue contracts its result with the folded one-channel tail (False: r4's two launches)
 
@@ -674,6 +682,16 @@ class GlobalStack(SplitModePolicy, nn.Module):
         return GlobalStack._layers(plans, "left2d" + _X3_KEY[kind], kind, fold)[0]
 
     @staticmethod
+    def _left_planes_layer_cm(plans, w, c):
+        """``_left_planes_layer``'s split-mode layer with its rows in class-major order (row cls * C + co holds channel co * 3 + cls):
+        a lane's eight channels are then one channel group of the interleaved output.  Same fold, its own key, same validity rule."""
+        def fold():
+            wl = w.detach()[:, :c].double()
+            k = torch.stack([wl[:, :, 1:].sum(2), wl.sum(2), wl[:, :, :2].sum(2)], dim=1).reshape(-1, c, 3, 3)
+            return [k[torch.tensor(ops.class_major_rows(w.shape[0]), device=k.device)]]
+        return GlobalStack._layers(plans, "left2d_cm_x3", ops.Conv2dLayerX3, fold)[0]
+
+    @staticmethod
     def _commuted_weights(wr):
         """(P, Q, E) weights of the warp-after-convolution first layer as [*, C, 3, 3] depth-1 kernels (see _commuted_layers)."""
         w = wr.detach()                                                   # [Cout, C, kd, kh, kw]
@@ -709,10 +727,11 @@ class GlobalStack(SplitModePolicy, nn.Module):
 
     # (the two chains below on two side streams, joined by events before the expand pass, were built and measured in r5 with interleaved
     # legs: 2.185 ms/step against 2.130 on one stream -- the cross-stream event waits cost more than the chains' overlap buys.  Removed.)
-    def _sheared_inputs(self, prep, right, q, m0, d, w, up=None):
+    def _sheared_inputs(self, prep, right, q, m0, d, w, up=None, pool_left=None):
         """(G, G', off, off_col, il) of the sheared layer with q phases on D = ``d`` planes and rows of ``w``: the depth-1 3 x 7 layers on
         ``right`` upsampled by ``up`` (q unless the caller's feature already is the upsampled image).  ``il`` (fused first layer only):
-        (G | G' channel-interleaved, pitch, lp)."""
+        (G | G' channel-interleaved, pitch, lp).  ``pool_left`` (fused first layer, q = 1 | 2): the left feature whose planes the caller
+        has NOT queued -- one pooled call (ops.prep_pooled_x3) then fills ``prep.planes`` and ``prep.p_il`` as ``_left_planes`` would."""
         off, wu, off_col, wu_col = sheared_geometry(q, m0, d, w)
         if prep.split_prep:
             # r5: G and G' (depth-1 3 x 7 layers, 7.8 + 2.5 GFLOP: 84 + 31 us on the fp32 matrix pipe) in split mode like the layers behind
@@ -723,8 +742,18 @@ class GlobalStack(SplitModePolicy, nn.Module):
             il = None
             if prep.fuse and q in (1, 2):      # G | G' also channel-interleaved, zero around the rows: what conv2's launch reads
                 pitch, lp = ops.fused_il_geometry(q, m0, d, w, wu, off, wu_col, off_col)
-                g, gcol, gi = ops.sheared_prep_x3_il(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep.prep_ws.setdefault("sheared_il", {}),
-                                                     pitch, lp)
+                if pool_left is not None:
+                    global POOLED_PREP_CALLS
+                    cm = bool(self.planes_class_major)
+                    lx = (self._left_planes_layer_cm(prep.plans, prep.weight, prep.c) if cm else
+                          self._left_planes_layer(prep.plans, prep.weight, prep.c, ops.Conv2dLayerX3))
+                    planes, prep.p_il, g, gcol, gi = ops.prep_pooled_x3(pool_left, right, q, wu, off, wu_col, off_col, lx_g, lx_col, lx,
+                                                                        prep.prep_ws.setdefault("pooled", {}), pitch, lp, int(cm))
+                    prep.planes = planes.view(right.size(0), prep.c, 3, right.size(2), right.size(3))
+                    POOLED_PREP_CALLS += 1
+                else:
+                    g, gcol, gi = ops.sheared_prep_x3_il(right, q, wu, off, wu_col, off_col, lx_g, lx_col,
+                                                         prep.prep_ws.setdefault("sheared_il", {}), pitch, lp)
                 il = (gi, pitch, lp)
             else:
                 g, gcol = ops.sheared_prep_x3(right, q, wu, off, wu_col, off_col, lx_g, lx_col, prep.prep_ws.setdefault("sheared", {}))
@@ -927,14 +956,24 @@ class GlobalStack(SplitModePolicy, nn.Module):
         # (a process-wide counter: invalidate_plans(model) drops the attribute, and a fresh count must not meet an old step's number)
         epoch = self.__dict__["_snvc_prep_epoch"] = next(_PREP_EPOCH)
         prep = _Prep(plans, c, conv.weight, st, scale, bias, split_prep, fuse, self.__dict__.setdefault("_snvc_prep_ws", {}))
-        self._left_planes(prep, left)
         can_commute = commuted and shift.dtype == torch.float32 and w <= 2048
         structure, guess, ready, ready_general = (spacing if known else None), None, None, None
         if ticket is not None:
             guess = plans.get("spacing_seen")    # (q, m0, D, W) of the previous call, or ("general", D, W): a guess, checked below
+        guessed = ticket is not None and sheared and guess is not None and guess[0] != "general" and guess[2:] == (d, w)   # a guess for this shape
+        # pooled_prep: where the fused first layer's sheared inputs are queued anyway -- the spacing is known, or guessed for this shape --
+        # the left planes are not queued on their own: the first _sheared_inputs below fills them too, three launches for the eight.
+        # In every other case the planes go first, as they always did.
+        pool_for = structure if known else (guess[:2] if guessed else None)
+        pool_left = left if (fuse and self.pooled_prep and pool_for is not None and pool_for[0] in (1, 2) and left.shape == right.shape
+                             and self._sheared_fits(pool_for[0], pool_for[1], d, w, False)) else None
+        if pool_left is None:
+            self._left_planes(prep, left)
+        if ticket is not None:
             _mark(timing, "volume", 0)
-            if sheared and guess is not None and guess[0] != "general" and guess[2:] == (d, w):
-                ready = self._sheared_inputs(prep, right, guess[0], guess[1], d, w)
+            if guessed:
+                ready = self._sheared_inputs(prep, right, guess[0], guess[1], d, w, pool_left=pool_left)
+                pool_left = None                 # the planes are queued: a wrong guess re-runs the sheared inputs alone
             elif can_commute and (not sheared or (guess is not None and guess[0] == "general" and guess[1:] == (d, w))):
                 ready_general = self._commuted_inputs(prep, right)
             nonneg, structure = ops.shift_spacing_result(ticket, d)
@@ -957,11 +996,15 @@ class GlobalStack(SplitModePolicy, nn.Module):
             prep.st = self._x3_select(left.device, arithmetic)
         if structure is not None and not self._sheared_fits(structure[0], structure[1], d, w, False):
             structure = None                     # rows the sheared kernels do not cover: the paths below
+        if pool_left is not None and structure is None:
+            self._left_planes(prep, left)        # nothing below queues the sheared inputs after all: the planes on their own
+            pool_left = None
         cost = None
         if structure is not None:
             if ready is None or tuple(guess[:2]) != tuple(structure):
                 _mark(timing, "volume", 0)
-                ready = self._sheared_inputs(prep, right, structure[0], structure[1], d, w)    # first call, or the spacing changed: the guess is dropped
+                # first call, or the spacing changed: the guess is dropped (pool_left: the spacing was known, nothing is queued yet)
+                ready = self._sheared_inputs(prep, right, structure[0], structure[1], d, w, pool_left=pool_left)
             cost = self._sheared_pair(prep, ready, structure, (left.size(0), c, d) + tuple(left.shape[2:]), timing, arithmetic)
         if cost is None and can_commute:
             if ready_general is None:

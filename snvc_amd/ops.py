@@ -17,7 +17,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _alias, _dedup, _derived, _fused, _hgdedup, _lib
+from . import _alias, _dedup, _derived, _fused, _hgdedup, _lib, _prep
 from ._lib import (EPI_ADD_POST, EPI_ADD_PRE, EPI_RELU, EPI_SIGMOID, EPI_STREAM_OUT, F32, F64, Conv3dDesc,
                    Unsupported, check)
 
@@ -1780,6 +1780,77 @@ def planes_x3_il(x, layer: "Conv2dLayerX3", ws: dict):
                                                       _ptr(ws["y"][0]), _ptr(ws["p_il"]), _ptr(ws["split"]), _ptr(scratch), _ptr(ws["mul"]),
                                                       _stream(x)), "snvc_fused_planes_from_f32")
     return ws["y"][0], ws["p_il"]
+
+
+# ---- the pooled first-layer prep (include/snvc_prep.h): the eight launches of planes_x3_il + sheared_prep_x3_il as three
+
+PREP_POOL_STAGES = [_prep.POOL_AB | _prep.POOL_C]      # tests / A-B timing: which stages prep_pooled_x3 pools (0: the single launches)
+
+
+def _pool_scratch(device) -> torch.Tensor:
+    """The pooled scale launch's four words (maximum and arrival counter of the right feature, of the left), one per (device, stream)
+    like ``_scale_scratch``'s two -- kept in the same table under a key of its own, so whatever drops that table drops these."""
+    key = (device, torch.cuda.current_stream(device).cuda_stream, "pooled")
+    scratch = _SCALE_SCRATCH.get(key)
+    if scratch is None:
+        with _SCALE_SCRATCH_LOCK:
+            scratch = _SCALE_SCRATCH.get(key)
+            if scratch is None:
+                scratch = _SCALE_SCRATCH[key] = torch.zeros(4, dtype=torch.int32, device=device)
+    return scratch
+
+
+def prep_pool_plan(n: int, c: int, h: int, w: int, wu: int, wu_col: int) -> "_prep.PoolPlan":
+    """The three grids of ``prep_pooled_x3`` for a shape (snvc_prep_pool_plan: what the launcher uses).  Host only."""
+    plan = _prep.PoolPlan()
+    if _prep.lib().snvc_prep_pool_plan(int(n), int(c), int(h), int(w), int(wu), int(wu_col), ctypes.byref(plan)):
+        raise ValueError(_lib.lib().snvc_last_error_string().decode())
+    return plan
+
+
+def class_major_rows(c: int):
+    """For a depth-class layer of 3 * c class-minor output channels (channel co * 3 + cls): the channel that row r holds once the rows
+    are put in class-major order (r = cls * c + co) -- snvc_prep_plain_plane, the function the epilogue uses.  Host only."""
+    fn = _prep.lib().snvc_prep_plain_plane
+    return [int(fn(r, int(c))) for r in range(3 * int(c))]
+
+
+def prep_pooled_x3(left, right, q: int, wu: int, off: int, wu_col: int, off_col: int, lay_g: "Conv2dLayerX3", lay_col: "Conv2dLayerX3",
+                   lay_left: "Conv2dLayerX3", ws: dict, pitch: int, lp: int, left_rows: int = 0):
+    """``planes_x3_il(left, lay_left, .)`` and ``sheared_prep_x3_il(right, ..., pitch, lp)`` in one host call of three launches
+    (snvc_prep_pooled_x3: both scales; the three split pairs; the three layers) -- the same bits in every result.  ``ws``: a dict the
+    caller keeps (workspaces and results allocated once per shape and reused; ``gi`` is zeroed once per shape).  ``left_rows=1``:
+    ``lay_left`` was packed with its rows in class-major order (``class_major_rows``); ``planes`` and ``p_il`` hold the same bytes.
+    Returns (planes, p_il, g, gcol, gi)."""
+    _gpu(left, "left")
+    _gpu(right, "right")
+    if left.dtype != torch.float32 or right.dtype != torch.float32 or left.dim() != 4 or left.shape != right.shape or left.device != right.device:
+        raise RuntimeError("prep_pooled_x3 needs two float32 [N,C,H,W] tensors of one shape on one device")
+    left, right = left.contiguous(), right.contiguous()
+    n, c, h, w = right.shape
+    key = (n, c, h, w, wu, wu_col, pitch, lp, id(lay_left), right.device)
+    if ws.get("key") != key:
+        dev = right.device
+        ws.clear()
+        ws.update(key=key, rq=torch.empty(n * 2 * c * h * wu, dtype=torch.float16, device=dev),
+                  rq2=torch.empty(n * 2 * c * h * wu_col, dtype=torch.float16, device=dev),
+                  split=torch.empty(n * 2 * c * h * w, dtype=torch.float16, device=dev),
+                  mul=torch.empty(1, dtype=torch.float32, device=dev), mul_left=torch.empty(1, dtype=torch.float32, device=dev),
+                  g=torch.empty((n, lay_g.cout, h, wu), dtype=torch.float32, device=dev),
+                  gcol=torch.empty((n, lay_col.cout, h, wu_col), dtype=torch.float32, device=dev),
+                  gi=torch.zeros((n, 6, c // 8, h, pitch, 8), dtype=torch.float32, device=dev),
+                  planes=torch.empty((n, lay_left.cout, h, w), dtype=torch.float32, device=dev),
+                  p_il=torch.empty((n, 3, c // 8, h, w, 8), dtype=torch.float32, device=dev), layers=[lay_left])
+    scratch = _pool_scratch(right.device)
+    with torch.cuda.device(right.device):
+        check(_prep.lib().snvc_prep_pooled_x3(_ptr(right), n, c, h, w, int(q), int(wu), int(off), int(wu_col), int(off_col), _ptr(lay_g.packed),
+                                              _ptr(lay_col.packed), lay_g.cout, float(2.0 ** -lay_g.w_exp), float(2.0 ** -lay_col.w_exp),
+                                              _ptr(ws["rq"]), _ptr(ws["rq2"]), _ptr(ws["mul"]), _ptr(ws["g"]), _ptr(ws["gcol"]), _ptr(ws["gi"]),
+                                              int(pitch), int(lp), _ptr(left), _ptr(lay_left.packed), lay_left.cout,
+                                              float(2.0 ** -lay_left.w_exp), _ptr(ws["planes"]), _ptr(ws["p_il"]), _ptr(ws["split"]),
+                                              _ptr(ws["mul_left"]), _ptr(scratch), int(left_rows), int(PREP_POOL_STAGES[0]), _stream(right)),
+              "snvc_prep_pooled_x3")
+    return ws["planes"], ws["p_il"], ws["g"], ws["gcol"], ws["gi"]
 
 
 def from_split(x: torch.Tensor, exp: int = 0, channels: Optional[int] = None) -> torch.Tensor:
