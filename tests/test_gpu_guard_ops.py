@@ -48,6 +48,7 @@ def _table():
     import depth_cases as DC
     import fcmodel_cases as FC
     import geometry_cases as GEO
+    import neck2d_backward_cases as NB
     import roi_crop_cases as RC
     import test_gpu_epilogue as E
     import test_gpu_hrnet as HR
@@ -120,6 +121,10 @@ def _table():
           ("dsgn_dilated", "test_gpu_dsgn", "test_dilated_layer_vs_torch", dict(cin=16, cout=16, hw=(37, 53)), 4, {})]
     t += [(f"conv2d_{cin}_{cout}_k{k}s{s}", "test_gpu_neck2d", "test_fused_conv2d_vs_torch", dict(k=k, stride=s, cin=cin, cout=cout, hw=hw), 4, {})
           for cin, cout, hw in ((9, 32, (6, 4)), (64, 27, (13, 34))) for k in (1, 3) for s in (1, 2)]
+    # one row per data-gradient kind of the 2D autograd function (tests/test_gpu_neck2d_backward.py, run unchanged): the [::2, ::2] scatter
+    # at odd extents, the cropped transposed layer, the stride-2 layer behind the transposed one, the flattened 1x1 layer
+    t += [(f"neck2d_backward_{n}", "test_gpu_neck2d_backward", "test_row", dict(row=NB.BY_NAME[n]), 4, {})
+          for n in ("k1s2_odd_bn_relu", "k3s2_odd_bn_relu", "deconv_bn_relu_res", "whole_bias_sigmoid")]
     return t
 
 
