@@ -8,12 +8,9 @@ loads nothing.
 import ctypes
 
 from . import _lib
+from ._lib import c_i64, c_int, c_p
 
 _ABI = 1   # snvc_decode_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
 
 GRID, COORDS_F32, COORDS_F64 = 0, 1, 2   # SNVC_DECODE_GRID, SNVC_DECODE_COORDS_F32, SNVC_DECODE_COORDS_F64
 
@@ -33,19 +30,4 @@ SIGNATURES = {
     "snvc_decode_boxes": (c_int, [_cfg_p, c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_decode_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so decode ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_decode_abi_version", _ABI, "decode")

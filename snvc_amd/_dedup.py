@@ -8,11 +8,9 @@ nothing.
 import ctypes
 
 from . import _fused, _lib
+from ._lib import c_i64, c_int
 
 _ABI = 1   # snvc_dedup_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_int = ctypes.c_int
 
 # name -> (restype, argtypes); kept next to the header so the symbol test can walk it
 SIGNATURES = {
@@ -22,19 +20,4 @@ SIGNATURES = {
                                              ctypes.POINTER(c_i64), c_int]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_dedup_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so wedge deduplication ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_dedup_abi_version", _ABI, "wedge deduplication")

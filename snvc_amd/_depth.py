@@ -5,16 +5,10 @@ Kept apart from ``_lib.SIGNATURES`` (the table of ``include/snvc_hip.h``): this 
 ``snvc_depth_abi_version()``.  The symbols are resolved on ``_lib.lib()``'s handle at first use, so importing this module
 loads nothing.
 """
-import ctypes
-
 from . import _lib
+from ._lib import c_f, c_i64, c_int, c_p
 
 _ABI = 1   # snvc_depth_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_f = ctypes.c_float
 
 MAX_PLANES = 2048     # SNVC_DEPTH_MAX_PLANES
 POINTS_BLOCK = 256    # SNVC_DEPTH_POINTS_BLOCK
@@ -29,19 +23,4 @@ SIGNATURES = {
     "snvc_depth_to_points_compact": (c_int, [c_p, c_p, c_int, c_p] + [c_f] * 7 + [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_depth_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so depth read-out ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_depth_abi_version", _ABI, "depth read-out")

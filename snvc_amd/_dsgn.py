@@ -5,17 +5,12 @@ Kept apart from ``_lib.SIGNATURES`` (the table of ``include/snvc_hip.h``): this 
 ``snvc_dsgn_abi_version()``.  The symbols are resolved on ``_lib.lib()``'s handle at first use, so importing this module
 loads nothing.
 """
-import ctypes
-
 import torch
 
 from . import _lib
+from ._lib import c_i64, c_int, c_p
 
 _ABI = 1   # snvc_dsgn_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
 
 WINDOWS = (8, 16, 32, 64)       # out8, out16, out32, out64 of snvc_dsgn_spp_pool
 MAX_CELLS = 8192                # SNVC_DSGN_MAX_CELLS
@@ -27,22 +22,7 @@ SIGNATURES = {
     "snvc_dsgn_spp_upsample": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_dsgn_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so dsgn ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_dsgn_abi_version", _ABI, "dsgn")
 
 
 def _check_gpu(t, name, dense=True):

@@ -5,16 +5,10 @@ Kept apart from ``_lib.SIGNATURES`` (the table of ``include/snvc_hip.h``): this 
 ``snvc_fc_abi_version()``.  The symbols are resolved on ``_lib.lib()``'s handle at first use, so importing this module
 loads nothing.
 """
-import ctypes
-
 from . import _lib
+from ._lib import c_f, c_i64, c_int, c_p
 
 _ABI = 1   # snvc_fc_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_f = ctypes.c_float
 
 MAX_WIDTH = 1024   # SNVC_FC_MAX_WIDTH
 
@@ -28,19 +22,4 @@ SIGNATURES = {
     "snvc_fc_train_layer_backward_input": (c_int, [c_p] * 4 + [c_i64, c_i64, c_i64, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_fc_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so FC head ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_fc_abi_version", _ABI, "FC head")

@@ -10,13 +10,9 @@ import re
 from typing import Tuple
 
 from . import _lib
+from ._lib import c_f, c_i64, c_int, c_p
 
 _ABI = 4   # snvc_forms_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_f = ctypes.c_float
 
 INFO = 8                                   # SNVC_FORMS_INFO
 ALIGNED_IN, ALIGNED_OUT, ALIGNED_ALL = 1, 2, 3
@@ -51,22 +47,7 @@ FIRST_LAYER_INFO = ("RB", "blocks", "chunks", "per_chunk", "grid_x", "grid_yz", 
 (FLE_SHEARED_EXPAND, FLE_SHEARED_EXPAND_AMAX, FLE_SHEARED_EXPAND_STATS, FLE_SHEARED_EXPAND_SPLIT, FLE_SHEARED_BACKWARD_REDUCE,
  FLE_SHEARED_REDUCE, FLE_WARPED_EXPAND, FLE_WARPED_EXPAND_SPLIT, FLE_WARPED_EXPAND_BACKWARD) = range(9)
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_forms_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so form-query ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_forms_abi_version", _ABI, "form-query")
 
 
 def enum_names(header_text: str, prefix: str) -> dict:

@@ -8,13 +8,9 @@ loads nothing.
 import ctypes
 
 from . import _lib
+from ._lib import c_f, c_i64, c_int, c_p
 
 _ABI = 1   # snvc_fused_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_f = ctypes.c_float
 
 # name -> (restype, argtypes); kept next to the header so the symbol test can walk it
 SIGNATURES = {
@@ -27,19 +23,4 @@ SIGNATURES = {
                                         + [c_int] * 5 + [c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_fused_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so fused first layer ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_fused_abi_version", _ABI, "fused first layer")

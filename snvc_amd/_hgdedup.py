@@ -8,12 +8,10 @@ importing this module loads nothing.
 import ctypes
 
 from . import _alias, _lib
+from ._lib import c_i64, c_int, c_p
 
 _ABI = 1   # snvc_hgdedup_abi_version() this binding was written against
 
-c_i64 = ctypes.c_int64
-c_int = ctypes.c_int
-c_p = ctypes.c_void_p
 _desc_p = ctypes.POINTER(_alias.WedgeDesc)
 _forward = (c_int, [ctypes.POINTER(_lib.Conv3dDesc), c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, _desc_p, c_p])
 
@@ -29,19 +27,4 @@ SIGNATURES = {
     "snvc_hgdedup_reader_f16x3_conv3d_forward": _forward,
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_hgdedup_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so hourglass duplicate ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_hgdedup_abi_version", _ABI, "hourglass duplicate")

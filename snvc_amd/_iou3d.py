@@ -4,16 +4,10 @@ Kept apart from ``_lib.SIGNATURES`` (the table of ``include/snvc_hip.h``): this 
 ``snvc_iou3d_abi_version()``.  The symbols are resolved on ``_lib.lib()``'s handle at first use, so importing this
 module loads nothing.
 """
-import ctypes
-
 from . import _lib
+from ._lib import c_f32, c_i64, c_int, c_p
 
 _ABI = 1   # snvc_iou3d_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_f32 = ctypes.c_float
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
 
 OVERLAP, IOU_BEV, IOU_3D = 0, 1, 2          # snvc_iou3d_pairwise `what`
 NMS_ROTATED, NMS_NORMAL = 0, 1              # snvc_iou3d_nms `kind`
@@ -30,19 +24,4 @@ SIGNATURES = {
     "snvc_iou3d_boxes_iou_bev_cpu": (c_int, [c_p, c_i64, c_p, c_i64, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_iou3d_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so iou3d ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_iou3d_abi_version", _ABI, "iou3d")

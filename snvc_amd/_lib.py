@@ -13,7 +13,7 @@ _lib = None
 _ABI = 6   # snvc_abi_version() this binding was written against
 
 c_i64 = ctypes.c_int64
-c_f32 = ctypes.c_float
+c_f = c_f32 = ctypes.c_float
 c_p = ctypes.c_void_p
 c_int = ctypes.c_int
 
@@ -164,15 +164,34 @@ def lib() -> ctypes.CDLL:
                 f"{LIB_PATH} is missing: the HIP extension has not been built "
                 "(run `python -c 'import __graft_entry__ as g; g.build()'` or `make -C snvc_amd/csrc`). "
                 "snvc_amd has no CPU fallback.")
-        handle = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so ABI version mismatch; rebuild it")
-        _lib = handle
+        _lib = _bind(ctypes.CDLL(LIB_PATH), SIGNATURES, "snvc_abi_version", _ABI, "")
     return _lib
+
+
+def _bind(handle, signatures, version_symbol, abi, what):
+    """Set ``signatures`` (name -> (restype, argtypes)) on ``handle`` and hold its ``version_symbol`` to ``abi``."""
+    for name, (res, args) in signatures.items():
+        fn = getattr(handle, name)  # AttributeError if the .so is stale
+        fn.restype = res
+        fn.argtypes = args
+    if getattr(handle, version_symbol)() != abi:
+        raise RuntimeError(f"libsnvc_hip.so {what + ' ' if what else ''}ABI version mismatch; rebuild it")
+    return handle
+
+
+def binder(signatures, version_symbol, abi, what):
+    """The ``lib`` callable of a self-versioned header's table module: ``_lib.lib()``'s handle, with ``signatures`` set and the
+    ABI checked at the first call.  ``lib.loaded()`` tells whether that call has happened; making a binder loads nothing."""
+    bound = None
+
+    def table_lib() -> ctypes.CDLL:
+        nonlocal bound
+        if bound is None:
+            bound = _bind(lib(), signatures, version_symbol, abi, what)
+        return bound
+
+    table_lib.loaded = lambda: bound is not None
+    return table_lib
 
 
 class Unsupported(RuntimeError):

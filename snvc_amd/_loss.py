@@ -15,12 +15,9 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import c_i64, c_int, c_p
 
 _ABI = 1   # snvc_loss_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
 
 # enum snvc_loss_kind
 MSE_ROWS, MSE_POSNEG, OCCUPANCY, OFFSET, SMOOTH_L1_MASKED, SIGMOID_FOCAL, SMOOTH_L1_ROWS = range(7)
@@ -59,22 +56,7 @@ SIGNATURES = {
     "snvc_loss_disparity_regression_backward": (c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_loss_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so loss ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_loss_abi_version", _ABI, "loss")
 
 
 # ------------------------------------------------------------------------------ the deferred input checks

@@ -8,11 +8,9 @@ loads nothing.
 import ctypes
 
 from . import _lib
+from ._lib import c_int, c_p
 
 _ABI = 1   # snvc_oiou_abi_version() this binding was written against
-
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
 
 BOXES, QUADS = 0, 1          # SNVC_OIOU_BOXES, SNVC_OIOU_QUADS
 DIOU, GIOU = 0, 1            # SNVC_OIOU_DIOU, SNVC_OIOU_GIOU
@@ -37,19 +35,4 @@ SIGNATURES = {
     "snvc_oiou_backward": (c_int, [_desc_p, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_oiou_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so oriented-IoU ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_oiou_abi_version", _ABI, "oriented-IoU")

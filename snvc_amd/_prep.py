@@ -8,15 +8,11 @@ module loads nothing.
 import ctypes
 
 from . import _lib
+from ._lib import c_f, c_i64, c_int, c_p
 
 _ABI = 1   # snvc_prep_abi_version() this binding was written against
 
 POOL_AB, POOL_C = 1, 2      # SNVC_PREP_POOL_AB, SNVC_PREP_POOL_C
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
-c_f = ctypes.c_float
 
 
 class PoolPlan(ctypes.Structure):
@@ -35,19 +31,4 @@ SIGNATURES = {
     "snvc_prep_plain_plane": (c_i64, [c_i64, c_i64]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_prep_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so pooled prep ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_prep_abi_version", _ABI, "pooled prep")

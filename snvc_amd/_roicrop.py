@@ -8,12 +8,9 @@ loads nothing.
 import ctypes
 
 from . import _lib
+from ._lib import c_i64, c_int, c_p
 
 _ABI = 1   # snvc_roicrop_abi_version() this binding was written against
-
-c_i64 = ctypes.c_int64
-c_p = ctypes.c_void_p
-c_int = ctypes.c_int
 
 MAX_SIDE = 32767       # SNVC_ROICROP_MAX_SIDE
 MAX_SAMPLES = 32767    # SNVC_ROICROP_MAX_SAMPLES
@@ -43,19 +40,4 @@ SIGNATURES = {
     "snvc_roicrop": (c_int, [_cfg_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p]),
 }
 
-_bound = None
-
-
-def lib() -> ctypes.CDLL:
-    """``_lib.lib()``'s handle with this table's signatures set and the ABI checked."""
-    global _bound
-    if _bound is None:
-        handle = _lib.lib()
-        for name, (res, args) in SIGNATURES.items():
-            fn = getattr(handle, name)  # AttributeError if the .so is stale
-            fn.restype = res
-            fn.argtypes = args
-        if handle.snvc_roicrop_abi_version() != _ABI:
-            raise RuntimeError("libsnvc_hip.so roicrop ABI version mismatch; rebuild it")
-        _bound = handle
-    return _bound
+lib = _lib.binder(SIGNATURES, "snvc_roicrop_abi_version", _ABI, "roicrop")

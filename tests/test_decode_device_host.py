@@ -25,14 +25,11 @@ HEADER = os.path.join(ROOT, "include", "snvc_decode.h")
 
 # ---------------------------------------------------------------------------------------------------- the binding
 def test_header_and_binding_agree():
+    """The mirrored constants and struct; names, parameters and the ABI number are held by tests/test_abi_tables_host.py."""
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_decode.SIGNATURES) and len(declared) == len(_decode.SIGNATURES) == 3
     for name, value in (("SNVC_DECODE_GRID", _decode.GRID), ("SNVC_DECODE_COORDS_F32", _decode.COORDS_F32),
                         ("SNVC_DECODE_COORDS_F64", _decode.COORDS_F64)):
         assert int(re.search(rf"{name} = (\d+)", text).group(1)) == value
-    L = _decode.lib()
-    assert L.snvc_decode_abi_version() == _decode._ABI == 1
     assert ctypes.sizeof(_decode.DecodeConfig) == 48
 
 

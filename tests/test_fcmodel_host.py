@@ -115,16 +115,12 @@ def test_restatement_gradients_equal_torch_autograd(c):
 
 # ---------------------------------------------------------------------------------------------------- binding, alias, model
 def test_header_and_binding_agree():
+    """The mirrored constant and the packed size; names, parameters and the ABI number are held by
+    tests/test_abi_tables_host.py."""
     from snvc_amd import _fc
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_fc.SIGNATURES) and len(declared) == len(_fc.SIGNATURES) == 6
     assert int(re.search(r"SNVC_FC_MAX_WIDTH = (\d+)", text).group(1)) == _fc.MAX_WIDTH
-    for name, (_, args) in _fc.SIGNATURES.items():      # one ctypes argument per declared parameter
-        params = re.search(rf"SNVC_API[^;(]*\b{name}\s*\(([^)]*)\)", text).group(1)
-        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
     L = _fc.lib()
-    assert L.snvc_fc_abi_version() == _fc._ABI == 1
     assert L.snvc_fc_packed_floats(18, 128, 1, 5) == 20 * 128 + 128 + 2 * (128 * 128 + 128) + 128 * 16 + 16
     assert L.snvc_fc_packed_floats(18, 40, 1, 5) < 0 and L.snvc_fc_packed_floats(18, 2048, 1, 5) < 0
 

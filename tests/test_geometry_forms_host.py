@@ -19,19 +19,12 @@ def _enum(entry):
 
 
 def test_header_and_binding_agree():
-    from snvc_amd import _forms, _lib
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", HEADER)
-    assert set(declared) == set(_forms.SIGNATURES) and len(declared) == len(_forms.SIGNATURES) == 9
-    assert not set(declared) & set(_lib.SIGNATURES)                  # snvc_hip.h's table is untouched
-    for name, (_, args) in _forms.SIGNATURES.items():                # one ctypes argument per declared parameter
-        params = re.search(rf"SNVC_API[^;(]*\b{name}\s*\(([^)]*)\)", HEADER).group(1)
-        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
+    """The info slots and the gather kinds; names, parameters and the ABI numbers are held by tests/test_abi_tables_host.py."""
+    from snvc_amd import _forms
     assert int(re.search(r"SNVC_FORMS_INFO = (\d+)", HEADER).group(1)) == _forms.INFO
     for info in (_forms.CV_FWD_INFO, _forms.CV_BWD_INFO, _forms.GATHER_FWD_INFO, _forms.GATHER_BWD_INFO, _forms.WGRAD_INFO,
                  _forms.CONV_FWD_INFO, _forms.FIRST_LAYER_INFO):
         assert len(info) == _forms.INFO
-    assert _forms.lib().snvc_forms_abi_version() == _forms._ABI == 4
-    assert _lib.lib().snvc_abi_version() == _lib._ABI                # snvc_hip.h's own number is untouched
     assert {k: v for k, v in _forms.enum_names(HEADER, "GATHER").items()} == {"F32": 0, "C8": 1, "SPLIT": 2} == {k.upper(): v for k, v in GC.KIND.items()}
 
 

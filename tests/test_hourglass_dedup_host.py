@@ -41,19 +41,9 @@ def L():
     return _hgdedup.lib()
 
 
-def test_header_binding_and_exports_agree(L):
-    from snvc_amd import _alias, _dedup, _fused, _hgdedup, _lib
+def test_header_binding_and_exports_agree():
+    """What is this header's own; names, parameters, exports and the ABI numbers are held by tests/test_abi_tables_host.py."""
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_hgdedup.SIGNATURES) and len(declared) == len(_hgdedup.SIGNATURES) == 8
-    pinned = set(_lib.SIGNATURES) | set(_fused.SIGNATURES) | set(_dedup.SIGNATURES) | set(_alias.SIGNATURES)
-    assert not set(declared) & pinned                                 # the pinned tables are untouched
-    for name, (_, args) in _hgdedup.SIGNATURES.items():               # one ctypes argument per declared parameter
-        params = re.search(rf"SNVC_API[^;(]*\b{name}\s*\(([^)]*)\)", text).group(1)
-        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
-        assert getattr(ctypes.CDLL(_lib.LIB_PATH), name)              # exported by the library itself
-    assert L.snvc_hgdedup_abi_version() == _hgdedup._ABI == 1
-    assert L.snvc_alias_abi_version() == 1 and L.snvc_dedup_abi_version() == 1      # the headers beside it keep their numbers
     # both forwards take snvc_alias_f16x3_conv3d_forward's arguments
     norm = lambda s: re.sub(r"\s+", " ", s).replace("in_desc", "in_alias").strip()  # noqa: E731
     alias = re.search(r"snvc_alias_f16x3_conv3d_forward\s*\(([^)]*)\)", open(os.path.join(ROOT, "include", "snvc_alias.h")).read()).group(1)

@@ -1,11 +1,10 @@
 """CPU checks of the HRNet backbone (snvc_amd.models.hrnet, include/snvc_hrnet.h): the module tree and state-dict keys
-against the reference's (tests/golden/hrnet_ref.npz, made by tests/golden/make_golden_hrnet.py), the header against the
-binding's table and the library's exports, argument validation before any device work, and the wiring into
-VernierScale and install_as_snvc."""
+against the reference's (tests/golden/hrnet_ref.npz, made by tests/golden/make_golden_hrnet.py), argument validation
+before any device work, and the wiring into VernierScale and install_as_snvc.  The header against the binding's table and
+the library's exports: tests/test_abi_tables_host.py."""
 import copy
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -61,17 +60,6 @@ def test_init_weights_loads_the_matching_keys(tmp_path):
     torch.save(part, tmp_path / "pre.pth")
     m.init_weights(str(tmp_path / "pre.pth"))
     assert torch.equal(m.conv2.weight, part["conv2.weight"]) and torch.equal(m.bn1.weight, torch.ones(64))
-
-
-def test_header_table_and_exports_agree(L):
-    hdr = open(os.path.join(ROOT, "include", "snvc_hrnet.h")).read()
-    declared = set(re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", hdr))
-    assert declared == set(_hrnet.SIGNATURES), declared ^ set(_hrnet.SIGNATURES)
-    assert not declared & set(_lib.SIGNATURES)
-    exports = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    for name in declared:
-        assert re.search(rf"\bT {name}$", exports, re.M), name
-    assert L.snvc_hrnet_abi_version() == _hrnet._ABI
 
 
 def _forward(L, ptrs, factors, extents, out=0x1000, shape=(1, 4, 8, 8)):

@@ -1,10 +1,9 @@
 """CPU checks of the rotated-box IoU / NMS family (include/snvc_iou3d.h, snvc_amd/extension/iou3d_nms): the host
 BEV IoU against the reference's own compiled CPU function (tests/golden/iou3d_ref.npz, made by
-tests/golden/make_golden_iou3d.py), the header against the binding's table and the library's exports, argument
-validation, and that importing / aliasing the module leaves the GPU alone."""
+tests/golden/make_golden_iou3d.py), argument validation, and that importing / aliasing the module leaves the GPU alone
+(the header against the binding's table and the library's exports: tests/test_abi_tables_host.py)."""
 import ctypes
 import os
-import re
 import subprocess
 import sys
 
@@ -12,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+import abi_tables
 from snvc_amd import _iou3d, _lib
 from snvc_amd.extension.iou3d_nms import iou3d_nms_utils as U
 from snvc_amd.extension.iou3d_nms import numerical_jaccobian as NJ
@@ -61,20 +61,6 @@ def test_empty_inputs_on_the_host(L):
     assert U.boxes_bev_iou_cpu(z, b).shape == (0, 3) and U.boxes_bev_iou_cpu(b, z).shape == (3, 0)
 
 
-def test_header_declarations_equal_the_binding_and_the_exports(L):
-    hdr = open(os.path.join(ROOT, "include", "snvc_iou3d.h")).read()
-    declared = set(re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", hdr))
-    assert declared == set(_iou3d.SIGNATURES), declared ^ set(_iou3d.SIGNATURES)
-    raw = ctypes.CDLL(_lib.LIB_PATH)
-    for name in declared:
-        assert getattr(raw, name) is not None
-    assert not declared & set(_lib.SIGNATURES)                       # snvc_hip.h's table is untouched
-
-
-def test_abi_version(L):
-    assert L.snvc_iou3d_abi_version() == 1 == _iou3d._ABI
-
-
 def test_argument_errors(L):
     p = ctypes.c_void_p(0)
     assert L.snvc_iou3d_pairwise(p, -1, p, 0, 1, 0, p, p, p) == 1
@@ -114,8 +100,10 @@ def test_numerical_jacobian_on_the_host():
 
 
 def test_import_and_alias_leave_the_gpu_untouched(tmp_path):
-    """A fresh interpreter: importing the module and install_as_snvc() (which imports every alias) neither load the
-    library nor initialise the GPU; the reference's import line resolves to this package."""
+    """A fresh interpreter: importing the module, every binding module and install_as_snvc() (which imports every alias)
+    neither load the library, nor bind a table, nor initialise the GPU; the reference's import line resolves to this package."""
+    tables = ", ".join(row.module for row in abi_tables.ROWS[1:])
+    assert len(abi_tables.ROWS) == 17 and "_iou3d" in tables
     for pkg in ("snvc", "snvc/extension"):
         (tmp_path / pkg).mkdir(parents=True)
         (tmp_path / pkg / "__init__.py").write_text("")
@@ -125,13 +113,13 @@ def test_import_and_alias_leave_the_gpu_untouched(tmp_path):
         f"sys.path[:0] = [{ROOT!r}, {str(tmp_path)!r}]\n"
         "import torch\n"
         "import snvc_amd\n"
-        "from snvc_amd import _lib, _iou3d\n"
+        f"from snvc_amd import _lib, {tables}\n"
         "import snvc_amd.extension.iou3d_nms.iou3d_nms_utils\n"
         "snvc_amd.install_as_snvc(backbone=False)\n"
         "from snvc.extension.iou3d_nms.iou3d_nms_utils import nms_gpu, boxes_iou3d_gpu, iou3d_nms_cuda\n"
         "from snvc.extension.iou3d_nms import iou3d_nms_utils as m\n"
         "assert m is snvc_amd.extension.iou3d_nms.iou3d_nms_utils and nms_gpu is m.nms_gpu\n"
-        "assert _lib._lib is None and _iou3d._bound is None, 'library loaded at import'\n"
+        f"assert _lib._lib is None and not any(m.lib.loaded() for m in ({tables})), 'library loaded at import'\n"
         "assert not torch.cuda.is_initialized(), 'GPU initialised at import'\n"
         "print('ok')\n")
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)

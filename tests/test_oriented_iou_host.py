@@ -324,17 +324,12 @@ def test_loss3d_names_still_raise_and_point_here():
 
 # ---------------------------------------------------------------------------------------------------- binding, alias
 def test_header_and_binding_agree():
+    """The struct's mirror, the constants and the tie rule; names, parameters and the ABI number are held by
+    tests/test_abi_tables_host.py."""
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_oiou.SIGNATURES) and len(declared) == len(_oiou.SIGNATURES) == 3
-    for name, (_, args) in _oiou.SIGNATURES.items():      # one ctypes argument per declared parameter
-        params = re.search(rf"SNVC_API[^;(]*\b{name}\s*\(([^)]*)\)", text).group(1)
-        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
     fields = re.findall(r"^\s+(?:const\s+)?(?:int32_t|int64_t|float)\s*\*?\s*(\w+);", re.search(r"typedef struct snvc_oiou_desc \{(.*?)\}", text, re.S).group(1), re.M)
     assert fields == [n for n, _ in _oiou.OiouDesc._fields_]
     assert int(re.search(r"#define SNVC_OIOU_OUT (\d+)", text).group(1)) == _oiou.OUT
-    L = _oiou.lib()
-    assert L.snvc_oiou_abi_version() == _oiou._ABI == 1
     source = open(os.path.join(ROOT, "snvc_amd", "csrc", "oriented_iou.hip")).read()
     # one tie rule in all three: 32 epsilons of the arithmetic at hand
     assert "kTie = 32.f * 1.1920929e-7f;" in source and np.float32(1.1920929e-7) == np.finfo(np.float32).eps

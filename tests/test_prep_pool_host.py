@@ -33,16 +33,10 @@ def widths(shape):
     return wu, wu_col
 
 
-def test_header_and_binding_agree(L):
-    from snvc_amd import _fused, _lib, _prep
+def test_header_and_binding_agree():
+    """The plan struct's mirror; names, parameters and the ABI number are held by tests/test_abi_tables_host.py."""
+    from snvc_amd import _prep
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_prep.SIGNATURES) and len(declared) == len(_prep.SIGNATURES) == 5
-    assert not set(declared) & (set(_lib.SIGNATURES) | set(_fused.SIGNATURES))      # the pinned tables are untouched
-    for name, (_, args) in _prep.SIGNATURES.items():                 # one ctypes argument per declared parameter
-        params = re.search(rf"SNVC_API[^;(]*\b{name}\s*\(([^)]*)\)", text).group(1)
-        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
-    assert L.snvc_prep_abi_version() == _prep._ABI == 1
     fields = re.search(r"typedef struct snvc_prep_pool_plan_t \{(.*?)\}", text, re.S).group(1)
     assert re.findall(r"int64_t (\w+)", fields) == [f[0] for f in _prep.PoolPlan._fields_]
     assert ctypes.sizeof(_prep.PoolPlan) == 8 * (2 + 3 + 3 + 1 + 3 + 1)

@@ -173,13 +173,12 @@ def test_the_table_is_torchs_normalisation():
 
 # ---------------------------------------------------------------------------------------------------- the binding and the class
 def test_header_and_binding_agree():
+    """The mirrored constants and the workspace query; names, parameters and the ABI number are held by
+    tests/test_abi_tables_host.py."""
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_roicrop.SIGNATURES) and len(declared) == len(_roicrop.SIGNATURES) == 3
     for macro, value in (("SNVC_ROICROP_MAX_SIDE", _roicrop.MAX_SIDE), ("SNVC_ROICROP_MAX_SAMPLES", _roicrop.MAX_SAMPLES)):
         assert int(re.search(rf"#define {macro} (\d+)", text).group(1)) == value
     L = _roicrop.lib()
-    assert L.snvc_roicrop_abi_version() == _roicrop._ABI == 1
     assert L.snvc_roicrop_workspace_bytes(0) == 0 and L.snvc_roicrop_workspace_bytes(3) > 0 and L.snvc_roicrop_workspace_bytes(3) % 8 == 0
     assert L.snvc_roicrop_workspace_bytes(-1) < 0 and L.snvc_roicrop_workspace_bytes(_roicrop.MAX_SAMPLES + 1) < 0
     assert _roicrop.ctypes.sizeof(_roicrop.RoICropConfig) == 56

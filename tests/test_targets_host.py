@@ -4,7 +4,6 @@ binding's table and the library's exports, and argument validation before any de
 import ctypes
 import os
 import re
-import subprocess
 
 import numpy as np
 import pytest
@@ -52,16 +51,9 @@ def L():
     return _targets.lib()
 
 
-def test_header_table_and_exports_agree(L):
+def test_header_table_and_exports_agree():
+    """The mirrored constants and struct; names, exports and the ABI number are held by tests/test_abi_tables_host.py."""
     hdr = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", hdr)
-    assert len(declared) == len(_targets.SIGNATURES) == 4
-    assert set(declared) == set(_targets.SIGNATURES), set(declared) ^ set(_targets.SIGNATURES)
-    assert not set(declared) & set(_lib.SIGNATURES)
-    exports = subprocess.run(["nm", "-D", "--defined-only", _lib.LIB_PATH], capture_output=True, text=True).stdout
-    for name in declared:
-        assert re.search(rf"\bT {name}$", exports, re.M), name
-    assert L.snvc_targets_abi_version() == _targets._ABI == 1
     assert f"SNVC_TARGETS_MAX_PARTS {_targets.MAX_PARTS}" in hdr and f"SNVC_TARGETS_MAX_SAMPLES {_targets.MAX_SAMPLES}" in hdr
     fields = re.search(r"typedef struct snvc_targets_grid \{(.*?)\} snvc_targets_grid;", hdr, re.S).group(1)
     fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)

@@ -28,17 +28,10 @@ def L():
     return _alias.lib()
 
 
-def test_header_binding_and_exports_agree(L):
-    from snvc_amd import _alias, _dedup, _fused, _lib
+def test_header_binding_and_exports_agree():
+    """What is this header's own; names, parameters, exports and the ABI number are held by tests/test_abi_tables_host.py."""
+    from snvc_amd import _alias
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_alias.SIGNATURES) and len(declared) == len(_alias.SIGNATURES) == 5
-    assert not set(declared) & (set(_lib.SIGNATURES) | set(_fused.SIGNATURES) | set(_dedup.SIGNATURES))      # the pinned tables are untouched
-    for name, (_, args) in _alias.SIGNATURES.items():                # one ctypes argument per declared parameter
-        params = re.search(rf"SNVC_API[^;(]*\b{name}\s*\(([^)]*)\)", text).group(1)
-        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
-        assert getattr(ctypes.CDLL(_lib.LIB_PATH), name)             # exported by the library itself
-    assert L.snvc_alias_abi_version() == _alias._ABI == 1
     # the aliased forward takes the plain one's arguments, declared in the same words
     norm = lambda s: re.sub(r"\s+", " ", s).strip()  # noqa: E731
     plain = re.search(r"snvc_fused_first_conv3d_forward\s*\(([^)]*)\)", open(os.path.join(ROOT, "include", "snvc_fused.h")).read()).group(1)

@@ -27,17 +27,9 @@ def L():
     return _dedup.lib()
 
 
-def test_header_binding_and_exports_agree(L):
-    from snvc_amd import _dedup, _fused, _lib
+def test_header_binding_and_exports_agree():
+    """What is this header's own; names, parameters, exports and the ABI number are held by tests/test_abi_tables_host.py."""
     text = open(HEADER).read()
-    declared = re.findall(r"SNVC_API\s+[\w\s\*]+?\b(snvc_\w+)\s*\(", text)
-    assert set(declared) == set(_dedup.SIGNATURES) and len(declared) == len(_dedup.SIGNATURES) == 3
-    assert not set(declared) & (set(_lib.SIGNATURES) | set(_fused.SIGNATURES))      # the pinned tables are untouched
-    for name, (_, args) in _dedup.SIGNATURES.items():                # one ctypes argument per declared parameter
-        params = re.search(rf"SNVC_API[^;(]*\b{name}\s*\(([^)]*)\)", text).group(1)
-        assert len(args) == (0 if params.strip() == "void" else params.count(",") + 1), name
-        assert getattr(ctypes.CDLL(_lib.LIB_PATH), name)             # exported by the library itself
-    assert L.snvc_dedup_abi_version() == _dedup._ABI == 1
     # the deduplicated forward takes the plain one's arguments, declared in the same words
     norm = lambda s: re.sub(r"\s+", " ", s).strip()  # noqa: E731
     plain = re.search(r"snvc_fused_first_conv3d_forward\s*\(([^)]*)\)", open(os.path.join(ROOT, "include", "snvc_fused.h")).read()).group(1)
